@@ -10,7 +10,10 @@ steps, L=1 control, complex128) through ``krotov_amd.optimize_pulses`` with
 storing chi(t_n) -> forward sweep with sequential pulse update -> tau, exactly
 the bracket the reference times per iteration (optimize.py:396 -> 510).  Inputs
 are synthetic (``krotov_amd.configs.config_c5``) and resident in HBM before the
-timed region.  One JSON line is printed by rank 0.
+timed region.  One JSON line is printed by rank 0; its ``ms_per_step`` is the
+wall time of one timed step (``--steps`` of them, after ``--warmup`` untimed
+ones).  ``--dump-outputs DIR`` writes what the last timed step returned to the
+caller as ``DIR/<name>.npy`` (``dump_outputs``).
 
 For N > 1 there is one rank per GPU.  Either a launcher provides them
 (``python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N``:
@@ -93,6 +96,41 @@ def build_id():
     except Exception:
         version = 'krotov_hip ?'
     return '%s %s' % (version, h.hexdigest()[:16])
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(res, dirname, limit=DUMP_LIMIT_BYTES, seed=0):
+    """``--dump-outputs DIR``: what the timed path handed its caller after the last step, as float64 ``DIR/<name>.npy``
+    (complex values as trailing (real, imaginary) pairs): ``optimized_controls`` (L, nt), ``tau_vals`` of the last
+    iteration (K, 2) and ``states``, the forward states at T (K, N, 2).  The inputs are seeded (krotov_amd.configs), so
+    two builds run with the same arguments can be compared file for file.  Should the arrays exceed ``limit`` bytes in
+    all, each keeps a fixed, seeded sample of its rows, sized to its share, and ``DIR/<name>_rows.npy`` names them."""
+    import numpy as np
+
+    def real(a):
+        a = np.asarray(a)
+        if np.iscomplexobj(a):
+            return np.stack([a.real, a.imag], axis=-1).astype(np.float64)
+        return a.astype(np.float64)
+
+    arrays = {
+        'optimized_controls': real([np.asarray(c) for c in res.optimized_controls]),
+        'tau_vals': real(res.tau_vals[-1]),
+        'states': real([np.asarray(s).ravel() for s in res.states]),
+    }
+    total = sum(a.nbytes for a in arrays.values())
+    # a sampled row costs its own bytes and 8 for its index; 256 bytes stay free for the header of every file written
+    share = (limit - 2 * 256 * len(arrays)) / sum(a.nbytes + 8 * len(a) for a in arrays.values())
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        if total > limit:
+            keep = max(1, int(len(a) * share))
+            rows = np.sort(np.random.default_rng(seed).choice(len(a), size=keep, replace=False))
+            a = a[rows]
+            np.save(os.path.join(dirname, name + '_rows.npy'), rows.astype(np.float64))
+        np.save(os.path.join(dirname, name + '.npy'), a)
 
 
 def pmc_traffic(kernel, K_loc, args):
@@ -451,9 +489,14 @@ def main():
     ap.add_argument('--rccl-leg-timeout', type=int, default=240, help='seconds the "rccl" side measurement may take')
     ap.add_argument('--force-dist', action='store_true',
                     help='run the multi-GPU code path (stepwise sweep + RCCL all-reduce per interval) even on 1 rank')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='after the timed steps, write what the headline measurement computed in its last step as '
+                         'DIR/<name>.npy (see dump_outputs)')
     ap.add_argument('--cpu-seconds', type=float, default=12.0)
     ap.add_argument('--cpu-procs', type=int, default=0, help='worker processes of the CPU baseline (0: every visible core)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
 
     import numpy as np
     import torch
@@ -499,7 +542,7 @@ def main():
     import krotov_amd
     from krotov_amd import configs, engine as _engine_mod
 
-    def measure(scaling):
+    def measure(scaling, dump_dir=None):
         K_total = args.K * world if scaling == 'weak' else args.K
         propagator = krotov_amd.propagators.expm
         if args.workload == 'c4':
@@ -621,6 +664,8 @@ def main():
                 diag = [mine]
 
         if rank == 0:
+            if dump_dir:
+                dump_outputs(res, dump_dir)
             K_loc = eng.K
             props = K_total * (args.nt - 1) * 2 * args.steps
             f_bw, f_up = algorithmic_flops(K_loc, args.N, args.nt, args.L)
@@ -781,7 +826,7 @@ def main():
                     os.environ[k] = v
 
     other = 'weak' if args.scaling == 'strong' else 'strong'
-    out = measure(args.scaling)
+    out = measure(args.scaling, dump_dir=args.dump_outputs)
     if rank == 0:
         out['n_ranks_seen'] = torch.distributed.get_world_size() if group is not None else 1
     else:

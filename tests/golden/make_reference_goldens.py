@@ -21,6 +21,7 @@ B. ``ref``     -- the reference's real ``krotov.optimize_pulses`` loop executed
    synthetic inputs of ``krotov_amd.configs``.  Outputs: all pulses, tau_vals.
 
 Usage:  python tests/golden/make_reference_goldens.py [dumps] [ref] [c5full] [c4full] [c5full5] [c4full5] [second_order]
+        [print_table] [print_debug] [summarize] [dump_continue]
 
 The reference is BSD-3-Clause (c) 2018-2024 Michael Goerz et al.; the fixtures
 derived from its shipped data keep that attribution (tests/golden/README.md).
@@ -547,6 +548,78 @@ def make_summarize_cases():
     print("\n".join(lines))
 
 
+def run_product_numpy_mode(spec, iter_stop, continue_from=None):
+    """(objectives, result) of this package's optimize_pulses with the numpy-mode plugins of tests/helpers.py."""
+    import krotov_amd
+    from krotov_amd import configs
+
+    sys.path.insert(0, os.path.dirname(HERE))
+    from helpers import numpy_plugins
+
+    objectives, pulse_options = configs.spec_to_objectives(spec, krotov_amd)
+    prop, mu, overlap = numpy_plugins(spec.is_super)
+    return objectives, krotov_amd.optimize_pulses(
+        objectives, pulse_options, spec.tlist, propagator=prop,
+        chi_constructor=getattr(krotov_amd.functionals, 'chis_' + spec.chi), mu=mu, overlap=overlap,
+        norm=np.linalg.norm, iter_stop=iter_stop, store_all_pulses=True, continue_from=continue_from)
+
+
+def _scipy_plugins(is_super):
+    """(propagator, mu) of the reference's numpy mode with scipy's expm."""
+    import scipy.linalg as la
+
+    f0 = (1.0 + 0j) if is_super else -1j
+
+    def expm(H, state, dt, c_ops=None, backwards=False, initialize=False):
+        f = f0.conjugate() if backwards else f0
+        A = f * H[0]
+        for part in H[1:]:
+            A = A + (f * part[1]) * part[0]
+        return la.expm(A * dt) @ state
+
+    def mu(objs, i_obj, pulses, mapping, i_pulse, n):
+        op = objs[i_obj].H[1 + i_pulse][0]
+        return (lambda s: 1j * (op @ s)) if is_super else (lambda s: op @ s)
+
+    return expm, mu
+
+
+def make_dump_continue_cases():
+    """This package's ``Result.dump(..., reference=True)`` after two iterations -> reference_format_<case>.dump; the
+    reference's own ``Result.load`` reads that file and its ``optimize_pulses(..., continue_from=...)`` continues it to
+    four iterations -> the optimized controls in ref_dump_continue.npz (one array per case; the cases are
+    DUMP_CONTINUE_CASES of tests/helpers.py)."""
+    from krotov_amd import configs
+
+    sys.path.insert(0, os.path.dirname(HERE))
+    from helpers import DUMP_CONTINUE_CASES
+
+    paths = {}
+    for name, builder in DUMP_CONTINUE_CASES.items():  # (all dumps first: they must be written without the real krotov)
+        _, res = run_product_numpy_mode(builder(configs), 2)
+        paths[name] = os.path.join(HERE, 'reference_format_%s.dump' % name)
+        res.dump(paths[name], reference=True)
+    krotov = import_reference_krotov()
+    out = {}
+    for name, builder in DUMP_CONTINUE_CASES.items():
+        spec = builder(configs)
+        objectives, pulse_options = configs.spec_to_objectives(spec, krotov)
+        res = krotov.result.Result.load(paths[name], objectives=objectives)
+        assert type(res).__module__ == 'krotov.result' and res.iters == [0, 1, 2], res.iters
+        assert res.message == 'Reached 2 iterations' and len(res.optimized_controls) == spec.L
+        assert isinstance(res.tlist, np.ndarray) and len(res.tau_vals) == 3 and len(res.all_pulses) == 3
+        expm, mu = _scipy_plugins(spec.is_super)
+        cont = krotov.optimize_pulses(
+            objectives, pulse_options, spec.tlist, propagator=expm,
+            chi_constructor=getattr(krotov.functionals, 'chis_' + spec.chi), mu=mu,
+            overlap=lambda a, b: complex(np.vdot(a, b)), norm=np.linalg.norm, iter_stop=4, continue_from=res,
+            store_all_pulses=True)
+        assert cont.iters == [0, 1, 2, 3, 4], cont.iters
+        out[name] = np.array(cont.optimized_controls)
+    np.savez_compressed(os.path.join(HERE, 'ref_dump_continue.npz'), **out)
+    print('ref_dump_continue:', {k: v.shape for k, v in out.items()})
+
+
 def make_c5_full():
     """Headline configuration through the real reference loop: 1 iteration
     (~2.5 sweeps * 256 * 4000 props at ~0.8 ms each => ~35 min, one core)."""
@@ -614,6 +687,8 @@ if __name__ == '__main__':
         make_print_debug_cases()
     if 'summarize' in what:
         make_summarize_cases()
+    if 'dump_continue' in what:
+        make_dump_continue_cases()
     for w in what:
         if w in REF_CASES:
             make_ref_fixtures([w])

@@ -9,6 +9,13 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
 
 CHI = {'re': ko.chis_re, 'ss': ko.chis_ss, 'sm': ko.chis_sm, 'hs': ko.chis_hs}
 
+# name: builder of krotov_amd.configs -> spec; tests/test_reference_dump_compat.py and the fixtures
+# make_reference_goldens.py dump_continue made for it
+DUMP_CONTINUE_CASES = {
+    'c1': lambda c: c.config_c1(nt=80),
+    'c5_L3': lambda c: c.config_c5(K=3, N=6, nt=41, L=3, distinct=True),
+}
+
 
 def golden(name):
     return np.load(os.path.join(GOLDEN, name + '.npz'))

@@ -809,8 +809,7 @@ def test_sparse_operator_sweeps(name, force_generic, monkeypatch):
 
     builder, family = SPARSE_CASES[name]
     if force_generic:
-        if family == 'generic/csr':
-            pytest.skip("already the generic kernels")
+        # (cases the engine runs on the generic kernels by itself: the switch must leave them there, same numbers)
         monkeypatch.setenv('KH_KERNEL', 'generic')
         family = 'generic/csr'
     spec = builder()
@@ -1526,14 +1525,15 @@ def _two_rank_spec(case):
         return spec
     if case == 'c4k25':  # 13 + 12 objectives per rank: two objectives per cooperative workgroup (7 + 6 column groups)
         return configs.config_c4(d=9, nt=31, n_logical=5)
-    if case == 'c5w8':  # BASELINE config 5's 8-GPU partition: 8 x 32 objectives of N = 64 -- 256 workgroups, one per CU
+    if case in ('c5w8', 'c5w5'):  # BASELINE config 5's 8-GPU partition: 8 x 32 objectives of N = 64 -- 256 workgroups, one
+        # per CU; as 52 + 4 x 51 on five ranks, the most that share one device (MAX_RANKS_SHARING_A_GPU)
         spec = configs.config_c5(K=256, N=64, nt=25, L=1)
         spec.chi = 'sm'
         return spec
     if case == 'c5w4':  # ... and its 4-GPU partition cut down to 4 x 9 (uneven shards: 36 = 9 + 9 + 9 + 9; L = 1)
         spec = configs.config_c5(K=38, N=64, nt=41, L=1)  # 38 -> 10 + 10 + 9 + 9
         return spec
-    if case in ('c4w4', 'c4w8'):  # BASELINE config 4's partition: 16 density matrices as 4 x 4 / 8 x 2 (N = 81 here)
+    if case in ('c4w4', 'c4w8', 'c4w5'):  # BASELINE config 4's partition: 16 density matrices as 4 x 4 / 8 x 2 / 4 + 4 x 3 (N = 81 here)
         return configs.config_c4(d=9, nt=41, n_logical=4)
     if case == 'sparse':  # sparse Liouvillians through DensityMatrixODEPropagator: the matrix-in-registers kernels, 2 + 2
         return configs.config_sparse_lindblad(d=9, nt=41, K=4)
@@ -1558,6 +1558,24 @@ def _rank_placement(rank, world):
     n_dev = max(1, torch.cuda.device_count())
     own = n_dev >= world
     return rank % n_dev, os.environ.get('KH_DIST_BACKEND', 'nccl' if own else 'gloo'), own
+
+
+# Ranks that share one device each hold it from a process of their own, and the test process holds it too.  The suite
+# keeps to at most six processes on a GPU at once (shared GPU nodes stop a run beyond that): up to five ranks share a
+# device (world 5 covers the one-device protocol beyond four ranks), more ranks need a device each.
+MAX_PROCESSES_ON_A_GPU = 6
+MAX_RANKS_SHARING_A_GPU = MAX_PROCESSES_ON_A_GPU - 1
+
+
+def _skip_unless_devices_for(world):
+    """Skip (before any work) a test of ``world`` ranks that would put more than MAX_RANKS_SHARING_A_GPU of them on one
+    device: it then needs a GPU per rank."""
+    import torch
+
+    n_dev = torch.cuda.device_count()
+    if world > MAX_RANKS_SHARING_A_GPU and n_dev < world:
+        pytest.skip("needs %d GPUs (one per rank), found %d: %d ranks sharing one GPU would be %d processes on it, more "
+                    "than the %d the suite keeps to" % (world, n_dev, world, world + 1, MAX_PROCESSES_ON_A_GPU))
 
 
 def _two_rank_worker(rank, world, port, queue, case='c5'):
@@ -1729,18 +1747,23 @@ def _check_placement(out, world, windows):
     return True
 
 
-@pytest.mark.parametrize('case,world', [('c5w8', 8), ('c5w4', 4), ('c4w4', 4), ('c4w8', 8), ('c5w4L2', 4)])
+@pytest.mark.parametrize('case,world', [('c5w8', 8), ('c5w4', 4), ('c4w4', 4), ('c4w8', 8), ('c5w4L2', 4), ('c5w5', 5),
+                                        ('c4w5', 5)])
 def test_ranks_sharded_on_one_gpu_world_4_and_8(case, world):
     """BASELINE's partitions at world = 4 and 8: config 5 as 8 x 32 objectives of N = 64 -- its
     256 workgroups are co-resident on the one MI355X, so the whole cross-rank protocol (IPC windows opened by 7 peers,
     system-scope publication by each rank's leader, every workgroup polling its own window, epochs across sweeps) runs
     for real, minus the xGMI link --, config 4's 16 density matrices as 4 x 4 and 8 x 2.  All ranks must arrive at
-    bit-identical pulses, within 1e-12 of the oracle, and through the peer windows."""
+    bit-identical pulses, within 1e-12 of the oracle, and through the peer windows.  World 8 needs a GPU per rank
+    (MAX_RANKS_SHARING_A_GPU); on one device the same partitions run as five ranks (c5w5: 52 + 4 x 51 objectives,
+    c4w5: 4 + 4 x 3 density matrices)."""
+    _skip_unless_devices_for(world)
     out = _run_ranks(world, case)
     spec = _two_rank_spec(case)
     ref = oracle_optimize(spec, 2)
     tol = 1e-12 if case.startswith('c5') else 1e-11
-    want_kernel = {'c5w8': 'tile64q2/512', 'c5w4': 'tile64q2/512', 'c5w4L2': 'tile64/512'}.get(case, 'coop16/mfma')
+    want_kernel = {'c5w8': 'tile64q2/512', 'c5w5': 'tile64q2/512', 'c5w4': 'tile64q2/512',
+                   'c5w4L2': 'tile64/512'}.get(case, 'coop16/mfma')
     assert len(out) == world
     for _, pulses, tau, used_p2p, kernel, _diag in out:
         assert np.abs(pulses - ref['all_pulses']).max() < tol * max(1.0, np.abs(ref['all_pulses']).max())
@@ -2335,6 +2358,37 @@ def test_update_kernel_series_regimes(name):
     assert np.abs(out[2] - ref_ga).max() < 1e-12 * max(1.0, np.abs(ref_ga).max())
 
 
+def test_bench_dump_outputs_match_the_oracle(tmp_path):
+    """``python bench.py --dump-outputs DIR`` end to end on the device path (the final states fetched from the device on
+    first access, the tau values from the device): one warm-up and one timed Krotov iteration of a small config-5
+    ensemble; the three files must hold the oracle's two iterations on the same seeded inputs."""
+    import json
+    import subprocess
+    import sys
+
+    from krotov_amd.conversions import pulse_onto_tlist
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / 'dump'
+    cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '1', '--warmup', '1', '--K', '8',
+           '--nt', '101', '--no-cpu-baseline', '--no-config4', '--no-variants', '--no-sparse', '--dump-outputs', str(out)]
+    proc = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert proc.returncode == 0, proc.stderr[-2000:]
+    rec = json.loads([ln for ln in proc.stdout.splitlines() if ln.startswith('{')][-1])
+    assert rec['steps'] == 1 and rec['warmup'] == 1 and rec['ms_per_step'] > 0
+    assert sorted(os.listdir(str(out))) == ['optimized_controls.npy', 'states.npy', 'tau_vals.npy']
+    got = {n: np.load(str(out / (n + '.npy'))) for n in ('optimized_controls', 'tau_vals', 'states')}
+    assert all(a.dtype == np.float64 for a in got.values())
+    ref = oracle_optimize(configs.config_c5(K=8, N=64, nt=101, L=1), 2)
+    want_controls = np.array([pulse_onto_tlist(p) for p in ref['all_pulses'][-1]])
+    assert got['optimized_controls'].shape == want_controls.shape == (1, 101)
+    assert np.abs(got['optimized_controls'] - want_controls).max() < 1e-11 * max(1.0, np.abs(want_controls).max())
+    assert got['tau_vals'].shape == (8, 2) and got['states'].shape == (8, 64, 2)
+    assert np.abs(got['tau_vals'][:, 0] + 1j * got['tau_vals'][:, 1] - ref['tau_vals'][-1]).max() < 1e-11
+    assert np.abs(got['states'][..., 0] + 1j * got['states'][..., 1] - ref['fw_T']).max() < 1e-11
+    assert abs(rec['final_J_T_re'] - (1 - np.mean(got['tau_vals'][:, 0]))) < 1e-12
+
+
 @pytest.mark.no_oracle
 def test_bench_self_launches_two_ranks(tmp_path):
     """``python bench.py --gpus 2`` with no launcher and no WORLD_SIZE in the environment -- the form the driver's
@@ -2385,7 +2439,7 @@ def test_bench_two_gpus_strong_scaling_where_the_box_has_them():
     import torch
 
     if torch.cuda.device_count() < 2:
-        pytest.skip("one GPU in this box: nothing crosses xGMI")
+        pytest.skip("needs 2 GPUs, found %d: nothing crosses xGMI" % torch.cuda.device_count())
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     env.pop('KH_DIST_BACKEND', None)
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -2429,12 +2483,14 @@ def test_bench_gpus_8_dry_run_on_one_gpu(tmp_path):
     by test_ranks_sharded_on_one_gpu_world_4_and_8[c4w8]: at full size with EIGHT processes on ONE device it works but
     takes minutes -- 155 s for two iterations, measured with scripts/debug_ranks.py c4full 8 -- because a device runs the
     kernels of at most four hardware queues at once and ranks that wait for each other inside their kernels then wait
-    for a queue switch in every interval; with one rank per GPU that cannot happen.)"""
+    for a queue switch in every interval; with one rank per GPU that cannot happen.)  Needs a GPU per rank
+    (MAX_RANKS_SHARING_A_GPU)."""
     import json
     import subprocess
     import sys
     import time
 
+    _skip_unless_devices_for(8)
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     env.pop('KH_DIST_BACKEND', None)
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

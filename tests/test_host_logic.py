@@ -392,6 +392,46 @@ def test_bench_starts_its_own_ranks(monkeypatch):
     assert seen['env'].get('HSA_ENABLE_IPC_MODE_LEGACY') == '0'
 
 
+def test_bench_dump_outputs_writes_what_the_caller_received(tmp_path):
+    """``bench.py --dump-outputs DIR`` (bench.dump_outputs): the optimized controls, the last iteration's tau values and
+    the forward states at T of a result, as float64 .npy files with complex values split into (real, imaginary);
+    beyond the size limit a seeded sample of rows, the same one every time, with its row indices beside it."""
+    import importlib
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    if root not in sys.path:
+        sys.path.insert(0, root)
+    bench = importlib.import_module('bench')
+    spec = configs.config_c5(K=40, N=16, nt=21, L=2, distinct=True)
+    objectives, pulse_options = configs.spec_to_objectives(spec, krotov_amd)
+    prop, mu, overlap = numpy_plugins(spec.is_super)
+    res = krotov_amd.optimize_pulses(objectives, pulse_options, spec.tlist, propagator=prop,
+                                     chi_constructor=krotov_amd.functionals.chis_re, mu=mu, overlap=overlap,
+                                     norm=np.linalg.norm, iter_stop=2)
+    bench.dump_outputs(res, str(tmp_path / 'all'))
+    got = {n: np.load(str(tmp_path / 'all' / (n + '.npy'))) for n in ('optimized_controls', 'tau_vals', 'states')}
+    assert sorted(os.listdir(str(tmp_path / 'all'))) == ['optimized_controls.npy', 'states.npy', 'tau_vals.npy']
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert np.array_equal(got['optimized_controls'], np.array(res.optimized_controls, dtype=np.float64))
+    tau = np.asarray(res.tau_vals[-1])
+    assert got['tau_vals'].shape == (40, 2) and np.array_equal(got['tau_vals'][:, 0] + 1j * got['tau_vals'][:, 1], tau)
+    states = np.array([np.asarray(s).ravel() for s in res.states])
+    assert got['states'].shape == (40, 16, 2) and np.array_equal(got['states'][..., 0] + 1j * got['states'][..., 1], states)
+
+    limit = sum(a.nbytes for a in got.values()) // 2
+    for run in ('a', 'b'):
+        bench.dump_outputs(res, str(tmp_path / run), limit=limit)
+    files = sorted(os.listdir(str(tmp_path / 'a')))
+    assert sum(os.path.getsize(str(tmp_path / 'a' / f)) for f in files) <= limit
+    for f in files:
+        assert np.array_equal(np.load(str(tmp_path / 'a' / f)), np.load(str(tmp_path / 'b' / f)))
+    for name in ('tau_vals', 'states'):
+        rows = np.load(str(tmp_path / 'a' / (name + '_rows.npy'))).astype(int)
+        assert 1 <= len(rows) < 40 and np.all(np.diff(rows) > 0)
+        assert np.array_equal(np.load(str(tmp_path / 'a' / (name + '.npy'))), got[name][rows])
+
+
 def test_update_sweep_retry_ladder_on_the_host(monkeypatch, caplog):
     """``_HipBackend.iterate`` after KH_ERR_TIMEOUT (the single-launch update sweep's workgroups were not all resident):
     half the workgroups, then an eighth, through ``set_update_workgroups`` -- two rungs at most, each costs a timed-out

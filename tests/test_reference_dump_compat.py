@@ -3,16 +3,16 @@
 Part 1 runs anywhere (no GPU, no reference): the file names only classes / functions that exist in an environment
 with the reference and NumPy 1.x or 2.x installed, and this package's own Result.load reads it back.
 
-Part 2 runs where the reference's sources are present (this build container: /root/reference; never the GPU box): a
-separate process imports the REAL ``krotov`` package (QuTiP & friends stubbed, as tests/golden/make_reference_goldens.py
-does), loads the file with the reference's own ``krotov.result.Result.load`` and CONTINUES the optimisation with the
-reference's own ``optimize_pulses(..., continue_from=...)``; the pulses it arrives at must be the ones this package
-arrives at when it continues the same result itself."""
+Part 2 checks against what the REAL ``krotov`` package did with such a dump (QuTiP & friends stubbed;
+``tests/golden/make_reference_goldens.py dump_continue`` ran it and stored the result in tests/golden/): it loaded the
+file with its own ``krotov.result.Result.load`` and CONTINUED the optimisation with its own
+``optimize_pulses(..., continue_from=...)``; the pulses it arrived at must be the ones this package arrives at when it
+continues the same result itself."""
 import os
+import pickle
 import pickletools
-import subprocess
 import sys
-import textwrap
+import time
 
 import numpy as np
 import pytest
@@ -20,10 +20,10 @@ import pytest
 import krotov_amd
 from krotov_amd import configs
 
-from helpers import numpy_plugins
+from helpers import DUMP_CONTINUE_CASES, numpy_plugins
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REFERENCE = '/root/reference/src/krotov'
+GOLDEN = os.path.join(ROOT, 'tests', 'golden')
 
 ALLOWED_GLOBALS = {
     'krotov.result Result', 'krotov.objectives _Objective_reduce_init', 'krotov.objectives _ControlPlaceholder',
@@ -85,53 +85,80 @@ def test_reference_format_dump_turns_numpy_scalars_into_python_scalars(tmp_path)
     assert [type(v) for v in back.iter_seconds] == [int, float]
 
 
-_CHILD = textwrap.dedent('''
-    import sys
-    sys.path.insert(0, {root!r}); sys.path.insert(0, {tests!r}); sys.path.insert(0, {golden!r})
-    import numpy as np
-    import make_reference_goldens as gen          # the committed generator: imports the REAL reference with stubs
-    from krotov_amd import configs
-    krotov = gen.import_reference_krotov()         # (sets krotov.Objective.type_checking = False: NumPy mode)
-    spec = {spec_expr}
-    objectives, pulse_options = configs.spec_to_objectives(spec, krotov)
-    res = krotov.result.Result.load({path!r}, objectives=objectives)
-    assert type(res).__module__ == 'krotov.result' and res.iters == [0, 1, 2], res.iters
-    assert res.message == 'Reached 2 iterations' and len(res.optimized_controls) == spec.L
-    assert isinstance(res.tlist, np.ndarray) and len(res.tau_vals) == 3 and len(res.all_pulses) == 3
-    import scipy.linalg as la
-    f0 = (1.0 + 0j) if spec.is_super else -1j
-    def expm(H, state, dt, c_ops=None, backwards=False, initialize=False):
-        f = f0.conjugate() if backwards else f0
-        A = f * H[0]
-        for part in H[1:]:
-            A = A + (f * part[1]) * part[0]
-        return la.expm(A * dt) @ state
-    def mu(objs, i_obj, pulses, mapping, i_pulse, n):
-        op = objs[i_obj].H[1 + i_pulse][0]
-        return (lambda s: 1j * (op @ s)) if spec.is_super else (lambda s: op @ s)
-    out = krotov.optimize_pulses(
-        objectives, pulse_options, spec.tlist, propagator=expm,
-        chi_constructor=getattr(krotov.functionals, 'chis_' + spec.chi), mu=mu,
-        overlap=lambda a, b: complex(np.vdot(a, b)), norm=np.linalg.norm, iter_stop=4, continue_from=res,
-        store_all_pulses=True)
-    assert out.iters == [0, 1, 2, 3, 4], out.iters
-    np.save({out!r}, np.array(out.optimized_controls))
-''')
+def _globals(path):
+    with open(path, 'rb') as fh:
+        return {arg for op, arg, _ in pickletools.genops(fh.read()) if op.name == 'GLOBAL'}
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="needs the reference's sources (build container only)")
-@pytest.mark.parametrize('name', ['c1', 'c5_L3'])
+class _Opaque:
+    """Stand-in for every class or function a dump names, except NumPy's array pieces and the builtins: keeps what the
+    unpickler hands it (constructor arguments, state), so that two dumps can be compared by structure."""
+
+    def __init__(self, *args):
+        self.args = args
+
+    def __setstate__(self, state):
+        self.state = state
+
+
+class _StructureUnpickler(pickle.Unpickler):
+    REAL = {('numpy.core.multiarray', '_reconstruct'), ('numpy._core.multiarray', '_reconstruct'), ('numpy', 'ndarray'),
+            ('numpy', 'dtype'), ('time', 'struct_time'), ('_codecs', 'encode'), ('builtins', 'complex'),
+            ('__builtin__', 'complex')}
+
+    def find_class(self, module, name):
+        if (module, name) in self.REAL:
+            if module == '__builtin__':
+                module = 'builtins'
+            if module == 'numpy.core.multiarray' and hasattr(np, '_core'):
+                module = 'numpy._core.multiarray'
+            return super().find_class(module, name)
+        return type('%s.%s' % (module, name), (_Opaque,), {})
+
+
+def _structure(x):
+    """What a loader meets in a dump, without the numbers: class names, attribute names, nesting, lengths, array dtypes
+    and shapes, scalar types, strings (the local-time stamps only as such: they depend on when and where)."""
+    if isinstance(x, _Opaque):
+        return (type(x).__name__, _structure(getattr(x, 'args', None)), _structure(getattr(x, 'state', None)))
+    if isinstance(x, dict):
+        return ('dict', tuple((k, _structure(x[k])) for k in sorted(x, key=repr)))
+    if isinstance(x, (list, tuple)) and not isinstance(x, time.struct_time):
+        return (type(x).__name__, tuple(_structure(v) for v in x))
+    if isinstance(x, np.ndarray):
+        return ('ndarray', x.dtype.str, x.shape)
+    if isinstance(x, str):
+        return ('str', x)
+    return (type(x).__name__,)
+
+
+def _load_structure(path):
+    with open(path, 'rb') as fh:
+        return _structure(_StructureUnpickler(fh).load())
+
+
+@pytest.mark.parametrize('name', sorted(DUMP_CONTINUE_CASES))
 def test_the_reference_loads_the_dump_and_continues_it(name, tmp_path):
-    spec_expr = "configs.config_c1(nt=80)" if name == 'c1' else "configs.config_c5(K=3, N=6, nt=41, L=3, distinct=True)"
-    spec = eval(spec_expr)
+    """The reference's side is stored in tests/golden/ (``make_reference_goldens.py dump_continue``): the dump this package
+    wrote after two iterations, which the reference's own ``Result.load`` read, and the controls the reference's
+    ``optimize_pulses(..., continue_from=...)`` arrived at from it after four.  The dump written now must be that one
+    (the same classes, functions, attributes, nesting, array shapes and types; the same numbers), and continuing it here
+    must arrive at the reference's pulses."""
+    spec = DUMP_CONTINUE_CASES[name](configs)
     objectives, res = _run_here(spec, 2)
-    path, out = str(tmp_path / 'result.dump'), str(tmp_path / 'continued.npy')
+    path = str(tmp_path / 'result.dump')
     res.dump(path, reference=True)
-    child = _CHILD.format(root=ROOT, tests=os.path.join(ROOT, 'tests'), golden=os.path.join(ROOT, 'tests', 'golden'),
-                          spec_expr=spec_expr, path=path, out=out)
-    proc = subprocess.run([sys.executable, '-c', child], capture_output=True, text=True, timeout=600)
-    assert proc.returncode == 0, proc.stderr[-3000:]
-    theirs = np.load(out)
+    shown = os.path.join(GOLDEN, 'reference_format_%s.dump' % name)
+    assert _globals(path) == _globals(shown)
+    assert _load_structure(path) == _load_structure(shown)
+    now, then = (krotov_amd.result.Result.load(p, objectives=objectives) for p in (path, shown))
+    assert now.iters == then.iters == [0, 1, 2] and now.message == then.message
+    for field in ('optimized_controls', 'all_pulses'):
+        a, b = np.array(getattr(now, field)), np.array(getattr(then, field))
+        assert a.shape == b.shape and np.abs(a - b).max() < 1e-13 * max(1.0, np.abs(b).max()), field
+    assert np.abs(np.array(now.tau_vals, dtype=complex) - np.array(then.tau_vals, dtype=complex)).max() < 1e-13
+    assert np.array_equal(now.tlist, then.tlist)
+    theirs = np.load(os.path.join(GOLDEN, 'ref_dump_continue.npz'))[name]
     _, mine = _run_here(spec, 4, continue_from=krotov_amd.result.Result.load(path, objectives=objectives))
     assert mine.iters == [0, 1, 2, 3, 4]
     assert np.abs(theirs - np.array(mine.optimized_controls)).max() < 1e-12 * max(1.0, np.abs(theirs).max())
