@@ -22,6 +22,7 @@
 #include <set>
 #include <string>
 #include <tuple>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -32,13 +33,7 @@
 #include "kh_tile64s.h"
 #include "kh_tile64x.h"
 #include "kh_tile64q2.h"
-#ifdef KH_WITH_Q4  // experiment build only (scripts/experiments/kh_tile64q4.h: 1024-thread plain sweep, measured 71 % slower)
-#include "../../scripts/experiments/kh_tile64q4.h"
-#endif
 #include "kh_coop.h"
-#ifdef KH_WITH_C4W  // experiment build only (scripts/experiments/kh_coop4w.h: rows over waves, measured slower)
-#include "../../scripts/experiments/kh_coop4w.h"
-#endif
 #include "kh_mini.h"
 #include "kh_ell.h"
 #include "kh_tilen.h"
@@ -59,6 +54,13 @@ static int kh_fail(int code, const char *fmt, ...) {
     return code;
 }
 
+// a step that reports a status of its own
+#define KH_TRY(step)                        \
+    do {                                    \
+        const int _rc = (step);             \
+        if (_rc != KH_OK) return _rc;       \
+    } while (0)
+
 #define KH_HIP(call)                                                                          \
     do {                                                                                      \
         hipError_t _e = (call);                                                               \
@@ -69,31 +71,139 @@ static int kh_fail(int code, const char *fmt, ...) {
 
 enum KernelKind { KIND_GENERIC = 0, KIND_TILE_RPT2 = 1, KIND_TILE_RPT1 = 2, KIND_TILE_Q2 = 3, KIND_COOP = 4, KIND_ELL = 5, KIND_TILEN = 6, KIND_TILEX = 7 /* plain sweeps only: kind_store */ };
 
+// Switches, read from the environment ONCE, at creation (read_switches; not per launch, not per process: engines with
+// different settings coexist)
+struct KhSwitches {
+    std::string kernel;  // KH_KERNEL (testing): "generic" | "tile256" | "tile512" | "q2" | "mini" | "coop" | "tilen" | "tilex" | "ellstream"
+    bool kernel_set = false;
+    bool kernel_is(const char *name) const { return kernel_set && kernel == name; }
+    bool taylor, no_adj, near_imag, ellstream, stepwise, stream, coop_xcd, coop_sq, coop_adj, tn_h1reg, tx, q2_store, ens2, gen_adj;
+    double ell_cap;
+    int stream_G, coop_cols, ens, ens_min_k, ens_ncg;
+    bool coop_launch, q2_single, tile_single, coop_single, poll_delay_set, timeout_set;
+    int poll_delay, adj_poll_delay, coop_poll_delay;  // (s_sleep units of 64 cycles)
+    long long timeout_ticks;                          // (100 MHz ticks)
+    int p2p_fail_at, p2p_fail_rank, p2p_fail_sweep;
+};
+
+// Each switch keeps its own reading: "set and != 0" (on), "set and == 0" (off), a number, or (KH_KERNEL) a name.
+static KhSwitches read_switches() {
+    auto on = [](const char *name) { const char *d = getenv(name); return d != nullptr && atoi(d) != 0; };
+    auto off = [](const char *name) { const char *d = getenv(name); return d != nullptr && atoi(d) == 0; };
+    auto num = [](const char *name, int dflt) { const char *d = getenv(name); return d != nullptr ? atoi(d) : dflt; };
+    KhSwitches s;
+    if (const char *d = getenv("KH_KERNEL")) s.kernel = d, s.kernel_set = true;
+    s.taylor = on("KH_TAYLOR");                // plain Taylor coefficients everywhere (A/B)
+    s.no_adj = on("KH_NO_ADJ");                // <chi|H phi> on the forward side (A/B; dense operators)
+    s.near_imag = !off("KH_NEAR_IMAG");        // =0: Taylor instead of the near-imaginary form's coefficients (A/B)
+    s.ell_cap = 0.0;                           // KH_ELL_CAP (> 0): another theta cap of the padded-row kernels' Chebyshev form
+    if (const char *d = getenv("KH_ELL_CAP")) s.ell_cap = atof(d);
+    s.ellstream = !on("KH_NO_ELLSTREAM");      // no streamed padded-row form
+    s.stepwise = !on("KH_NO_STEPWISE");        // no register-tile kernel with one launch per interval
+    s.stream = !on("KH_NO_STREAM");            // that launch per interval instead of the streaming kernel (A/B)
+    s.stream_G = num("KH_STREAM_G", 0);        // workgroups of the streaming kernel (testing)
+    s.coop_cols = num("KH_COOP_COLS", 0);      // objectives per cooperative workgroup, 2 | 4 | 16 (testing)
+    s.coop_xcd = !off("KH_COOP_XCD");          // =0: no column group per XCD
+    s.coop_sq = !on("KH_COOP_NOSQ");           // no A^2 chain in the cooperative kernels
+    s.coop_adj = !on("KH_COOP_NO_ADJ");        // the cooperative update sweep's sums by one more round per interval
+    s.tn_h1reg = !off("KH_TN_H1REG");          // =0: the tilen kernels stream the control operator
+    s.tx = !off("KH_TX");                      // =0: no tile64x kernels (A/B)
+    s.q2_store = !off("KH_Q2_STORE");          // =0: the plain sweeps take the update sweep's own family (A/B)
+    s.ens = num("KH_ENS", -1);                 // 0: no ensemble kernel; 1: for any K (testing)
+    s.ens_min_k = num("KH_ENS_MINK", 257);     // smallest K that takes it
+    s.ens_ncg = num("KH_ENS_NCG", 0);          // its column groups, 1 | 2 | 4 | 8 (testing)
+    s.ens2 = !off("KH_ENS2");                  // =0: no A^2-chain ensemble kernel (A/B)
+    s.gen_adj = !off("KH_GEN_ADJ");            // =0: the generic kernels' update sums stay on the forward side
+    s.coop_launch = !off("KH_COOP_LAUNCH");    // =0: plain launches instead of cooperative ones (A/B timing)
+    s.q2_single = !off("KH_Q2_SINGLE");        // =0: the instantiations with the cross-GPU stage on one GPU too (A/B)
+    s.tile_single = !off("KH_TILE_SINGLE");    // =0: the same for the one-term-per-phase kernels
+    s.coop_single = !off("KH_COOP_SINGLE");    // =0: the same for the cooperative kernels' adjoint-side form
+    // head start of the update-sum stores, ~0.4 us: measured best (one control); given in the environment, several
+    // controls do not apply their own default
+    s.poll_delay_set = getenv("KH_POLL_DELAY") != nullptr;
+    s.poll_delay = num("KH_POLL_DELAY", 16);
+    s.adj_poll_delay = num("KH_ADJ_DELAY", 0);  // the same where a matrix-vector product already sits between store and poll
+    // the same for the cooperative kernels' block exchange (a polling pass is four 16-byte loads per lane there: an
+    // early, stale pass costs little -- measured 0 best)
+    s.coop_poll_delay = num("KH_COOP_DELAY", 0);
+    // bound on any in-kernel wait (1 s), e.g. longer under a profiler; given in the environment, the cross-GPU sweeps
+    // keep it instead of their 10 s
+    s.timeout_ticks = 100000000LL;
+    s.timeout_set = false;
+    if (const char *d = getenv("KH_TIMEOUT_MS"))
+        if (atoll(d) > 0) s.timeout_ticks = atoll(d) * 100000LL, s.timeout_set = true;
+    // fault injection for the sharded protocol (tests): rank KH_P2P_FAIL_RANK withholds its GPU's sum at interval
+    // KH_P2P_FAIL_AT of its KH_P2P_FAIL_SWEEP-th update sweep through the peer windows (1-based; default 1)
+    s.p2p_fail_at = num("KH_P2P_FAIL_AT", -1);
+    s.p2p_fail_rank = num("KH_P2P_FAIL_RANK", 0);
+    s.p2p_fail_sweep = num("KH_P2P_FAIL_SWEEP", 1);
+    return s;
+}
+
+// What engine_create learns about the problem before it picks the kernel families (the device-side detection kernels,
+// the padded row form, the ensemble detection)
+struct KhFacts {
+    int K, N, L, num_cus;
+    bool csr, shared;            // sparse operators; every objective has the same operator list
+    bool has_h1, all_h1;         // objective 0 / every objective has its first control
+    bool ell = false, ell_stream = false;  // the padded row form (kh_ell.h) was built, in its streamed form
+    int ell_E = 0;               // ... widest row over all objectives and both directions
+    int ens_ncg = 0;             // column groups of the ensemble kernel where the detection found (H0, s_k H1), else 0
+    double adj_sign = 0.0;       // +1 / -1: every control operator equals +/- its adjoint exactly (else 0)
+    bool real_spectrum = false;  // every operator Hermitian (bit for bit) and f = -+i
+    double imag_defect = -1.0;   // >= 0: bound on the Hermitian part of f A dt when the controls' f H_l are exactly
+                                 // anti-Hermitian (|| . ||_F of the drift's part x max dt); < 0: not of that kind
+    double theta_max;            // as given (<= 0: the families' own default)
+};
+
+// Which kernel families an engine runs, with every instantiation parameter (plan_families).  Two residency checks after
+// staging may still demote it (q2 -> generic, ensemble off); the runtime fallbacks change kind_store / coop_xcd / coop_adj.
+struct KhPlan {
+    KernelKind kind = KIND_GENERIC;        // the update sweep (and its one-launch-per-interval form)
+    KernelKind kind_store = KIND_GENERIC;  // the plain sweeps (no cross-objective coupling: any K)
+    int max_wgs = 0, grid_update = 0;  // workgroups the in-kernel exchange takes; of the single-launch update sweep
+    bool mini = false, quad = false;   // kind q2: the one-wave-per-objective kernels (kh_mini.h), one wave in all
+    bool stepwise_only = false, stream = false;  // one launch per interval; unless the streaming kernel takes them (kh_tile64s.h) ...
+    int stream_G = 0;                            // ... on this many workgroups
+    int coop_G = 0, coop_Y = 0, coop_ks = 0, coop_cols = KH_COOP_COLS;  // kh_coop.h: row blocks, column groups, slots, objectives
+    bool coop_xcd = false, coop_sq = false, coop_adj = false, coop_series = false;  // (coop_xcd / coop_adj: off at runtime too)
+    bool tilen = false, tn_h1reg = false;  // kh_tilen.h lane-order copies; the control in registers too
+    int tn_EP = 0;
+    bool tx = false, tx_update = false;    // kh_tile64x.h lane-order copies (plain sweeps); its update sweep too
+    bool ell_stream = false;               // kh_ell.h: streamed form, row width
+    int ell_E = 0;
+    bool ens = false, ens2 = true;         // kh_ens.h: the single-launch update sweep, whatever `kind` says; the A^2-chain form
+    int ens_ncg = 0, ens_G = 0;
+    bool stage_sq = false;                 // P0, P1, P2 of A^2 per objective (q2 kernels, the cooperative A^2 chain, ens2)
+    double theta_max = 1.0;
+    bool series_rows = false;              // series tables: the Chebyshev form's rows (theta cap, Hermitian defect), else Taylor's
+    double series_cap = 2.0, series_defect = 0.0;
+
+    // kh_forward_update runs kh_update_begin / _step / _end (no single launch)
+    bool per_interval() const { return stepwise_only && !stream && !ens; }
+    // workgroups of the single-launch update sweep
+    int single_grid() const { return ens ? ens_G : (stream ? stream_G : grid_update); }
+    // the sums cross workgroups (and GPUs) inside the update kernel; else kh_update_step + an all-reduce per interval
+    bool exchanges_in_kernel() const { return !(stepwise_only && !ens); }
+    // the ensemble kernel's column groups, and its workgroups *G, on at most max_G workgroups (0: its own grid)
+    int ens_cols(int K, int max_G, int *G) const {
+        int ncg = ens_ncg;
+        *G = ens_G;
+        if (max_G > 0)
+            while (*G > max_G && ncg < KH_ENS_MAXCG) ncg *= 2, *G = (K + 2 * ncg - 1) / (2 * ncg);
+        return ncg;
+    }
+    // the register-tile families, whose update sweep has a form on fewer workgroups (the streaming kernel)
+    bool tile_family() const { return (kind == KIND_TILE_Q2 && !mini) || kind == KIND_TILE_RPT1 || kind == KIND_TILE_RPT2; }
+};
+
 struct kh_engine {
     int K, N, L, nt, is_super;
-    double tol, theta_max;
+    double tol;
     int device, num_cus;
-    KernelKind kind;
-    KernelKind kind_store;  // family of the plain sweeps (no cross-objective coupling: any K)
-    int grid_update;  // workgroups of the single-launch update sweep
-    // cooperative shared-operator kernels (kh_coop.h): row blocks, column groups, k-steps per wave
-    int coop_G = 0, coop_Y = 0, coop_ks = 0, coop_cols = KH_COOP_COLS;
-    kh_u64 *d_coop_vbuf = nullptr;
-    unsigned int *d_coop_xcc = nullptr;  // [Y * G] placement check of the cooperative kernels (zeroed per launch)
-    bool coop_xcd = false;               // one column group per XCD (kh_coop.h, kh_coop_place); KH_COOP_XCD=0: off
-    size_t coop_vbuf_bytes = 0;
-    // update sums on the adjoint side (kh_coop_adjoint_side): H_1^+ chi for the whole store, formed in front of the
-    // update sweep; KH_COOP_NO_ADJ=1: the sums by one more round per interval, as for second order / two controls
-    // experiment (-DKH_WITH_C4W builds, KH_COOP4W=1; scripts/experiments/kh_coop4w.h): four waves per workgroup, a wave
-    // owns four rows for the whole k range; plain sweeps only; measured slower than the k-split kernels
-    bool coop4w = false;
-    int c4_NG = 0;  // groups of 16 columns
-    const cplx **d_c4_fops_fw = nullptr, **d_c4_fops_bw = nullptr;  // [2] H0, H1 in kh_coop4w.h's fragment order
-    const cplx **d_c4_sq_fw = nullptr, **d_c4_sq_bw = nullptr;      // [3] P0, P1, P2
-    bool coop_adj = false;
-    unsigned char *d_coop_adj_nz = nullptr;  // [G][G] non-zero 16 x 16 blocks of H_1^+
-    cplx *d_coop_adj = nullptr;              // [K][nt][N], allocated by the first update sweep
-    const cplx *coop_adj_op = nullptr;       // H_1^+, row-major (the staged adjoint of the shared control operator)
+    KhSwitches sw;
+    KhPlan plan;
+    std::vector<void *> owned;        // every device allocation made at creation (kh_engine_destroy frees them)
     // device-side problem data
     const cplx **d_ops_fw = nullptr;  // [K*(1+L)]
     const cplx **d_ops_bw = nullptr;  // [K*(1+L)] adjoints
@@ -105,35 +215,42 @@ struct kh_engine {
     KhEll *d_ell_fw = nullptr, *d_ell_bw = nullptr;  // [K] sparse operators in padded row form (kh_ell.h), or NULL
     int *d_ell_off = nullptr;         // ... their column offsets and values (one pool each)
     cplx *d_ell_vals = nullptr;
-    int ell_E = 0;                    // widest row over all objectives and both directions (picks the instantiation)
     bool gen_fits = true;             // the generic kernels' LDS vectors fit (N <= 2540)
-    bool ell_stream = false;          // the streamed form of kh_ell.h (rows that do not fit the registers, N <= 4096)
-    cplx *d_ell_scratch = nullptr;    // ... its per-workgroup scratch planes [workgroups][ell_scratch_stride]
+    cplx *d_ell_scratch = nullptr;    // the streamed padded-row form's per-workgroup scratch planes [workgroups][stride]
     long long ell_scratch_stride = 0;
     const cplx **d_coop_fops_fw = nullptr, **d_coop_fops_bw = nullptr;  // [1+L] fragment-ordered operator copies
     const cplx **d_coop_sq_fw = nullptr, **d_coop_sq_bw = nullptr;      // [3] the same for P0, P1, P2 (one control)
+    kh_u64 *d_coop_vbuf = nullptr;
+    size_t coop_vbuf_bytes = 0;
+    unsigned int *d_coop_xcc = nullptr;      // [Y * G] placement check of the cooperative kernels (zeroed per launch)
+    unsigned char *d_coop_adj_nz = nullptr;  // [G][G] non-zero 16 x 16 blocks of H_1^+
+    cplx *d_coop_adj = nullptr;              // [K][nt][N], allocated by the first update sweep
+    const cplx *coop_adj_op = nullptr;       // H_1^+, row-major (the staged adjoint of the shared control operator)
     const cplx **d_sq_fw = nullptr;   // [K*3] P0, P1, P2 of A^2 (q2 kernels), forward operators
     const cplx **d_sq_bw = nullptr;   // [K*3] the same for the adjoint operators
     const cplx **d_tn_fw = nullptr, **d_tn_bw = nullptr;  // [K*(1+L)] lane-order operator copies (kh_tilen.h), or NULL
     const cplx **d_tx_fw = nullptr, **d_tx_bw = nullptr;  // [K*(1+L)] lane-order 64 x 64 operator copies (kh_tile64x.h), or NULL
-    bool tx_update = false;           // ... and the update sweep may take that family too (K <= co-resident workgroups)
-    bool tn_h1reg = false;            // ... one control, present in every objective, N <= 96: it stays in registers too
-    std::vector<void *> owned;        // adjoint operator copies
+    const cplx *ens_H0 = nullptr, *ens_H1 = nullptr;
+    double *d_ens_scale = nullptr;    // [K]
+    double *d_q2_theta = nullptr, *d_q2_c0 = nullptr, *d_q2_rows = nullptr, *d_ratios = nullptr;  // series tables of the register-tile kernels
     // workspaces
     cplx *d_phi = nullptr;            // [K][N]
     kh_u64 *d_slots = nullptr;        // [2][G][L][2]
+    size_t slots_bytes = 0;
     unsigned int *d_abort = nullptr;
     unsigned long long *d_wait_ticks = nullptr;  // [4] kh_p2p_stats: in-GPU gather, cross-GPU wait (last sharded sweep); self-test ticks, rounds
     double *d_stats = nullptr;        // [4] (+ 64 trace stamps behind them in a KH_TIMING build)
     double *d_wg_partial = nullptr;   // [G][L]
+    double *d_step_partial = nullptr; // [L] the interval's sums of kh_forward_update's per-interval path
     cplx *d_gen_scratch = nullptr;    // [gen_scratch_wgs][N][N] generic kernels: the interval's generator (ensure_gen_scratch)
+    int gen_scratch_wgs = 0;
+    bool gen_scratch_failed = false;
     // generic kernels, first order, dense operators: the update sums on the adjoint side (kh_gen_adjoint_side):
     // H_lk^+ chi_k(t_n) for the whole co-state store, [L][K][nt][N], formed in front of every update sweep
     cplx *d_gen_adj = nullptr;
     bool gen_adj_failed = false;      // the allocation did not fit: the sums stay on the forward side
     bool gen_adj_ready = false;       // d_gen_adj holds the store of the sweep in progress (stepwise launches reuse it)
-    int gen_scratch_wgs = 0;
-    bool gen_scratch_failed = false;
+    double adj_sign = 0.0;            // KhFacts::adj_sign (0 with KH_NO_ADJ)
     const double *guess_dev = nullptr;  // remembered by kh_update_begin
     // second-order update (kh_set_second_order); all NULL = first order
     const cplx *so_fw_prev = nullptr;
@@ -147,51 +264,11 @@ struct kh_engine {
     kh_u64 **d_p2p_peers = nullptr;          // device array [world] of window pointers
     unsigned int p2p_epoch_base = 0;         // advanced by nt per sweep: epochs never repeat
     bool p2p_ready = false;
-    size_t slots_bytes = 0;
+    int p2p_sweeps = 0;
     double last_intervals = 0, last_wgs = 0;
-    std::set<const void *> lds_raised;  // kernels whose dynamic-LDS limit was raised on this engine's device
-    // tuning knobs (s_sleep units of 64 cycles), read from the environment once at creation
-    int poll_delay = 16;       // KH_POLL_DELAY: head start of the update-sum stores, ~0.4 us: measured best (one control)
-    bool poll_delay_set = false;  // ... given in the environment: several controls do not apply their own default then
-    int adj_poll_delay = 0;    // KH_ADJ_DELAY: the same where a matrix-vector product already sits between store and poll
-    int coop_poll_delay = 0;   // KH_COOP_DELAY: the same for the cooperative kernels' block exchange (a polling pass is four
-                               // 16-byte loads per lane there: an early, stale pass costs little -- measured 0 best)
-    double adj_sign = 0.0;  // +1 / -1: every control operator equals +/- its adjoint exactly (else 0)
-    bool real_spectrum = false;  // every operator Hermitian (bit for bit) and f = -+i
-    double imag_defect = -1.0;   // >= 0: bound on the Hermitian part of f A dt when the controls' f H_l are exactly
-                                 // anti-Hermitian (|| . ||_F of the drift's part x max dt); < 0: not of that kind
-    bool coop_series = false;    // the cooperative kernels run the Chebyshev-form series (kh_common.h)
-    bool use_q4 = false;         // KH_Q4=1 in a -DKH_WITH_Q4 build (experiment): plain sweeps with 1024-thread workgroups
-    bool stepwise_only = false;  // more objectives than can be co-resident: kh_forward_update runs one launch per interval
-    // ... unless the streaming kernel takes them (kh_tile64s.h): ONE launch of stream_G co-resident workgroups, each
-    // walking through its objectives in every interval (one GPU; KH_NO_STREAM=1: the launch per interval, A/B)
-    bool stream = false;
-    int stream_G = 0;
     int last_update_grid = 0;  // workgroups of the last single-launch update sweep where the ensemble / streaming kernels ran it
     int reduced_G = 0;  // kh_set_update_workgroups: the single-launch update sweep on at most this many workgroups (0: off)
-    double *d_step_partial = nullptr;  // [L] the interval's sums on that path
-    // ensembles (kh_ens.h): every objective's operator list is (H0, s_k H1) with one H0 and one H1 -- the single-launch
-    // update sweep then runs on the matrix cores with 2 ens_ncg objectives per workgroup, whatever `kind` says (which
-    // still serves the plain sweeps and the per-interval form)
-    bool ens = false;
-    int ens_ncg = 0, ens_G = 0;
-    const cplx *ens_H0 = nullptr, *ens_H1 = nullptr;
-    bool ens2 = true;  // first order, 4 objectives per workgroup: the A^2-chain form (kh_ens2_forward_update); KH_ENS2=0: off
-    double *d_ens_scale = nullptr;     // [K]
-    bool mini = false;           // kind q2, N <= 16, K <= 8: the one-wave-per-objective kernels (kh_mini.h)
-    bool quad = false;           // mini with N <= 4, K <= 4: the whole problem in one wave
-    double *d_q2_theta = nullptr, *d_q2_c0 = nullptr, *d_q2_rows = nullptr, *d_ratios = nullptr;  // series tables of the register-tile kernels
-    long long timeout_ticks = 100000000LL;  // KH_TIMEOUT_MS: bound on any in-kernel wait (100 MHz ticks; 1 s)
-    bool timeout_set = false;    // ... given in the environment (the cross-GPU sweeps then keep it instead of their 10 s)
-    // switches read from the environment ONCE, at creation (not per launch, not per process: engines with different
-    // settings coexist)
-    bool coop_launch = true;     // KH_COOP_LAUNCH=0: plain launches instead of cooperative ones (A/B timing)
-    bool q2_single = true;       // KH_Q2_SINGLE=0: the instantiations with the cross-GPU stage on one GPU too (A/B)
-    bool tile_single = true;     // KH_TILE_SINGLE=0: the same for the one-term-per-phase kernels
-    bool coop_single = true;     // KH_COOP_SINGLE=0: the same for the cooperative kernels' adjoint-side form
-    // fault injection for the sharded protocol (tests): rank KH_P2P_FAIL_RANK withholds its GPU's sum at interval
-    // KH_P2P_FAIL_AT of its KH_P2P_FAIL_SWEEP-th update sweep through the peer windows (1-based; default 1)
-    int p2p_fail_at = -1, p2p_fail_rank = 0, p2p_fail_sweep = 1, p2p_sweeps = 0;
+    std::set<const void *> lds_raised;  // kernels whose dynamic-LDS limit was raised on this engine's device
 };
 
 // Kernels with more than 64 KiB of dynamic LDS need the limit raised once per device: remembered per
@@ -281,7 +358,7 @@ static int launch_persistent(const kh_engine *e, dim3 grid, dim3 block, size_t l
         hipLaunchKernelGGL(Kernel, grid, block, lds, st, args...);
         return KH_OK;
     }
-    if (!e->coop_launch) {
+    if (!e->sw.coop_launch) {
         // a plain launch has the same residency but nobody checks the grid against it (the cooperative launch below
         // does): ask the occupancy of THIS instantiation as built -- registers, scratch, LDS -- once per shape, so that
         // a grid that cannot be co-resident is refused here (KH_ERR_UNSUPPORTED: the caller takes a smaller grid or one
@@ -322,11 +399,23 @@ static int launch_persistent(const kh_engine *e, dim3 grid, dim3 block, size_t l
     return KH_OK;
 }
 
-// grid <= (resident workgroups per CU of THIS kernel) x CUs ?  (checked once per kernel at engine creation)
-static int check_residency(const kh_engine *e, const void *func, int threads, size_t lds, int grid, const char *what);
+// the same after raising the kernel's dynamic-LDS limit (ensure_dynamic_lds)
+template <auto Kernel, class... Args>
+static int launch_plain_lds(kh_engine *e, dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args) {
+    const int rc = ensure_dynamic_lds(e, (const void *)Kernel, lds);
+    if (rc == KH_OK) launch_plain<Kernel>(grid, block, lds, st, args...);
+    return rc;
+}
+
+template <auto Kernel, class... Args>
+static int launch_persistent_lds(kh_engine *e, dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args) {
+    const int rc = ensure_dynamic_lds(e, (const void *)Kernel, lds);
+    return rc != KH_OK ? rc : launch_persistent<Kernel>(e, grid, block, lds, st, args...);
+}
 
 extern "C" const char *kh_last_error(void) { return g_last_error.c_str(); }
 
+// grid <= (resident workgroups per CU of THIS kernel) x CUs ?  (checked once per kernel at engine creation)
 static int check_residency(const kh_engine *e, const void *func, int threads, size_t lds, int grid, const char *what) {
     int per_cu = 0;
     KH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, func, threads, lds));
@@ -340,15 +429,16 @@ extern "C" const char *kh_version(void) { return "krotov_hip 0.6 (gfx950; tile64
 
 extern "C" const char *kh_engine_kernel(const kh_engine *e) {
     if (e == nullptr) return "";
-    if (e->ens) return "ens64/mfma";
-    switch (e->kind) {
+    const KhPlan &p = e->plan;
+    if (p.ens) return "ens64/mfma";
+    switch (p.kind) {
         case KIND_TILE_RPT2: return "tile64/256";
-        case KIND_TILE_RPT1: return e->stepwise_only ? (e->stream ? "tile64/stream" : "tile64/512 per interval") : "tile64/512";
-        case KIND_TILE_Q2: return e->mini ? (e->quad ? "mini4/wave" : "mini16/wave") : "tile64q2/512";
+        case KIND_TILE_RPT1: return p.stepwise_only ? (p.stream ? "tile64/stream" : "tile64/512 per interval") : "tile64/512";
+        case KIND_TILE_Q2: return p.mini ? (p.quad ? "mini4/wave" : "mini16/wave") : "tile64q2/512";
         case KIND_COOP: return "coop16/mfma";
-        case KIND_ELL: return e->ell_stream ? "ellstream/csr" : "ell/csr";
+        case KIND_ELL: return p.ell_stream ? "ellstream/csr" : "ell/csr";
         case KIND_TILEN: return "tile128/512";
-        default: return e->d_csr_fw != nullptr ? "generic/csr" : (e->d_tx_fw != nullptr ? "tile64x/512" : "generic");
+        default: return e->d_csr_fw != nullptr ? "generic/csr" : (p.tx ? "tile64x/512" : "generic");
     }
 }
 
@@ -371,8 +461,8 @@ static KhSweepArgs sweep_args(const kh_engine *e, bool backward) {
         p.fim = backward ? 1.0 : -1.0;
     }
     p.tol = e->tol;
-    p.theta_max = e->theta_max;
-    p.inv_theta_max = 1.0 / e->theta_max;
+    p.theta_max = e->plan.theta_max;
+    p.inv_theta_max = 1.0 / e->plan.theta_max;
     p.deg_theta = e->d_deg_theta;
     p.q2_theta = e->d_q2_theta;
     p.q2_c0 = e->d_q2_c0;
@@ -412,11 +502,10 @@ static void ensure_gen_scratch(kh_engine *e, int wgs) {
 static bool ensure_gen_adj(kh_engine *e) {
     if (e->d_gen_adj != nullptr) return true;
     if (e->gen_adj_failed) return false;
-    if (const char *d = getenv("KH_GEN_ADJ"))
-        if (atoi(d) == 0) {
-            e->gen_adj_failed = true;
-            return false;
-        }
+    if (!e->sw.gen_adj) {
+        e->gen_adj_failed = true;
+        return false;
+    }
     const size_t bytes = sizeof(cplx) * (size_t)e->L * e->K * e->nt * e->N;
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || bytes > free_b / 4 || hipMalloc(&e->d_gen_adj, bytes) != hipSuccess) {
@@ -431,49 +520,9 @@ static bool ensure_gen_adj(kh_engine *e) {
 extern "C" void kh_engine_destroy(kh_engine *e) {
     if (e == nullptr) return;
     for (void *ptr : e->owned) (void)hipFree(ptr);
-    (void)hipFree((void *)e->d_ops_fw);
-    (void)hipFree((void *)e->d_ops_bw);
-    (void)hipFree(e->d_norms);
-    (void)hipFree(e->d_dt);
-    (void)hipFree(e->d_deg_theta);
-    (void)hipFree(e->d_q2_theta);
-    (void)hipFree(e->d_q2_c0);
-    (void)hipFree(e->d_q2_rows);
-    (void)hipFree(e->d_ratios);
-    (void)hipFree(e->d_csr_fw);
-    (void)hipFree(e->d_csr_bw);
-    (void)hipFree(e->d_ell_fw);
-    (void)hipFree(e->d_ell_bw);
-    (void)hipFree(e->d_ell_off);
-    (void)hipFree(e->d_ell_vals);
-    (void)hipFree((void *)e->d_coop_fops_fw);
-    (void)hipFree((void *)e->d_coop_fops_bw);
-    (void)hipFree((void *)e->d_coop_sq_fw);
-    (void)hipFree((void *)e->d_coop_sq_bw);
-    (void)hipFree((void *)e->d_c4_fops_fw);
-    (void)hipFree((void *)e->d_c4_fops_bw);
-    (void)hipFree((void *)e->d_c4_sq_fw);
-    (void)hipFree((void *)e->d_c4_sq_bw);
-    (void)hipFree((void *)e->d_sq_fw);
-    (void)hipFree((void *)e->d_sq_bw);
-    (void)hipFree((void *)e->d_tn_fw);
-    (void)hipFree((void *)e->d_tn_bw);
-    (void)hipFree((void *)e->d_tx_fw);
-    (void)hipFree((void *)e->d_tx_bw);
-    (void)hipFree(e->d_phi);
-    (void)hipFree(e->d_slots);
-    (void)hipFree(e->d_abort);
-    (void)hipFree(e->d_wait_ticks);
+    // (allocated lazily or reallocated: not in the owned list)
     (void)hipFree(e->d_gen_scratch);
     (void)hipFree(e->d_gen_adj);
-    (void)hipFree(e->d_ell_scratch);
-    (void)hipFree(e->d_stats);
-    (void)hipFree(e->d_wg_partial);
-    (void)hipFree(e->d_step_partial);
-    (void)hipFree(e->d_ens_scale);
-    (void)hipFree(e->d_coop_vbuf);
-    (void)hipFree(e->d_coop_xcc);
-    (void)hipFree(e->d_coop_adj_nz);
     (void)hipFree(e->d_coop_adj);
     for (void *ptr : e->p2p_opened) (void)hipIpcCloseMemHandle(ptr);
     (void)hipFree(e->p2p_window);
@@ -635,6 +684,695 @@ static bool build_ell_host(const std::vector<const HostCsr *> &ops, int N, std::
     return true;
 }
 
+// ---------------------------------------------------------------------------
+// kernel families: decided on the host from the problem's facts and the switches (no HIP calls)
+// ---------------------------------------------------------------------------
+static int max_update_wgs(int num_cus) { return num_cus < 64 * KH_GATHER_CHUNKS ? num_cus : 64 * KH_GATHER_CHUNKS; }
+
+// Ensembles (kh_ens.h): one drift, control operators equal up to a real scale, N <= 64, one control, more objectives
+// than CUs (from 257 on it beats the two-workgroups-per-CU tile kernels too: 10.7 against 11.1 us per interval at
+// K = 512; one objective per CU: the two-terms-per-phase kernels, 4.8 us per interval against 10.2 there).  The column
+// groups where the shape asks for the ensemble detection, else 0.
+static int ens_candidate(const KhFacts &f, const KhSwitches &sw) {
+    const bool want = sw.ens == 1 || (sw.ens != 0 && !sw.kernel_set && f.K >= sw.ens_min_k);
+    if (!want || f.csr || f.N > KH_TILE_N || f.L != 1 || !f.has_h1) return 0;
+    const int max_wgs = max_update_wgs(f.num_cus);
+    int ncg = 0;
+    for (int c = 1; c <= KH_ENS_MAXCG; c *= 2)
+        if ((f.K + 2 * c - 1) / (2 * c) <= max_wgs) {
+            ncg = c;
+            break;
+        }
+    const int c = sw.ens_ncg;
+    if ((c == 1 || c == 2 || c == 4 || c == 8) && (f.K + 2 * c - 1) / (2 * c) <= max_wgs) ncg = c;
+    return ncg;
+}
+
+// The override order below is the precedence: every family that a later block picks replaces an earlier choice.
+static KhPlan plan_families(const KhFacts &f, const KhSwitches &sw) {
+    KhPlan p;
+    const bool dense = !f.csr, theta_given = f.theta_max > 0.0;
+    const bool force = sw.kernel_set, not_generic = !sw.kernel_is("generic");
+    const int K = f.K, N = f.N, L = f.L;
+    const int max_wgs = max_update_wgs(f.num_cus);
+    p.max_wgs = max_wgs;
+    p.grid_update = K < max_wgs ? K : max_wgs;
+    p.theta_max = theta_given ? f.theta_max : 1.0;
+    p.ell_stream = f.ell_stream;
+    p.ell_E = f.ell_E;
+    const bool tile_shape = dense && N <= KH_TILE_N && L >= 1 && L <= 4;
+    const bool tile_ok = tile_shape && K <= max_wgs;
+    // More objectives than CUs, one control: 256-thread workgroups (one wave per SIMD, 256 VGPRs) fit two per
+    // CU, so up to 2 x #CUs objectives stay co-resident -- and the two workgroups of a CU hide each other's
+    // phase latency.
+    const int max_wgs2 = 2 * f.num_cus < 64 * KH_GATHER_CHUNKS_WIDE ? 2 * f.num_cus : 64 * KH_GATHER_CHUNKS_WIDE;
+    const bool tile2_ok = dense && N <= KH_TILE_N && L == 1 && K > max_wgs && K <= max_wgs2;
+    if (tile2_ok && not_generic) {
+        p.kind = KIND_TILE_RPT2;
+        p.grid_update = K;
+    }
+    // More objectives than can be co-resident (so no in-kernel exchange), tile-sized: the register-tile kernel with
+    // ONE LAUNCH PER INTERVAL (the form the sharded sweep uses, kh_update_step) -- every launch re-stages the two
+    // operator tiles of its objectives (128 KiB each, from L2 / the Infinity Cache), which still beats the generic
+    // kernels' re-streaming of the operators for every term by 5x (K = 1024: 207 -> see DESIGN.md us per interval).
+    if (tile_shape && !tile_ok && !tile2_ok && K > max_wgs && sw.stepwise && !force) {
+        p.kind = KIND_TILE_RPT1;
+        p.grid_update = K;
+        p.stepwise_only = true;
+        // one workgroup per CU; as few workgroups as give everybody the same number of objectives (K = 384, two controls:
+        // 192 x 2 in 23.9 us per interval against 128 x 2 + 128 x 1 in 24.5)
+        int G = max_wgs;
+        if (K > G) G = (K + (K + G - 1) / G - 1) / ((K + G - 1) / G);
+        if (sw.stream_G >= 1 && sw.stream_G <= G) G = sw.stream_G;
+        if (G > K) G = K;
+        p.stream_G = G;
+        p.stream = (long long)G * KH_STREAM_MMAX >= K && sw.stream;
+    }
+    if (tile_ok && not_generic) {
+        // two waves per SIMD are needed to keep the fp64 FMA pipe issuing back to back
+        p.kind = L == 1 ? KIND_TILE_Q2 : KIND_TILE_RPT1;  // (one control: two Taylor terms per phase, kh_tile64q2.h)
+        if (sw.kernel_is("tile512")) p.kind = KIND_TILE_RPT1;
+        if (sw.kernel_is("tile256") && L == 1) p.kind = KIND_TILE_RPT2;  // (two controls: 204 spilled values, never a default choice -- no such instantiation any more)
+        p.grid_update = K;
+        // small problems: one wave per objective, the objectives of the GPU in one workgroup (kh_mini.h);
+        // KH_KERNEL=q2 keeps the workgroup-per-objective kernels, KH_KERNEL=mini is accepted for symmetry
+        p.mini = p.kind == KIND_TILE_Q2 && N <= KH_MINI_N && K <= KH_MINI_MAXK && !force;
+    }
+    if (sw.kernel_is("mini") && tile_ok && L == 1 && N <= KH_MINI_N && K <= KH_MINI_MAXK) {
+        p.kind = KIND_TILE_Q2;
+        p.grid_update = K;
+        p.mini = true;
+    }
+    p.quad = p.mini && N <= KH_QUAD_N && K <= KH_QUAD_MAXK && !sw.kernel_is("mini");
+    // objectives sharing ONE operator list with a state too large for a register tile: one Taylor
+    // term of all objectives is a dense (N x N)(N x K) product -> fp64 matrix cores (kh_coop.h)
+    {
+        // objectives per workgroup: as few as keeps the grid within the co-resident limit (a round is bound by
+        // the block fetch, which shrinks with the column count; the MFMA work per workgroup does not grow)
+        const int G = (N + 15) / 16;
+        int cols = G * ((K + 3) / 4) <= max_wgs ? 4 : KH_COOP_COLS;
+        // two objectives per workgroup (half the matrix-core work of a round per workgroup, twice the workgroups)
+        // where every column group still gets an XCD of its own (kh_coop_place): up to 8 groups of at most 32
+        if (K > 8 && (K + 1) / 2 <= 8 && G <= 32 && G * ((K + 1) / 2) <= max_wgs) cols = 2;
+        const int want = sw.coop_cols;
+        if ((want == 2 || want == 4 || want == 16) && G * ((K + want - 1) / want) <= max_wgs) cols = want;
+        const int Y = (K + cols - 1) / cols;
+        const bool fits = dense && f.shared && N <= 480 && L <= KH_COOP_MAX_L && G * Y <= max_wgs;
+        if (fits && (sw.kernel_is("coop") || (N > KH_TILE_N && !force))) {
+            p.kind = KIND_COOP;
+            p.coop_G = G;
+            p.coop_Y = Y;
+            p.coop_cols = cols;
+            p.coop_ks = cols <= 4 ? kh_coop4_slots(N) : (N + 31) / 32;  // operator-fragment slots per lane
+            p.coop_xcd = cols <= 4 && Y <= 8 && G <= 32 && sw.coop_xcd;
+            p.grid_update = K < max_wgs ? K : max_wgs;  // (stepwise launches use the generic kernel)
+            // A round (one Taylor term) costs a cross-workgroup exchange here, so fewer, longer
+            // sub-steps pay: theta <= 4 needs ~31 terms per sub-step against 4 x 18 at theta <= 1.
+            // Round-off grows like e^theta (55 eps per step at theta = 4), still far inside the
+            // parity budget (measured: unchanged 3e-15 vs the oracle on the transmon Liouvillians).
+            if (!theta_given) p.theta_max = 4.0;
+        }
+    }
+    // Per-objective operators with 64 < N <= 128: the generator in registers (kh_tilen.h) instead of the generic kernels'
+    // re-streaming of every operator for every term.  (Objectives sharing one operator list took the cooperative
+    // matrix-core kernels above; KH_KERNEL=tilen forces this family for them too: testing.)
+    if (dense && N > KH_TILE_N && N <= KH_TN_NMAX && L >= 1 && L <= KH_MAX_L &&
+        ((p.kind == KIND_GENERIC && !force) || sw.kernel_is("tilen"))) {
+        p.tilen = true;
+        if (sw.kernel_is("tilen")) {
+            p.kind = KIND_GENERIC;  // (undo the cooperative choice)
+            p.grid_update = K < max_wgs ? K : max_wgs;
+            if (!theta_given) p.theta_max = 1.0;
+        }
+        p.tn_EP = N <= 80 ? 20 : N <= 96 ? 24 : N <= 112 ? 28 : 32;
+        p.tn_h1reg = L == 1 && N <= 96 && sw.tn_h1reg && f.all_h1;
+        if (K <= max_wgs) {
+            p.kind = KIND_TILEN;
+            p.grid_update = K;
+        }
+    }
+    // Five to eight controls, N <= 64: the register-tile kernels with the operators beyond the CU's room streamed
+    // (kh_tile64x.h) instead of the generic kernels.  The plain sweeps take their objectives in turns (any K); the
+    // update sweep needs one resident workgroup per objective, first order and the adjoint-side store (update_route:
+    // otherwise the generic kernels, which stay this engine's `kind`).  KH_TX=0: off (A/B switch); KH_KERNEL=tilex: testing
+    if (dense && N <= KH_TILE_N && L >= KH_TX_MIN_L && L <= KH_MAX_L && p.kind == KIND_GENERIC &&
+        (!force || sw.kernel_is("tilex")) && sw.tx) {
+        p.tx = true;
+        p.tx_update = K <= max_wgs;
+    }
+    // Sparse operators in the padded row form: one 1024-thread workgroup per objective, the matrix in registers
+    // (kh_ell.h).  The update sweep exchanges the sums in-kernel, so all K workgroups must be resident (one per CU);
+    // with more objectives it stays with the generic CSR kernels, the plain sweeps take their objectives in turns.
+    const bool near_imag = f.imag_defect >= 0.0 && f.imag_defect <= 0.05;
+    const bool ell_cheb = f.ell && (f.real_spectrum || near_imag) && sw.near_imag;
+    const double ell_cap = sw.ell_cap > 0.0 && sw.ell_cap < KH_ELL_THETA_CAP ? sw.ell_cap : KH_ELL_THETA_CAP;
+    if (f.ell) {
+        if (K <= max_wgs) {
+            p.kind = KIND_ELL;
+            p.grid_update = K;
+        }
+        // a term of the series costs a workgroup-wide round whatever it multiplies: fewer, longer sub-steps pay, as
+        // for the cooperative kernels (theta <= 4: round-off ~ e^theta eps per step, far inside the parity budget);
+        // the long sub-steps only with the Chebyshev form's coefficients, Taylor's at theta <= 4 as before.
+        // KH_ELL_CAP (scripts/exp_ell_cap.py): another cap for the Chebyshev-form tables only, never beyond the one
+        // they were validated for -- plain Taylor keeps theta <= 4 (its round-off grows like e^theta)
+        if (!theta_given) p.theta_max = ell_cheb ? ell_cap : 4.0;
+    }
+    // The plain sweeps have no cross-objective coupling, so the register-tile kernel serves them for any
+    // number of objectives (workgroups simply run in turns) even when the update sweep needs the generic one.
+    p.kind_store = f.ell ? KIND_ELL : (p.tilen ? KIND_TILEN : (p.tx ? KIND_TILEX : p.kind));
+    if (p.kind == KIND_GENERIC && tile_shape && not_generic) p.kind_store = KIND_TILE_RPT1;
+    // ... and with one control that kernel is the two-terms-per-phase one (kh_q2_sweep_store takes its objectives in
+    // turns: no co-residency needed), whatever the update sweep has to use: K = 512 on one GPU 7.5 -> 5.8 us per
+    // interval of the backward sweep (two turns of the 256-objective sweep instead of the one-term-per-phase kernel
+    // with two workgroups per CU).  KH_Q2_STORE=0: the update sweep's own family (A/B switch)
+    if ((p.kind_store == KIND_TILE_RPT2 || p.kind_store == KIND_TILE_RPT1) && L == 1 && !force && sw.q2_store)
+        p.kind_store = KIND_TILE_Q2;
+    // (not for 16 operator slots per lane x 16 objectives per workgroup -- N > 256 with more objectives than 4 per
+    // workgroup keep co-resident --: the A^2 chain's second fragment does not fit the registers there, launch_coop_store)
+    p.coop_sq = p.kind == KIND_COOP && L == 1 && sw.coop_sq && !(p.coop_cols == 16 && p.coop_ks > 8);
+    p.coop_adj = p.coop_sq && f.has_h1 && sw.coop_adj;
+    p.stage_sq = p.kind == KIND_TILE_Q2 || p.kind_store == KIND_TILE_Q2 || p.coop_sq;
+    // series tables (every kernel family but the cooperative one reads them; the cooperative kernels with the A^2 chain:
+    // a term is a cross-workgroup round, so the Chebyshev form is used up to theta = 4 and also for generators that are
+    // anti-Hermitian only up to a small defect)
+    p.coop_series = p.coop_sq && near_imag;
+    p.series_rows = true;
+    if (p.coop_series) {
+        p.series_cap = 4.0, p.series_defect = f.imag_defect;
+    } else if (ell_cheb) {
+        // sparse operators in the padded row form: a term costs a workgroup-wide round, so one long sub-step beats
+        // several short ones: the Chebyshev form up to theta = 6.  Measured on the reference's three-states problem
+        // (scripts/exp_ell_cap.py, theta = 4.4 ... 7.9 per step, 3 iterations x 3 sweeps x 2000 steps): tau within
+        // 6e-14 and the pulses within 7e-15 of the same run with theta <= 1 per sub-step, for caps 4, 5, 6 and 8
+        // alike; KH_ELL_CAP: A/B switch
+        p.series_cap = ell_cap, p.series_defect = f.real_spectrum ? 0.0 : f.imag_defect;
+    } else if (f.real_spectrum) {
+        p.series_cap = 2.0, p.series_defect = 0.0;
+    } else if (f.imag_defect > 0.0 && f.imag_defect <= 0.05 && sw.near_imag) {
+        // the same form, with the margin for the Hermitian defect, for the other kernel families (weakly damped
+        // Liouvillians, Hamiltonians with a small anti-Hermitian part); KH_NEAR_IMAG=0: Taylor (A/B switch)
+        p.series_cap = 2.0, p.series_defect = f.imag_defect;
+    } else {
+        p.series_rows = false;
+    }
+    // ensembles: whatever `kind` says, the single-launch update sweep (KH_ENS=0: off; KH_ENS_MINK: smallest K that
+    // takes it; KH_ENS_NCG: column groups)
+    if (f.ens_ncg > 0) {
+        p.ens = true;
+        p.ens2 = sw.ens2;
+        p.ens_ncg = f.ens_ncg;
+        p.ens_G = (K + 2 * f.ens_ncg - 1) / (2 * f.ens_ncg);
+    }
+    return p;
+}
+
+// ---------------------------------------------------------------------------
+// engine creation: validate -> gather facts -> plan -> stage what the plan names -> residency demotions
+// ---------------------------------------------------------------------------
+template <class T>
+static int dev_alloc(kh_engine *e, T **ptr, size_t bytes) {
+    void *q = nullptr;
+    KH_HIP(hipMalloc(&q, bytes));
+    e->owned.push_back(q);
+    *ptr = (T *)q;
+    return KH_OK;
+}
+
+template <class T>
+static int dev_upload(kh_engine *e, T **ptr, const void *src, size_t bytes) {
+    KH_TRY(dev_alloc(e, ptr, bytes));
+    KH_HIP(hipMemcpy((void *)*ptr, src, bytes, hipMemcpyHostToDevice));
+    return KH_OK;
+}
+
+// One device copy per distinct operator (or operator pair): the first request for a key allocates `bytes` and lets
+// `fill(dst)` write it; later requests get the same copy.
+struct KhCopies {
+    std::map<std::pair<const void *, const void *>, cplx *> of;
+    template <class Fill>
+    int get(kh_engine *e, const void *a, const void *b, size_t bytes, Fill &&fill, const cplx **out) {
+        auto it = of.find(std::make_pair(a, b));
+        if (it == of.end()) {
+            cplx *dst = nullptr;
+            int rc = dev_alloc(e, &dst, bytes);
+            if (rc == KH_OK) rc = fill(dst);
+            if (rc != KH_OK) return rc;
+            it = of.emplace(std::make_pair(a, b), dst).first;
+        }
+        *out = it->second;
+        return KH_OK;
+    }
+};
+
+// the device table [tab.size()] of one copy per distinct operator of `tab` (`absent` where tab has none)
+template <class Fill>
+static int stage_copies(kh_engine *e, KhCopies &copies, const std::vector<const cplx *> &tab, size_t bytes,
+                        const cplx *absent, Fill &&fill, const cplx ***slot) {
+    std::vector<const cplx *> out(tab.size(), absent);
+    for (size_t i = 0; i < tab.size(); ++i) {
+        if (tab[i] == nullptr) continue;
+        const int rc = copies.get(e, tab[i], nullptr, bytes, [&](cplx *dst) { return fill(tab[i], dst); }, &out[i]);
+        if (rc != KH_OK) return rc;
+    }
+    KH_HIP(hipGetLastError());
+    return dev_upload(e, slot, out.data(), sizeof(cplx *) * out.size());
+}
+
+// Operator tables: forward pointers as given, adjoints staged once per distinct operator (dense) or as the caller
+// supplies them (CSR); norms, degree table, time steps.
+static int stage_operators(kh_engine *e, const kh_problem *pr, const kh_csr *csr_fw, const kh_csr *csr_bw,
+                           std::vector<const cplx *> &fw, std::vector<const cplx *> &bw) {
+    const size_t nops = (size_t)e->K * (1 + e->L);
+    fw.assign(nops, nullptr);
+    bw.assign(nops, nullptr);
+    KhCopies adj;
+    const int tiles = (e->N + 31) / 32;
+    for (size_t i = 0; i < nops; ++i) {
+        const cplx *src = (const cplx *)pr->ops[i];
+        fw[i] = src;
+        if (src == nullptr) continue;
+        if (csr_fw != nullptr) {  // the caller supplies the conjugate transposes
+            bw[i] = (const cplx *)csr_bw[i].data;
+            continue;
+        }
+        const int rc = adj.get(e, src, nullptr, sizeof(cplx) * (size_t)e->N * e->N, [&](cplx *dst) {
+            kh_adjoint_kernel<<<dim3(tiles, tiles), 256>>>(src, dst, e->N);
+            return KH_OK;
+        }, &bw[i]);
+        if (rc != KH_OK) return rc;
+    }
+    KH_HIP(hipGetLastError());
+    KH_TRY(dev_upload(e, &e->d_ops_fw, fw.data(), sizeof(cplx *) * nops));
+    KH_TRY(dev_upload(e, &e->d_ops_bw, bw.data(), sizeof(cplx *) * nops));
+    if (csr_fw != nullptr) {
+        static_assert(sizeof(KhCsr) == sizeof(kh_csr), "kh_csr layout");
+        KH_TRY(dev_upload(e, &e->d_csr_fw, csr_fw, sizeof(KhCsr) * nops));
+        KH_TRY(dev_upload(e, &e->d_csr_bw, csr_bw, sizeof(KhCsr) * nops));
+    }
+    if (pr->op_norms != nullptr) {
+        KH_TRY(dev_upload(e, &e->d_norms, pr->op_norms, sizeof(double) * nops));
+    } else {
+        KH_TRY(dev_alloc(e, &e->d_norms, sizeof(double) * nops));
+        kh_fro_norms<<<(unsigned)nops, 256>>>(e->d_ops_fw, (int)nops, e->N, e->d_norms);
+        KH_HIP(hipGetLastError());
+    }
+    double tab[KH_MAX_DEGREE + 1];
+    kh_build_degree_table(e->tol, tab);
+    KH_TRY(dev_upload(e, &e->d_deg_theta, tab, sizeof(tab)));
+    return dev_upload(e, &e->d_dt, pr->dt, sizeof(double) * (e->nt - 1));
+}
+
+// `launch(d)` on a zeroed device buffer of `bytes`, copied back to `out` (the set-up kernels that answer a question)
+template <class Launch>
+static int device_probe(void *out, size_t bytes, Launch &&launch) {
+    void *d = nullptr;
+    KH_HIP(hipMalloc(&d, bytes));
+    hipError_t err = hipMemset(d, 0, bytes);
+    if (err == hipSuccess) {
+        launch(d);
+        err = hipGetLastError();  // (the launch's own verdict, not whatever the copy below reports)
+    }
+    if (err == hipSuccess) err = hipMemcpy(out, d, bytes, hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    KH_HIP(err);
+    return KH_OK;
+}
+
+// What the detection found -> adj_sign, real spectrum, Hermitian defect.  ctl_plus / ctl_minus: every control operator
+// equals +/- its adjoint, bit for bit; drift_plus: the drift equals its adjoint; fro2(v): || Hermitian part of the
+// drift ||_F^2, asked only where the controls qualify.  Every generator Hermitian and f = -+i: real spectrum (the
+// shorter series of kh_common.h); f A anti-Hermitian up to a small Hermitian part of the drift (a weakly damped
+// Liouvillian; a Hamiltonian with a small anti-Hermitian part): the same series with a margin.
+template <class Fro2>
+static int classify_operators(const kh_engine *e, const kh_problem *pr, bool ctl_plus, bool ctl_minus, bool drift_plus,
+                              Fro2 &&fro2, KhFacts &f) {
+    f.adj_sign = ctl_plus ? 1.0 : (ctl_minus ? -1.0 : 0.0);
+    f.real_spectrum = ctl_plus && drift_plus && !e->is_super;
+    if (e->is_super ? ctl_minus : ctl_plus) {
+        double v = 0.0, dt_max = 0.0;
+        KH_TRY(fro2(v));
+        for (int n = 0; n < e->nt - 1; ++n) dt_max = pr->dt[n] > dt_max ? pr->dt[n] : dt_max;
+        f.imag_defect = sqrt(v) * dt_max;
+    }
+    return KH_OK;
+}
+
+// dense operators: the device-side detection kernels
+static int detect_dense(kh_engine *e, const kh_problem *pr, KhFacts &f) {
+    const int nops = e->K * (1 + e->L);
+    int flags[3] = {1, 1, 1};
+    KH_TRY(device_probe(flags, sizeof(flags), [&](void *d) {
+        kh_adjoint_sign_kernel<<<(unsigned)(nops < 1024 ? nops : 1024), 256>>>(e->d_ops_fw, e->d_ops_bw, nops, 1 + e->L, e->N, (int *)d);
+    }));
+    return classify_operators(e, pr, flags[0] == 0, flags[1] == 0, flags[2] == 0, [&](double &v) {
+        return device_probe(&v, sizeof(v), [&](void *d) {
+            kh_herm_defect_kernel<<<(unsigned)(e->K < 1024 ? e->K : 1024), 256>>>(e->d_ops_fw, e->d_ops_bw, nops, 1 + e->L, e->N,
+                                                                                  e->is_super ? 1.0 : -1.0, (unsigned long long *)d);
+        });
+    }, f);
+}
+
+// Sparse operators: the same questions asked of canonical host copies, and the padded row form (kh_ell.h), one structure
+// per distinct operator list and direction: the matrix in registers where the rows fit (N <= 2048), else -- or with
+// KH_KERNEL=ellstream -- the streamed form (N <= 4096, rows up to 32 entries): the same pools with their own row count,
+// read per term.
+static int build_sparse(kh_engine *e, const kh_problem *pr, const kh_csr *csr_fw, const kh_csr *csr_bw,
+                        const std::vector<const cplx *> &fw, KhFacts &f) {
+    const size_t nops = fw.size();
+    // canonical host copies of every distinct operator and of its conjugate transpose (small: a few entries per row)
+    std::map<const void *, HostCsr> host_fw, host_bw;
+    for (size_t i = 0; i < nops; ++i) {
+        if (fw[i] == nullptr || host_fw.count(fw[i])) continue;
+        KH_HIP(fetch_csr(csr_fw[i], e->N, host_fw[fw[i]]));
+        KH_HIP(fetch_csr(csr_bw[i], e->N, host_bw[fw[i]]));
+    }
+    if (e->L >= 1) {
+        bool ctl_plus = true, ctl_minus = true, drift_plus = true;
+        double fro2 = 0.0;
+        for (size_t i = 0; i < nops; ++i) {
+            if (fw[i] == nullptr) continue;
+            const HostCsr &a = host_fw[fw[i]], &b = host_bw[fw[i]];
+            if (i % (size_t)(1 + e->L) == 0) {
+                drift_plus = drift_plus && csr_equal(a, b, 1.0);
+                fro2 = std::max(fro2, csr_part_fro2(a, b, e->is_super ? 1.0 : -1.0));
+            } else {
+                ctl_plus = ctl_plus && csr_equal(a, b, 1.0);
+                ctl_minus = ctl_minus && csr_equal(a, b, -1.0);
+            }
+        }
+        KH_TRY(classify_operators(e, pr, ctl_plus, ctl_minus, drift_plus, [&](double &v) { return v = fro2, KH_OK; }, f));
+    }
+    const bool want_stream = e->sw.kernel_is("ellstream");
+    for (int form = want_stream ? 1 : 0; form < 2 && !f.ell; ++form) {
+        const bool stream = form == 1;
+        if (e->N > (stream ? KH_ELLS_NMAX : KH_ELL_NMAX) || e->L > KH_MAX_L || e->sw.kernel_is("generic")) continue;
+        if (stream && !e->sw.ellstream) continue;
+        bool ok = true;
+        int E_max = 0, ec_max = 0;
+        std::map<std::vector<const void *>, std::pair<KhEll, KhEll>> made;
+        std::vector<KhEll> ell_fw(e->K), ell_bw(e->K);
+        std::vector<int> off_pool;
+        std::vector<cplx> vals_pool;
+        for (int k = 0; k < e->K && ok; ++k) {
+            std::vector<const void *> key(fw.begin() + (size_t)k * (1 + e->L), fw.begin() + (size_t)(k + 1) * (1 + e->L));
+            auto it = made.find(key);
+            if (it == made.end()) {
+                KhEll pair[2];
+                for (int dir = 0; dir < 2 && ok; ++dir) {
+                    std::vector<const HostCsr *> ops_h;
+                    for (const void *ptr : key)
+                        ops_h.push_back(ptr == nullptr ? nullptr : (dir == 0 ? &host_fw[ptr] : &host_bw[ptr]));
+                    std::vector<int> off;
+                    std::vector<cplx> vals;
+                    int E = 0, Ec = 0;
+                    ok = build_ell_host(ops_h, e->N, off, vals, E, Ec, stream);
+                    if (!ok) break;
+                    ec_max = std::max(ec_max, Ec);
+                    pair[dir].off_at = (long long)off_pool.size();
+                    pair[dir].vals_at = (long long)vals_pool.size();
+                    off_pool.insert(off_pool.end(), off.begin(), off.end());
+                    vals_pool.insert(vals_pool.end(), vals.begin(), vals.end());
+                    pair[dir].E = E;
+                    pair[dir].Ec = Ec;
+                    pair[dir].rows = stream ? (e->N + 63) / 64 * 64 : kh_ell_rows(e->N);
+                    pair[dir].pad_ = 0;
+                    E_max = std::max(E_max, E);
+                }
+                if (!ok) break;
+                it = made.emplace(key, std::make_pair(pair[0], pair[1])).first;
+            }
+            ell_fw[k] = it->second.first;
+            ell_bw[k] = it->second.second;
+        }
+        if (!ok) continue;
+        f.ell = true;
+        f.ell_stream = stream;
+        f.ell_E = E_max;
+        KH_TRY(dev_upload(e, &e->d_ell_off, off_pool.data(), sizeof(int) * off_pool.size()));
+        KH_TRY(dev_upload(e, &e->d_ell_vals, vals_pool.data(), sizeof(cplx) * vals_pool.size()));
+        KH_TRY(dev_upload(e, &e->d_ell_fw, ell_fw.data(), sizeof(KhEll) * e->K));
+        KH_TRY(dev_upload(e, &e->d_ell_bw, ell_bw.data(), sizeof(KhEll) * e->K));
+        if (stream) {
+            // one scratch plane per workgroup (update sweep: K of them; plain sweeps: at most one per CU)
+            e->ell_scratch_stride = (long long)std::max(ec_max, 4) * ((e->N + 63) / 64 * 64);
+            const int wgs = e->K < e->num_cus ? e->K : e->num_cus;  // (the update sweep takes K <= #CUs workgroups, the plain sweeps at most #CUs)
+            KH_TRY(dev_alloc(e, &e->d_ell_scratch, sizeof(cplx) * (size_t)e->ell_scratch_stride * wgs));
+        }
+    }
+    return KH_OK;
+}
+
+// Ensembles: is every objective's operator list (H0, s_k H1) with objective 0's H0 and H1?  (kh_ens_detect_kernel;
+// the scales s_k stay in d_ens_scale)
+static int detect_ensemble(kh_engine *e, const std::vector<const cplx *> &fw, bool &found) {
+    found = false;
+    // reference element: the largest component of objective 0's control operator
+    std::vector<cplx> ref((size_t)e->N * e->N);
+    KH_HIP(hipMemcpy(ref.data(), fw[1], sizeof(cplx) * ref.size(), hipMemcpyDeviceToHost));
+    int ref_idx = 0, ref_comp = 0;
+    double best = 0.0;
+    for (size_t i = 0; i < ref.size(); ++i) {
+        if (fabs(ref[i].x) > best) best = fabs(ref[i].x), ref_idx = (int)i, ref_comp = 0;
+        if (fabs(ref[i].y) > best) best = fabs(ref[i].y), ref_idx = (int)i, ref_comp = 1;
+    }
+    if (!(best > 0.0)) return KH_OK;
+    KH_TRY(dev_alloc(e, &e->d_ens_scale, sizeof(double) * e->K));
+    int flags[2] = {1, 1};
+    KH_TRY(device_probe(flags, sizeof(flags), [&](void *d) {
+        kh_ens_detect_kernel<<<e->K, 256>>>(e->d_ops_fw, e->K, e->N, ref_idx, ref_comp, e->d_ens_scale, (int *)d);
+    }));
+    found = flags[0] == 0 && flags[1] == 0;
+    return KH_OK;
+}
+
+// P0 = H0 H0, P1 = H0 H1 + H1 H0, P2 = H1 H1 once per distinct operator (pair), per direction -> d_sq_fw / d_sq_bw
+// (sq: the same tables on the host)
+static int stage_squares(kh_engine *e, const std::vector<const cplx *> &fw, const std::vector<const cplx *> &bw,
+                         std::vector<const cplx *> sq[2]) {
+    const unsigned pgrid = (unsigned)(((size_t)e->N * e->N + 255) / 256 < 16 ? 16 : ((size_t)e->N * e->N + 255) / 256);
+    const size_t bytes = sizeof(cplx) * (size_t)e->N * e->N;
+    for (int dir = 0; dir < 2; ++dir) {
+        const std::vector<const cplx *> &tab = dir == 0 ? fw : bw;
+        sq[dir].assign((size_t)e->K * 3, nullptr);
+        KhCopies p0, p1, p2;
+        for (int k = 0; k < e->K; ++k) {
+            const cplx *H0 = tab[(size_t)k * 2], *H1 = tab[(size_t)k * 2 + 1];
+            auto product = [&](const cplx *X, const cplx *Y, int sym) {
+                return [=](cplx *dst) {
+                    kh_q2_product<<<pgrid, 256>>>(X, Y, dst, e->N, sym);
+                    return KH_OK;
+                };
+            };
+            KH_TRY(p0.get(e, H0, nullptr, bytes, product(H0, H0, 0), &sq[dir][(size_t)k * 3]));
+            if (H1 == nullptr) continue;
+            KH_TRY(p2.get(e, H1, nullptr, bytes, product(H1, H1, 0), &sq[dir][(size_t)k * 3 + 2]));
+            KH_TRY(p1.get(e, H0, H1, bytes, product(H0, H1, 1), &sq[dir][(size_t)k * 3 + 1]));
+        }
+        KH_HIP(hipGetLastError());
+        KH_TRY(dev_upload(e, dir == 0 ? &e->d_sq_fw : &e->d_sq_bw, sq[dir].data(), sizeof(cplx *) * sq[dir].size()));
+    }
+    return KH_OK;
+}
+
+// The cooperative kernels (kh_coop.h): exchange buffers, fragment-ordered copies of the (shared) operators and, for one
+// control, of P0, P1, P2; the non-zero blocks of H_1^+ for the adjoint-side sums
+static int stage_coop(kh_engine *e, const std::vector<const cplx *> &fw, const std::vector<const cplx *> &bw,
+                      const std::vector<const cplx *> sq[2]) {
+    const KhPlan &p = e->plan;
+    e->coop_vbuf_bytes = sizeof(kh_u64) * KH_COOP_RING * (size_t)p.coop_Y * p.coop_G * 16 * KH_COOP_COLS * 4;
+    KH_TRY(dev_alloc(e, &e->d_coop_vbuf, e->coop_vbuf_bytes));
+    KH_TRY(dev_alloc(e, &e->d_coop_xcc, sizeof(unsigned int) * (size_t)p.coop_G * p.coop_Y));
+    const size_t elems = kh_coop_table_elems(p.coop_G, p.coop_ks);  // (row blocks padded apart: kh_coop_table_stride)
+    const size_t frag_elems = (size_t)p.coop_G * KH_COOP_WAVES * p.coop_ks * 64;
+    // (+ one zero-slot word per (row block, wave) behind the table: kh_coop_mask_kernel)
+    const size_t bytes = sizeof(cplx) * elems + sizeof(unsigned int) * p.coop_G * KH_COOP_WAVES;
+    auto permute = [&](const cplx *src, cplx *dst) -> int {
+        KH_HIP(hipMemset(dst, 0, sizeof(cplx) * elems));
+        kh_coop_permute_kernel<<<(unsigned)((frag_elems + 255) / 256), 256>>>(src, dst, e->N, p.coop_G, p.coop_ks, p.coop_cols);
+        kh_coop_mask_kernel<<<p.coop_G * KH_COOP_WAVES, 64>>>(dst, (unsigned int *)(dst + elems), p.coop_ks);
+        return KH_OK;
+    };
+    KhCopies copies;
+    for (int dir = 0; dir < 2; ++dir) {
+        const std::vector<const cplx *> ops((dir == 0 ? fw : bw).begin(), (dir == 0 ? fw : bw).begin() + 1 + e->L);
+        KH_TRY(stage_copies(e, copies, ops, bytes, nullptr, permute, dir == 0 ? &e->d_coop_fops_fw : &e->d_coop_fops_bw));
+        if (p.coop_sq) {
+            const std::vector<const cplx *> sq3(sq[dir].begin(), sq[dir].begin() + 3);
+            KH_TRY(stage_copies(e, copies, sq3, bytes, nullptr, permute, dir == 0 ? &e->d_coop_sq_fw : &e->d_coop_sq_bw));
+        }
+    }
+    if (p.coop_adj) {
+        e->coop_adj_op = bw[1];
+        KH_TRY(dev_alloc(e, &e->d_coop_adj_nz, (size_t)p.coop_G * p.coop_G));
+        kh_coop_adj_mask_kernel<<<p.coop_G * p.coop_G, 256>>>(bw[1], e->N, p.coop_G, e->d_coop_adj_nz);
+        KH_HIP(hipGetLastError());
+    }
+    return KH_OK;
+}
+
+// the series tables of the plan (every kernel family but the cooperative one reads them; that one where coop_series)
+static int stage_series(kh_engine *e) {
+    std::vector<double> tab(KH_MAX_DEGREE + 1), c0(KH_MAX_DEGREE + 1), rows((size_t)(KH_MAX_DEGREE + 1) * KH_Q2_ROWS * 2),
+        ratios((size_t)(KH_MAX_DEGREE + 1) * KH_RATIO_STRIDE);
+    if (e->plan.series_rows) {
+        kh_build_real_spectrum_rows(e->tol, tab.data(), c0.data(), rows.data(), ratios.data(), e->plan.series_cap,
+                                    e->plan.series_defect);
+    } else {
+        kh_build_degree_table(e->tol, tab.data());
+        kh_build_taylor_rows(c0.data(), rows.data(), ratios.data());
+    }
+    KH_TRY(dev_upload(e, &e->d_ratios, ratios.data(), sizeof(double) * ratios.size()));
+    KH_TRY(dev_upload(e, &e->d_q2_theta, tab.data(), sizeof(double) * tab.size()));
+    KH_TRY(dev_upload(e, &e->d_q2_c0, c0.data(), sizeof(double) * c0.size()));
+    return dev_upload(e, &e->d_q2_rows, rows.data(), sizeof(double) * rows.size());
+}
+
+template <class F>
+static auto with_ens(int ncg, F &&f) {
+    switch (ncg) {
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 4: return f(std::integral_constant<int, 4>{});
+        default: return f(std::integral_constant<int, 8>{});
+    }
+}
+
+// the two instantiations of the ensemble kernel with `ncg` column groups (first / second order), their LDS limit raised
+static int ens_forms(kh_engine *e, int ncg, const void *forms[2]) {
+    with_ens(ncg, [&](auto c) {
+        forms[0] = (const void *)kh_ens_forward_update<decltype(c)::value, false>;
+        forms[1] = (const void *)kh_ens_forward_update<decltype(c)::value, true>;
+        return 0;
+    });
+    for (int i = 0; i < 2; ++i) {
+        KH_TRY(ensure_dynamic_lds(e, forms[i], kh_ens_lds_bytes(ncg)));
+    }
+    return KH_OK;
+}
+
+// Everything but the validation of engine_create; on failure the caller destroys the half-built engine.
+static int engine_build(kh_engine *e, const kh_problem *pr, const kh_csr *csr_fw, const kh_csr *csr_bw) {
+    KH_HIP(hipGetDevice(&e->device));
+    hipDeviceProp_t prop;
+    KH_HIP(hipGetDeviceProperties(&prop, e->device));
+    e->num_cus = prop.multiProcessorCount;
+    // the generic kernels -- every engine's last resort -- keep four vectors of N elements in LDS: N <= 2540.  Sparse
+    // operators up to N = 4096 may still run the streamed padded-row kernels (gen_fits stays false then and whatever
+    // would need the generic kernels -- one launch per interval, more objectives than CUs -- is refused)
+    const size_t gen_lds = kh_gen_lds_bytes(e->N, csr_fw == nullptr);
+    e->gen_fits = !(gen_lds > (size_t)prop.sharedMemPerBlock && gen_lds > 160 * 1024);
+    if (!e->gen_fits && !(csr_fw != nullptr && e->N <= KH_ELLS_NMAX))
+        return kh_fail(KH_ERR_UNSUPPORTED, "N=%d needs %zu bytes of LDS", e->N, gen_lds);
+
+    // ---- facts
+    std::vector<const cplx *> fw, bw;
+    KH_TRY(stage_operators(e, pr, csr_fw, csr_bw, fw, bw));
+    KhFacts f;
+    f.K = e->K, f.N = e->N, f.L = e->L, f.num_cus = e->num_cus;
+    f.csr = csr_fw != nullptr;
+    f.theta_max = pr->theta_max;
+    f.shared = true;
+    for (size_t i = 0; i < fw.size() && f.shared; ++i) f.shared = fw[i] == fw[i % (size_t)(1 + e->L)];
+    f.has_h1 = e->L >= 1 && fw[1] != nullptr;
+    f.all_h1 = e->L >= 1;
+    for (int k = 0; k < e->K && f.all_h1; ++k) f.all_h1 = fw[(size_t)k * (1 + e->L) + 1] != nullptr;
+    if (e->L >= 1) {
+        KH_TRY(csr_fw == nullptr ? detect_dense(e, pr, f) : build_sparse(e, pr, csr_fw, csr_bw, fw, f));
+        if (e->sw.taylor) f.real_spectrum = false, f.imag_defect = -1.0;  // A/B switch: plain Taylor coefficients everywhere
+        if (e->sw.no_adj && csr_fw == nullptr) f.adj_sign = 0.0;        // A/B switch: keep <chi|H phi> on the forward side
+    } else if (csr_fw != nullptr) {
+        KH_TRY(build_sparse(e, pr, csr_fw, csr_bw, fw, f));
+    }
+    if (!e->gen_fits && !f.ell)
+        return kh_fail(KH_ERR_UNSUPPORTED, "N=%d: rows wider than 32 entries and no room for the generic kernels' vectors in LDS", e->N);
+    if (const int ncg = ens_candidate(f, e->sw)) {
+        bool found = false;
+        KH_TRY(detect_ensemble(e, fw, found));
+        if (found) f.ens_ncg = ncg;
+    }
+    e->adj_sign = f.adj_sign;
+
+    // ---- plan, and what it names
+    e->plan = plan_families(f, e->sw);
+    KhPlan &p = e->plan;
+    if (p.tilen) {
+        auto permute = [&](const cplx *src, cplx *dst) {
+            kh_tn_permute<<<KH_TN_NMAX / 4, KH_TN_THREADS>>>(src, dst, e->N);
+            return KH_OK;
+        };
+        const size_t bytes = sizeof(cplx) * (KH_TN_NMAX / 4) * KH_TN_THREADS;
+        KhCopies copies;  // (one per distinct operator over both directions)
+        KH_TRY(stage_copies(e, copies, fw, bytes, nullptr, permute, &e->d_tn_fw));
+        KH_TRY(stage_copies(e, copies, bw, bytes, nullptr, permute, &e->d_tn_bw));
+    }
+    if (p.tx) {
+        auto permute = [&](const cplx *src, cplx *dst) {
+            kh_tx_permute<<<8, KH_TX_THREADS>>>(src, dst, e->N);
+            return KH_OK;
+        };
+        const size_t bytes = sizeof(cplx) * 8 * KH_TX_THREADS;
+        cplx *zero_tile = nullptr;  // stands in for a control an objective does not have (no branches in the kernels' loads)
+        KH_TRY(dev_alloc(e, &zero_tile, bytes));
+        KH_HIP(hipMemset(zero_tile, 0, bytes));
+        KhCopies copies;
+        KH_TRY(stage_copies(e, copies, fw, bytes, zero_tile, permute, &e->d_tx_fw));
+        KH_TRY(stage_copies(e, copies, bw, bytes, zero_tile, permute, &e->d_tx_bw));
+    }
+    std::vector<const cplx *> sq[2];
+    if (p.stage_sq) KH_TRY(stage_squares(e, fw, bw, sq));
+    if (p.kind == KIND_COOP) KH_TRY(stage_coop(e, fw, bw, sq));
+    KH_TRY(stage_series(e));
+    if (p.kind_store == KIND_TILE_Q2)
+        KH_HIP(hipFuncSetAttribute((const void *)kh_q2_sweep_store, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kh_q2_lds_bytes()));
+    if (p.kind == KIND_TILE_Q2) {
+        // every instantiation a sweep of this engine may launch: one GPU / sharded, first / second order, sums on
+        // either side -- their register footprints differ
+        const void *forms[] = {(const void *)kh_q2_forward_update<false, true, true>, (const void *)kh_q2_forward_update<false, false, true>,
+                               (const void *)kh_q2_forward_update<true, false, true>, (const void *)kh_q2_forward_update<false, true>,
+                               (const void *)kh_q2_forward_update<false, false>,      (const void *)kh_q2_forward_update<true, false>};
+        for (const void *fn : forms)
+            KH_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kh_q2_lds_bytes()));
+        // every workgroup of the single-launch update sweep must be resident at once: ask the occupancy of the kernel
+        // as built (registers, LDS) instead of assuming one per CU; if it does not fit, the generic kernels (which
+        // loop over objectives inside at most #CUs workgroups) take over
+        int rc = KH_OK;
+        if (!p.mini && e->K > 1)
+            for (const void *fn : forms)
+                if (rc == KH_OK) rc = check_residency(e, fn, KH_Q2_THREADS, kh_q2_lds_bytes(), e->K, "kh_q2_forward_update");
+        if (rc != KH_OK) {
+            p.kind = KIND_GENERIC;  // (the plain sweeps keep the q2 kernel: its workgroups do not wait for each other)
+            p.grid_update = e->K < p.max_wgs ? e->K : p.max_wgs;
+        }
+    }
+    if (p.ens) {  // all ens_G workgroups resident at once?  (as the q2 path asks for its instantiations)
+        e->ens_H0 = fw[0];
+        e->ens_H1 = fw[1];
+        const void *forms[2];
+        int rc = ens_forms(e, p.ens_ncg, forms);
+        for (const void *fn : forms)
+            if (rc == KH_OK) rc = check_residency(e, fn, KH_ENS_THREADS, kh_ens_lds_bytes(p.ens_ncg), p.ens_G, "kh_ens_forward_update");
+        if (rc != KH_OK) p.ens = false;
+    }
+
+    // ---- workspaces
+    const int Lx = e->L > 0 ? e->L : 1;
+    const int slot_wgs = p.kind == KIND_COOP && p.coop_G * p.coop_Y > p.grid_update ? p.coop_G * p.coop_Y : p.grid_update;
+    e->slots_bytes = sizeof(kh_u64) * 2 * (size_t)slot_wgs * Lx * 2;
+    KH_TRY(dev_alloc(e, &e->d_phi, sizeof(cplx) * (size_t)e->K * e->N));
+    KH_TRY(dev_alloc(e, &e->d_slots, e->slots_bytes));
+    KH_TRY(dev_alloc(e, &e->d_abort, 2 * sizeof(unsigned int)));  // [0] abort flag, [1] (KH_TIMING) polling rounds
+    KH_TRY(dev_alloc(e, &e->d_wait_ticks, 4 * sizeof(unsigned long long)));
+    KH_TRY(dev_alloc(e, &e->d_stats, sizeof(double) * 68));
+    KH_TRY(dev_alloc(e, &e->d_wg_partial, sizeof(double) * (size_t)p.grid_update * Lx));
+    KH_TRY(dev_alloc(e, &e->d_step_partial, sizeof(double) * Lx));
+    KH_HIP(hipMemset(e->d_abort, 0, 2 * sizeof(unsigned int)));
+    KH_HIP(hipMemset(e->d_wait_ticks, 0, 4 * sizeof(unsigned long long)));
+    KH_HIP(hipMemset(e->d_stats, 0, sizeof(double) * 68));
+    KH_HIP(hipDeviceSynchronize());
+    return KH_OK;
+}
+
 // csr_fw / csr_bw: [K*(1+L)] sparse operators and their conjugate transposes (pr->ops then holds their
 // data arrays), or both NULL for dense row-major operators
 static int engine_create(const kh_problem *pr, const kh_csr *csr_fw, const kh_csr *csr_bw, kh_engine **out) {
@@ -647,7 +1385,6 @@ static int engine_create(const kh_problem *pr, const kh_csr *csr_fw, const kh_cs
     if (pr->dt == nullptr || pr->ops == nullptr) return kh_fail(KH_ERR_INVALID, "dt/ops missing");
     for (int n = 0; n < pr->nt - 1; ++n)
         if (!(pr->dt[n] > 0.0)) return kh_fail(KH_ERR_INVALID, "dt[%d] = %g is not positive", n, pr->dt[n]);
-    const size_t nops = (size_t)pr->K * (1 + pr->L);
     for (int k = 0; k < pr->K; ++k)
         if (pr->ops[(size_t)k * (1 + pr->L)] == nullptr)
             return kh_fail(KH_ERR_INVALID, "objective %d has no drift operator", k);
@@ -659,767 +1396,12 @@ static int engine_create(const kh_problem *pr, const kh_csr *csr_fw, const kh_cs
     e->nt = pr->nt;
     e->is_super = pr->is_super ? 1 : 0;
     e->tol = pr->tol > 0.0 ? pr->tol : ldexp(1.0, -53);
-    e->theta_max = pr->theta_max > 0.0 ? pr->theta_max : 1.0;
-#define KH_HIP_E(call)                                                                   \
-    do {                                                                                 \
-        hipError_t _e = (call);                                                          \
-        if (_e != hipSuccess) {                                                          \
-            kh_engine_destroy(e);                                                        \
-            return kh_fail(KH_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(_e));   \
-        }                                                                                \
-    } while (0)
-    KH_HIP_E(hipGetDevice(&e->device));
-    hipDeviceProp_t prop;
-    KH_HIP_E(hipGetDeviceProperties(&prop, e->device));
-    e->num_cus = prop.multiProcessorCount;
-    // the generic kernels -- every engine's last resort -- keep four vectors of N elements in LDS: N <= 2540.  Sparse
-    // operators up to N = 4096 may still run the streamed padded-row kernels (decided below: gen_fits stays false then
-    // and whatever would need the generic kernels -- one launch per interval, more objectives than CUs -- is refused)
-    const bool gen_fits = !(kh_gen_lds_bytes(e->N, csr_fw == nullptr) > (size_t)prop.sharedMemPerBlock && kh_gen_lds_bytes(e->N, csr_fw == nullptr) > 160 * 1024);
-    e->gen_fits = gen_fits;
-    if (!gen_fits && !(csr_fw != nullptr && e->N <= KH_ELLS_NMAX)) {
+    e->sw = read_switches();
+    const int rc = engine_build(e, pr, csr_fw, csr_bw);
+    if (rc != KH_OK) {
         kh_engine_destroy(e);
-        return kh_fail(KH_ERR_UNSUPPORTED, "N=%d needs %zu bytes of LDS", pr->N, kh_gen_lds_bytes(pr->N, csr_fw == nullptr));
+        return rc;
     }
-
-    // ---- operator tables: forward pointers as given, adjoints staged once per distinct operator
-    std::vector<const cplx *> fw(nops), bw(nops);
-    std::map<const void *, cplx *> adj_of;
-    for (size_t i = 0; i < nops; ++i) {
-        const cplx *src = (const cplx *)pr->ops[i];
-        fw[i] = src;
-        if (src == nullptr) {
-            bw[i] = nullptr;
-            continue;
-        }
-        if (csr_fw != nullptr) {  // the caller supplies the conjugate transposes
-            bw[i] = (const cplx *)csr_bw[i].data;
-            continue;
-        }
-        auto it = adj_of.find(src);
-        if (it == adj_of.end()) {
-            cplx *dst = nullptr;
-            KH_HIP_E(hipMalloc(&dst, sizeof(cplx) * (size_t)e->N * e->N));
-            e->owned.push_back(dst);
-            const int tiles = (e->N + 31) / 32;
-            kh_adjoint_kernel<<<dim3(tiles, tiles), 256>>>(src, dst, e->N);
-            it = adj_of.emplace(src, dst).first;
-        }
-        bw[i] = it->second;
-    }
-    KH_HIP_E(hipGetLastError());
-    KH_HIP_E(hipMalloc((void **)&e->d_ops_fw, sizeof(cplx *) * nops));
-    KH_HIP_E(hipMalloc((void **)&e->d_ops_bw, sizeof(cplx *) * nops));
-    KH_HIP_E(hipMemcpy((void *)e->d_ops_fw, fw.data(), sizeof(cplx *) * nops, hipMemcpyHostToDevice));
-    KH_HIP_E(hipMemcpy((void *)e->d_ops_bw, bw.data(), sizeof(cplx *) * nops, hipMemcpyHostToDevice));
-    if (csr_fw == nullptr && e->L >= 1) {  // is every control operator its own (negative) adjoint, bit for bit?
-        int *d_flags = nullptr, flags[3] = {1, 1, 1};
-        KH_HIP_E(hipMalloc(&d_flags, sizeof(flags)));
-        hipError_t err = hipMemset(d_flags, 0, sizeof(flags));
-        if (err == hipSuccess) {
-            kh_adjoint_sign_kernel<<<(unsigned)(nops < 1024 ? nops : 1024), 256>>>(e->d_ops_fw, e->d_ops_bw, (int)nops,
-                                                                                   1 + e->L, e->N, d_flags);
-            err = hipMemcpy(flags, d_flags, sizeof(flags), hipMemcpyDeviceToHost);
-        }
-        (void)hipFree(d_flags);
-        KH_HIP_E(err);
-        e->adj_sign = flags[0] == 0 ? 1.0 : (flags[1] == 0 ? -1.0 : 0.0);
-        // every generator Hermitian and f = -+i: real spectrum (the q2 kernels' shorter series, kh_common.h)
-        e->real_spectrum = flags[0] == 0 && flags[2] == 0 && !e->is_super;
-        {   // f A anti-Hermitian up to a small Hermitian part of the drift (a weakly damped Liouvillian; a Hamiltonian
-            // with a small anti-Hermitian part): the shorter series of kh_common.h applies with a margin
-            const bool controls_ok = e->is_super ? flags[1] == 0 : flags[0] == 0;
-            if (controls_ok) {
-                unsigned long long *d_max = nullptr, bits = 0;
-                KH_HIP_E(hipMalloc(&d_max, sizeof(bits)));
-                hipError_t err2 = hipMemset(d_max, 0, sizeof(bits));
-                if (err2 == hipSuccess) {
-                    kh_herm_defect_kernel<<<(unsigned)(e->K < 1024 ? e->K : 1024), 256>>>(
-                        e->d_ops_fw, e->d_ops_bw, (int)nops, 1 + e->L, e->N, e->is_super ? 1.0 : -1.0, d_max);
-                    err2 = hipMemcpy(&bits, d_max, sizeof(bits), hipMemcpyDeviceToHost);
-                }
-                (void)hipFree(d_max);
-                KH_HIP_E(err2);
-                double fro2, dt_max = 0.0;
-                memcpy(&fro2, &bits, sizeof(fro2));
-                for (int n = 0; n < e->nt - 1; ++n) dt_max = pr->dt[n] > dt_max ? pr->dt[n] : dt_max;
-                e->imag_defect = sqrt(fro2) * dt_max;
-            }
-        }
-        if (const char *d = getenv("KH_TAYLOR"))  // A/B switch: plain Taylor coefficients everywhere
-            if (atoi(d) != 0) {
-                e->real_spectrum = false;
-                e->imag_defect = -1.0;
-            }
-        if (const char *d = getenv("KH_NO_ADJ"))  // A/B switch: keep <chi|H phi> on the forward side
-            if (atoi(d) != 0) e->adj_sign = 0.0;
-    }
-    KH_HIP_E(hipMalloc(&e->d_norms, sizeof(double) * nops));
-    if (csr_fw != nullptr) {
-        static_assert(sizeof(KhCsr) == sizeof(kh_csr), "kh_csr layout");
-        KH_HIP_E(hipMalloc(&e->d_csr_fw, sizeof(KhCsr) * nops));
-        KH_HIP_E(hipMalloc(&e->d_csr_bw, sizeof(KhCsr) * nops));
-        KH_HIP_E(hipMemcpy(e->d_csr_fw, csr_fw, sizeof(KhCsr) * nops, hipMemcpyHostToDevice));
-        KH_HIP_E(hipMemcpy(e->d_csr_bw, csr_bw, sizeof(KhCsr) * nops, hipMemcpyHostToDevice));
-    }
-    bool ell_ok = false;
-    if (csr_fw != nullptr) {
-        // canonical host copies of every distinct operator and of its conjugate transpose (small: a few entries per row)
-        std::map<const void *, HostCsr> host_fw, host_bw;
-        for (size_t i = 0; i < nops; ++i) {
-            if (fw[i] == nullptr || host_fw.count(fw[i])) continue;
-            KH_HIP_E(fetch_csr(csr_fw[i], e->N, host_fw[fw[i]]));
-            KH_HIP_E(fetch_csr(csr_bw[i], e->N, host_bw[fw[i]]));
-        }
-        // what the dense engines ask the device (kh_adjoint_sign_kernel, kh_herm_defect_kernel): is every generator
-        // Hermitian (real spectrum), or anti-Hermitian up to a small part of the drift?  -> the shorter series
-        if (e->L >= 1) {
-            bool ctl_plus = true, ctl_minus = true, drift_plus = true;
-            double fro2 = 0.0;
-            for (size_t i = 0; i < nops; ++i) {
-                if (fw[i] == nullptr) continue;
-                const HostCsr &a = host_fw[fw[i]], &b = host_bw[fw[i]];
-                if (i % (size_t)(1 + e->L) == 0) {
-                    drift_plus = drift_plus && csr_equal(a, b, 1.0);
-                    fro2 = std::max(fro2, csr_part_fro2(a, b, e->is_super ? 1.0 : -1.0));
-                } else {
-                    ctl_plus = ctl_plus && csr_equal(a, b, 1.0);
-                    ctl_minus = ctl_minus && csr_equal(a, b, -1.0);
-                }
-            }
-            e->adj_sign = ctl_plus ? 1.0 : (ctl_minus ? -1.0 : 0.0);
-            e->real_spectrum = ctl_plus && drift_plus && !e->is_super;
-            if (e->is_super ? ctl_minus : ctl_plus) {
-                double dt_max = 0.0;
-                for (int n = 0; n < e->nt - 1; ++n) dt_max = pr->dt[n] > dt_max ? pr->dt[n] : dt_max;
-                e->imag_defect = sqrt(fro2) * dt_max;
-            }
-            if (const char *d = getenv("KH_TAYLOR"))
-                if (atoi(d) != 0) {
-                    e->real_spectrum = false;
-                    e->imag_defect = -1.0;
-                }
-        }
-        // the padded row form (kh_ell.h): one structure per distinct operator list and direction
-        const char *force_k = getenv("KH_KERNEL");
-        // ... matrix in registers where the rows fit (N <= 2048), else -- or with KH_KERNEL=ellstream -- the streamed form
-        // (N <= 4096, rows up to 32 entries): the same pools with their own row count, read per term
-        const bool want_stream = force_k && strcmp(force_k, "ellstream") == 0;
-        for (int form = want_stream ? 1 : 0; form < 2 && !ell_ok; ++form) {
-            const bool stream = form == 1;
-            if (e->N > (stream ? KH_ELLS_NMAX : KH_ELL_NMAX) || e->L > KH_MAX_L || (force_k && strcmp(force_k, "generic") == 0)) continue;
-            if (stream && getenv("KH_NO_ELLSTREAM") && atoi(getenv("KH_NO_ELLSTREAM"))) continue;
-            ell_ok = true;
-            e->ell_E = 0;
-            int ec_max = 0;
-            std::map<std::vector<const void *>, std::pair<KhEll, KhEll>> made;
-            std::vector<KhEll> ell_fw(e->K), ell_bw(e->K);
-            std::vector<int> off_pool;
-            std::vector<cplx> vals_pool;
-            for (int k = 0; k < e->K && ell_ok; ++k) {
-                std::vector<const void *> key(fw.begin() + (size_t)k * (1 + e->L), fw.begin() + (size_t)(k + 1) * (1 + e->L));
-                auto it = made.find(key);
-                if (it == made.end()) {
-                    KhEll pair[2];
-                    for (int dir = 0; dir < 2 && ell_ok; ++dir) {
-                        std::vector<const HostCsr *> ops_h;
-                        for (const void *ptr : key)
-                            ops_h.push_back(ptr == nullptr ? nullptr : (dir == 0 ? &host_fw[ptr] : &host_bw[ptr]));
-                        std::vector<int> off;
-                        std::vector<cplx> vals;
-                        int E = 0, Ec = 0;
-                        if (!build_ell_host(ops_h, e->N, off, vals, E, Ec, stream)) {
-                            ell_ok = false;
-                            break;
-                        }
-                        ec_max = std::max(ec_max, Ec);
-                        pair[dir].off_at = (long long)off_pool.size();
-                        pair[dir].vals_at = (long long)vals_pool.size();
-                        off_pool.insert(off_pool.end(), off.begin(), off.end());
-                        vals_pool.insert(vals_pool.end(), vals.begin(), vals.end());
-                        pair[dir].E = E;
-                        pair[dir].Ec = Ec;
-                        pair[dir].rows = stream ? (e->N + 63) / 64 * 64 : kh_ell_rows(e->N);
-                        pair[dir].pad_ = 0;
-                        e->ell_E = std::max(e->ell_E, E);
-                    }
-                    if (!ell_ok) break;
-                    it = made.emplace(key, std::make_pair(pair[0], pair[1])).first;
-                }
-                ell_fw[k] = it->second.first;
-                ell_bw[k] = it->second.second;
-            }
-            if (ell_ok) {
-                KH_HIP_E(hipMalloc(&e->d_ell_off, sizeof(int) * off_pool.size()));
-                KH_HIP_E(hipMalloc(&e->d_ell_vals, sizeof(cplx) * vals_pool.size()));
-                KH_HIP_E(hipMemcpy(e->d_ell_off, off_pool.data(), sizeof(int) * off_pool.size(), hipMemcpyHostToDevice));
-                KH_HIP_E(hipMemcpy(e->d_ell_vals, vals_pool.data(), sizeof(cplx) * vals_pool.size(), hipMemcpyHostToDevice));
-                KH_HIP_E(hipMalloc(&e->d_ell_fw, sizeof(KhEll) * e->K));
-                KH_HIP_E(hipMalloc(&e->d_ell_bw, sizeof(KhEll) * e->K));
-                KH_HIP_E(hipMemcpy(e->d_ell_fw, ell_fw.data(), sizeof(KhEll) * e->K, hipMemcpyHostToDevice));
-                KH_HIP_E(hipMemcpy(e->d_ell_bw, ell_bw.data(), sizeof(KhEll) * e->K, hipMemcpyHostToDevice));
-                e->ell_stream = stream;
-                if (stream) {
-                    // one scratch plane per workgroup (update sweep: K of them; plain sweeps: at most one per CU)
-                    e->ell_scratch_stride = (long long)std::max(ec_max, 4) * ((e->N + 63) / 64 * 64);
-                    const int wgs = e->K < e->num_cus ? e->K : e->num_cus;  // (the update sweep takes K <= #CUs workgroups, the plain sweeps at most #CUs)
-                    KH_HIP_E(hipMalloc(&e->d_ell_scratch, sizeof(cplx) * (size_t)e->ell_scratch_stride * wgs));
-                }
-            }
-        }
-    }
-    if (!e->gen_fits && !ell_ok) {
-        kh_engine_destroy(e);
-        return kh_fail(KH_ERR_UNSUPPORTED, "N=%d: rows wider than 32 entries and no room for the generic kernels' vectors in LDS", pr->N);
-    }
-    if (pr->op_norms != nullptr) {
-        KH_HIP_E(hipMemcpy(e->d_norms, pr->op_norms, sizeof(double) * nops, hipMemcpyHostToDevice));
-    } else {
-        kh_fro_norms<<<(unsigned)nops, 256>>>(e->d_ops_fw, (int)nops, e->N, e->d_norms);
-        KH_HIP_E(hipGetLastError());
-    }
-    {
-        double tab[KH_MAX_DEGREE + 1];
-        kh_build_degree_table(e->tol, tab);
-        KH_HIP_E(hipMalloc(&e->d_deg_theta, sizeof(tab)));
-        KH_HIP_E(hipMemcpy(e->d_deg_theta, tab, sizeof(tab), hipMemcpyHostToDevice));
-    }
-    KH_HIP_E(hipMalloc(&e->d_dt, sizeof(double) * (e->nt - 1)));
-    KH_HIP_E(hipMemcpy(e->d_dt, pr->dt, sizeof(double) * (e->nt - 1), hipMemcpyHostToDevice));
-
-    // ---- kernel family
-    e->kind = KIND_GENERIC;
-    const int max_wgs = e->num_cus < 64 * KH_GATHER_CHUNKS ? e->num_cus : 64 * KH_GATHER_CHUNKS;
-    e->grid_update = e->K < max_wgs ? e->K : max_wgs;
-    if (const char *d = getenv("KH_COOP_LAUNCH")) e->coop_launch = atoi(d) != 0;
-    if (const char *d = getenv("KH_Q2_SINGLE")) e->q2_single = atoi(d) != 0;
-    if (const char *d = getenv("KH_TILE_SINGLE")) e->tile_single = atoi(d) != 0;
-    if (const char *d = getenv("KH_COOP_SINGLE")) e->coop_single = atoi(d) != 0;
-    if (const char *d = getenv("KH_P2P_FAIL_AT")) e->p2p_fail_at = atoi(d);
-    if (const char *d = getenv("KH_P2P_FAIL_RANK")) e->p2p_fail_rank = atoi(d);
-    if (const char *d = getenv("KH_P2P_FAIL_SWEEP")) e->p2p_fail_sweep = atoi(d);
-    if (const char *d = getenv("KH_Q4")) e->use_q4 = atoi(d) != 0;
-    if (const char *d = getenv("KH_POLL_DELAY")) {
-        e->poll_delay = atoi(d);
-        e->poll_delay_set = true;
-    }
-    if (const char *d = getenv("KH_ADJ_DELAY")) e->adj_poll_delay = atoi(d);
-    if (const char *d = getenv("KH_COOP_DELAY")) e->coop_poll_delay = atoi(d);
-    if (const char *d = getenv("KH_TIMEOUT_MS"))  // e.g. under a profiler that slows the kernels down
-        if (atoll(d) > 0) {
-            e->timeout_ticks = atoll(d) * 100000LL;
-            e->timeout_set = true;
-        }
-    const char *force = getenv("KH_KERNEL");  // "generic" | "tile256" | "tile512" | "q2" | "coop" (testing)
-    const bool tile_ok = csr_fw == nullptr && e->N <= KH_TILE_N && e->L >= 1 && e->L <= 4 && e->K <= max_wgs;
-    // More objectives than CUs, one control: 256-thread workgroups (one wave per SIMD, 256 VGPRs) fit two per
-    // CU, so up to 2 x #CUs objectives stay co-resident -- and the two workgroups of a CU hide each other's
-    // phase latency.
-    const int max_wgs2 = 2 * e->num_cus < 64 * KH_GATHER_CHUNKS_WIDE ? 2 * e->num_cus : 64 * KH_GATHER_CHUNKS_WIDE;
-    const bool tile2_ok = csr_fw == nullptr && e->N <= KH_TILE_N && e->L == 1 && e->K > max_wgs && e->K <= max_wgs2;
-    if (tile2_ok && !(force && strcmp(force, "generic") == 0)) {
-        e->kind = KIND_TILE_RPT2;
-        e->grid_update = e->K;
-    }
-    // More objectives than can be co-resident (so no in-kernel exchange), tile-sized: the register-tile kernel with
-    // ONE LAUNCH PER INTERVAL (the form the sharded sweep uses, kh_update_step) -- every launch re-stages the two
-    // operator tiles of its objectives (128 KiB each, from L2 / the Infinity Cache), which still beats the generic
-    // kernels' re-streaming of the operators for every term by 5x (K = 1024: 207 -> see DESIGN.md us per interval).
-    const bool tile_step_ok = csr_fw == nullptr && e->N <= KH_TILE_N && e->L >= 1 && e->L <= 4 && !tile_ok && !tile2_ok &&
-                              e->K > max_wgs && !(getenv("KH_NO_STEPWISE") && atoi(getenv("KH_NO_STEPWISE")));
-    if (tile_step_ok && force == nullptr) {
-        e->kind = KIND_TILE_RPT1;
-        e->grid_update = e->K;
-        e->stepwise_only = true;
-        // one workgroup per CU; as few workgroups as give everybody the same number of objectives (K = 384, two controls:
-        // 192 x 2 in 23.9 us per interval against 128 x 2 + 128 x 1 in 24.5)
-        int G = e->num_cus < 64 * KH_GATHER_CHUNKS ? e->num_cus : 64 * KH_GATHER_CHUNKS;
-        if (e->K > G) G = (e->K + (e->K + G - 1) / G - 1) / ((e->K + G - 1) / G);
-        if (const char *g = getenv("KH_STREAM_G"))  // testing
-            if (atoi(g) >= 1 && atoi(g) <= G) G = atoi(g);
-        if (G > e->K) G = e->K;
-        e->stream_G = G;
-        e->stream = (long long)G * KH_STREAM_MMAX >= e->K && !(getenv("KH_NO_STREAM") && atoi(getenv("KH_NO_STREAM")));
-    }
-    if (tile_ok && !(force && strcmp(force, "generic") == 0)) {
-        // two waves per SIMD are needed to keep the fp64 FMA pipe issuing back to back
-        e->kind = KIND_TILE_RPT1;
-        if (e->L == 1) e->kind = KIND_TILE_Q2;  // two Taylor terms per phase (kh_tile64q2.h)
-        if (force && strcmp(force, "tile512") == 0) e->kind = KIND_TILE_RPT1;
-        if (force && strcmp(force, "tile256") == 0 && e->L == 1) e->kind = KIND_TILE_RPT2;  // (two controls: 204 spilled values, never a default choice -- no such instantiation any more)
-        e->grid_update = e->K;
-        // small problems: one wave per objective, the objectives of the GPU in one workgroup (kh_mini.h);
-        // KH_KERNEL=q2 keeps the workgroup-per-objective kernels, KH_KERNEL=mini is accepted for symmetry
-        e->mini = e->kind == KIND_TILE_Q2 && e->N <= KH_MINI_N && e->K <= KH_MINI_MAXK && force == nullptr;
-    }
-    if (force && strcmp(force, "mini") == 0 && tile_ok && e->L == 1 && e->N <= KH_MINI_N && e->K <= KH_MINI_MAXK) {
-        e->kind = KIND_TILE_Q2;
-        e->grid_update = e->K;
-        e->mini = true;
-    }
-    e->quad = e->mini && e->N <= KH_QUAD_N && e->K <= KH_QUAD_MAXK && !(force && strcmp(force, "mini") == 0);
-    // objectives sharing ONE operator list with a state too large for a register tile: one Taylor
-    // term of all objectives is a dense (N x N)(N x K) product -> fp64 matrix cores (kh_coop.h)
-    {
-        bool shared = true;
-        for (size_t i = 0; i < nops && shared; ++i) shared = fw[i] == fw[i % (size_t)(1 + e->L)];
-        // objectives per workgroup: as few as keeps the grid within the co-resident limit (a round is bound by
-        // the block fetch, which shrinks with the column count; the MFMA work per workgroup does not grow)
-        const int G = (e->N + 15) / 16;
-        int cols = G * ((e->K + 3) / 4) <= max_wgs ? 4 : KH_COOP_COLS;
-        // two objectives per workgroup (half the matrix-core work of a round per workgroup, twice the workgroups)
-        // where every column group still gets an XCD of its own (kh_coop_place): up to 8 groups of at most 32
-        if (e->K > 8 && (e->K + 1) / 2 <= 8 && G <= 32 && G * ((e->K + 1) / 2) <= max_wgs) cols = 2;
-        if (const char *cenv = getenv("KH_COOP_COLS")) {  // testing
-            const int want = atoi(cenv);
-            if ((want == 2 || want == 4 || want == 16) && G * ((e->K + want - 1) / want) <= max_wgs)
-                cols = want;
-        }
-        const int Y = (e->K + cols - 1) / cols;
-        const bool forced = force && strcmp(force, "coop") == 0;
-        const bool fits = csr_fw == nullptr && shared && e->N <= 480 && e->L <= KH_COOP_MAX_L && G * Y <= max_wgs;
-        if (fits && (forced || (e->N > KH_TILE_N && force == nullptr))) {
-            e->kind = KIND_COOP;
-            e->coop_G = G;
-            e->coop_Y = Y;
-            e->coop_cols = cols;
-            e->coop_ks = cols <= 4 ? kh_coop4_slots(e->N) : (e->N + 31) / 32;  // operator-fragment slots per lane
-            e->coop_vbuf_bytes = sizeof(kh_u64) * KH_COOP_RING * (size_t)Y * G * 16 * KH_COOP_COLS * 4;
-            KH_HIP_E(hipMalloc(&e->d_coop_vbuf, e->coop_vbuf_bytes));
-            KH_HIP_E(hipMalloc(&e->d_coop_xcc, sizeof(unsigned int) * (size_t)G * Y));
-            e->coop_xcd = cols <= 4 && Y <= 8 && G <= 32 && !(getenv("KH_COOP_XCD") && atoi(getenv("KH_COOP_XCD")) == 0);
-            e->grid_update = e->K < max_wgs ? e->K : max_wgs;  // (stepwise launches use the generic kernel)
-            // A round (one Taylor term) costs a cross-workgroup exchange here, so fewer, longer
-            // sub-steps pay: theta <= 4 needs ~31 terms per sub-step against 4 x 18 at theta <= 1.
-            // Round-off grows like e^theta (55 eps per step at theta = 4), still far inside the
-            // parity budget (measured: unchanged 3e-15 vs the oracle on the transmon Liouvillians).
-            if (!(pr->theta_max > 0.0)) e->theta_max = 4.0;
-        }
-    }
-    // Per-objective operators with 64 < N <= 128: the generator in registers (kh_tilen.h) instead of the generic kernels'
-    // re-streaming of every operator for every term.  (Objectives sharing one operator list took the cooperative
-    // matrix-core kernels above; KH_KERNEL=tilen forces this family for them too: testing.)
-    bool tilen_ok = false;
-    {
-        const bool forced = force && strcmp(force, "tilen") == 0;
-        if (csr_fw == nullptr && e->N > KH_TILE_N && e->N <= KH_TN_NMAX && e->L >= 1 && e->L <= KH_MAX_L &&
-            ((e->kind == KIND_GENERIC && force == nullptr) || forced)) {
-            tilen_ok = true;
-            if (forced) {
-                e->kind = KIND_GENERIC;  // (undo the cooperative choice)
-                e->grid_update = e->K < max_wgs ? e->K : max_wgs;
-                if (!(pr->theta_max > 0.0)) e->theta_max = 1.0;
-            }
-            std::map<const void *, cplx *> perm_of;
-            for (int dir = 0; dir < 2; ++dir) {
-                const std::vector<const cplx *> &tab = dir == 0 ? fw : bw;
-                std::vector<const cplx *> out(nops, nullptr);
-                for (size_t i = 0; i < nops; ++i) {
-                    if (tab[i] == nullptr) continue;
-                    auto it = perm_of.find(tab[i]);
-                    if (it == perm_of.end()) {
-                        cplx *dst = nullptr;
-                        KH_HIP_E(hipMalloc(&dst, sizeof(cplx) * (KH_TN_NMAX / 4) * KH_TN_THREADS));
-                        e->owned.push_back(dst);
-                        kh_tn_permute<<<KH_TN_NMAX / 4, KH_TN_THREADS>>>(tab[i], dst, e->N);
-                        it = perm_of.emplace(tab[i], dst).first;
-                    }
-                    out[i] = it->second;
-                }
-                const cplx ***slot = dir == 0 ? &e->d_tn_fw : &e->d_tn_bw;
-                KH_HIP_E(hipMalloc((void **)slot, sizeof(cplx *) * nops));
-                KH_HIP_E(hipMemcpy((void *)*slot, out.data(), sizeof(cplx *) * nops, hipMemcpyHostToDevice));
-            }
-            KH_HIP_E(hipGetLastError());
-            e->tn_h1reg = e->L == 1 && e->N <= 96 && !(getenv("KH_TN_H1REG") && atoi(getenv("KH_TN_H1REG")) == 0);
-            for (int k = 0; k < e->K; ++k) e->tn_h1reg = e->tn_h1reg && fw[(size_t)k * 2 + 1] != nullptr;
-            if (e->K <= max_wgs) {
-                e->kind = KIND_TILEN;
-                e->grid_update = e->K;
-            }
-        }
-    }
-    // Five to eight controls, N <= 64: the register-tile kernels with the operators beyond the CU's room streamed
-    // (kh_tile64x.h) instead of the generic kernels.  The plain sweeps take their objectives in turns (any K); the
-    // update sweep needs one resident workgroup per objective, first order and the adjoint-side store (launch_update:
-    // otherwise the generic kernels, which stay this engine's `kind`).  KH_TX=0: off (A/B switch); KH_KERNEL=tilex: testing
-    bool tx_ok = false;
-    {
-        const bool forced = force && strcmp(force, "tilex") == 0;
-        const bool off = getenv("KH_TX") && atoi(getenv("KH_TX")) == 0;
-        if (csr_fw == nullptr && e->N <= KH_TILE_N && e->L >= KH_TX_MIN_L && e->L <= KH_MAX_L && e->kind == KIND_GENERIC &&
-            (force == nullptr || forced) && !off) {
-            tx_ok = true;
-            std::map<const void *, cplx *> perm_of;
-            cplx *zero_tile = nullptr;  // stands in for a control an objective does not have (no branches in the kernels' loads)
-            KH_HIP_E(hipMalloc(&zero_tile, sizeof(cplx) * 8 * KH_TX_THREADS));
-            e->owned.push_back(zero_tile);
-            KH_HIP_E(hipMemset(zero_tile, 0, sizeof(cplx) * 8 * KH_TX_THREADS));
-            for (int dir = 0; dir < 2; ++dir) {
-                const std::vector<const cplx *> &tab = dir == 0 ? fw : bw;
-                std::vector<const cplx *> out(nops, zero_tile);
-                for (size_t i = 0; i < nops; ++i) {
-                    if (tab[i] == nullptr) continue;
-                    auto it = perm_of.find(tab[i]);
-                    if (it == perm_of.end()) {
-                        cplx *dst = nullptr;
-                        KH_HIP_E(hipMalloc(&dst, sizeof(cplx) * 8 * KH_TX_THREADS));
-                        e->owned.push_back(dst);
-                        kh_tx_permute<<<8, KH_TX_THREADS>>>(tab[i], dst, e->N);
-                        it = perm_of.emplace(tab[i], dst).first;
-                    }
-                    out[i] = it->second;
-                }
-                const cplx ***slot = dir == 0 ? &e->d_tx_fw : &e->d_tx_bw;
-                KH_HIP_E(hipMalloc((void **)slot, sizeof(cplx *) * nops));
-                KH_HIP_E(hipMemcpy((void *)*slot, out.data(), sizeof(cplx *) * nops, hipMemcpyHostToDevice));
-            }
-            KH_HIP_E(hipGetLastError());
-            e->tx_update = e->K <= max_wgs;
-        }
-    }
-    // Sparse operators in the padded row form: one 1024-thread workgroup per objective, the matrix in registers
-    // (kh_ell.h).  The update sweep exchanges the sums in-kernel, so all K workgroups must be resident (one per CU);
-    // with more objectives it stays with the generic CSR kernels, the plain sweeps take their objectives in turns.
-    if (ell_ok) {
-        if (e->K <= max_wgs) {
-            e->kind = KIND_ELL;
-            e->grid_update = e->K;
-        }
-        // a term of the series costs a workgroup-wide round whatever it multiplies: fewer, longer sub-steps pay, as
-        // for the cooperative kernels (theta <= 4: round-off ~ e^theta eps per step, far inside the parity budget)
-        if (!(pr->theta_max > 0.0)) {
-            // (the long sub-steps only with the Chebyshev form's coefficients; Taylor's at theta <= 4 as before)
-            const bool cheb = (e->real_spectrum || (e->imag_defect >= 0.0 && e->imag_defect <= 0.05)) &&
-                              !(getenv("KH_NEAR_IMAG") && atoi(getenv("KH_NEAR_IMAG")) == 0);
-            e->theta_max = cheb ? KH_ELL_THETA_CAP : 4.0;
-            // KH_ELL_CAP (scripts/exp_ell_cap.py): another cap for the Chebyshev-form tables only, never beyond the one
-            // they were validated for -- plain Taylor keeps theta <= 4 (its round-off grows like e^theta)
-            if (const char *d = getenv("KH_ELL_CAP"))
-                if (cheb && atof(d) > 0.0) e->theta_max = atof(d) < KH_ELL_THETA_CAP ? atof(d) : KH_ELL_THETA_CAP;
-        }
-    }
-    // The plain sweeps have no cross-objective coupling, so the register-tile kernel serves them for any
-    // number of objectives (workgroups simply run in turns) even when the update sweep needs the generic one.
-    e->kind_store = ell_ok ? KIND_ELL : (tilen_ok ? KIND_TILEN : (tx_ok ? KIND_TILEX : e->kind));
-    if (e->kind == KIND_GENERIC && csr_fw == nullptr && e->N <= KH_TILE_N && e->L >= 1 && e->L <= 4 &&
-        !(force && strcmp(force, "generic") == 0))
-        e->kind_store = KIND_TILE_RPT1;
-    // ... and with one control that kernel is the two-terms-per-phase one (kh_q2_sweep_store takes its objectives in
-    // turns: no co-residency needed), whatever the update sweep has to use: K = 512 on one GPU 7.5 -> 5.8 us per
-    // interval of the backward sweep (two turns of the 256-objective sweep instead of the one-term-per-phase kernel
-    // with two workgroups per CU).  KH_Q2_STORE=0: the update sweep's own family (A/B switch)
-    if ((e->kind_store == KIND_TILE_RPT2 || e->kind_store == KIND_TILE_RPT1) && e->L == 1 && force == nullptr &&
-        !(getenv("KH_Q2_STORE") && atoi(getenv("KH_Q2_STORE")) == 0))
-        e->kind_store = KIND_TILE_Q2;
-    // (not for 16 operator slots per lane x 16 objectives per workgroup -- N > 256 with more objectives than 4 per
-    // workgroup keep co-resident --: the A^2 chain's second fragment does not fit the registers there, launch_coop_store)
-    const bool coop_sq = e->kind == KIND_COOP && e->L == 1 && !(getenv("KH_COOP_NOSQ") && atoi(getenv("KH_COOP_NOSQ"))) &&
-                         !(e->coop_cols == 16 && e->coop_ks > 8);
-    if (e->kind == KIND_TILE_Q2 || e->kind_store == KIND_TILE_Q2 || coop_sq) {
-        // stage P0 = H0 H0, P1 = H0 H1 + H1 H0, P2 = H1 H1 once per distinct operator (pair)
-        const unsigned pgrid = (unsigned)(((size_t)e->N * e->N + 255) / 256 < 16 ? 16 : ((size_t)e->N * e->N + 255) / 256);
-        const size_t bytes = sizeof(cplx) * (size_t)e->N * e->N;
-        for (int dir = 0; dir < 2; ++dir) {
-            const std::vector<const cplx *> &tab = dir == 0 ? fw : bw;
-            std::vector<const cplx *> sq((size_t)e->K * 3, nullptr);
-            std::map<const void *, cplx *> p0_of, p2_of;
-            std::map<std::pair<const void *, const void *>, cplx *> p1_of;
-            for (int k = 0; k < e->K; ++k) {
-                const cplx *H0 = tab[(size_t)k * 2], *H1 = tab[(size_t)k * 2 + 1];
-                auto it0 = p0_of.find(H0);
-                if (it0 == p0_of.end()) {
-                    cplx *dst = nullptr;
-                    KH_HIP_E(hipMalloc(&dst, bytes));
-                    e->owned.push_back(dst);
-                    kh_q2_product<<<pgrid, 256>>>(H0, H0, dst, e->N, 0);
-                    it0 = p0_of.emplace(H0, dst).first;
-                }
-                sq[(size_t)k * 3] = it0->second;
-                if (H1 == nullptr) continue;
-                auto it2 = p2_of.find(H1);
-                if (it2 == p2_of.end()) {
-                    cplx *dst = nullptr;
-                    KH_HIP_E(hipMalloc(&dst, bytes));
-                    e->owned.push_back(dst);
-                    kh_q2_product<<<pgrid, 256>>>(H1, H1, dst, e->N, 0);
-                    it2 = p2_of.emplace(H1, dst).first;
-                }
-                sq[(size_t)k * 3 + 2] = it2->second;
-                auto key = std::make_pair((const void *)H0, (const void *)H1);
-                auto it1 = p1_of.find(key);
-                if (it1 == p1_of.end()) {
-                    cplx *dst = nullptr;
-                    KH_HIP_E(hipMalloc(&dst, bytes));
-                    e->owned.push_back(dst);
-                    kh_q2_product<<<pgrid, 256>>>(H0, H1, dst, e->N, 1);
-                    it1 = p1_of.emplace(key, dst).first;
-                }
-                sq[(size_t)k * 3 + 1] = it1->second;
-            }
-            KH_HIP_E(hipGetLastError());
-            const cplx ***slot = dir == 0 ? &e->d_sq_fw : &e->d_sq_bw;
-            KH_HIP_E(hipMalloc((void **)slot, sizeof(cplx *) * sq.size()));
-            KH_HIP_E(hipMemcpy((void *)*slot, sq.data(), sizeof(cplx *) * sq.size(), hipMemcpyHostToDevice));
-        }
-    }
-    if (e->kind == KIND_COOP) {
-        // fragment-ordered copies of the (shared) operators and, for one control, of P0, P1, P2 (kh_coop.h)
-        const size_t elems = kh_coop_table_elems(e->coop_G, e->coop_ks);  // (row blocks padded apart: kh_coop_table_stride)
-        const size_t frag_elems = (size_t)e->coop_G * KH_COOP_WAVES * e->coop_ks * 64;
-        std::map<const void *, const cplx *> perm_of;
-        auto permuted = [&](const cplx *src, const cplx **out) -> hipError_t {
-            *out = nullptr;
-            if (src == nullptr) return hipSuccess;
-            auto it = perm_of.find(src);
-            if (it == perm_of.end()) {
-                cplx *dst = nullptr;
-                // (+ one zero-slot word per (row block, wave) behind the table: kh_coop_mask_kernel)
-                const hipError_t err = hipMalloc(&dst, sizeof(cplx) * elems + sizeof(unsigned int) * e->coop_G * KH_COOP_WAVES);
-                if (err != hipSuccess) return err;
-                e->owned.push_back(dst);
-                {
-                    const hipError_t merr = hipMemset(dst, 0, sizeof(cplx) * elems);
-                    if (merr != hipSuccess) return merr;
-                }
-                kh_coop_permute_kernel<<<(unsigned)((frag_elems + 255) / 256), 256>>>(src, dst, e->N, e->coop_G, e->coop_ks, e->coop_cols);
-                kh_coop_mask_kernel<<<e->coop_G * KH_COOP_WAVES, 64>>>(dst, (unsigned int *)(dst + elems), e->coop_ks);
-                it = perm_of.emplace(src, dst).first;
-            }
-            *out = it->second;
-            return hipSuccess;
-        };
-        for (int dir = 0; dir < 2; ++dir) {
-            const std::vector<const cplx *> &tab = dir == 0 ? fw : bw;
-            std::vector<const cplx *> fops(1 + e->L, nullptr), sq3(3, nullptr);
-            for (int o = 0; o <= e->L; ++o) KH_HIP_E(permuted(tab[o], &fops[o]));
-            const cplx ***slot = dir == 0 ? &e->d_coop_fops_fw : &e->d_coop_fops_bw;
-            KH_HIP_E(hipMalloc((void **)slot, sizeof(cplx *) * fops.size()));
-            KH_HIP_E(hipMemcpy((void *)*slot, fops.data(), sizeof(cplx *) * fops.size(), hipMemcpyHostToDevice));
-            if (coop_sq) {
-                std::vector<const cplx *> nat(3, nullptr);
-                KH_HIP_E(hipMemcpy(nat.data(), dir == 0 ? e->d_sq_fw : e->d_sq_bw, sizeof(cplx *) * 3, hipMemcpyDeviceToHost));
-                for (int i = 0; i < 3; ++i) KH_HIP_E(permuted(nat[i], &sq3[i]));
-                const cplx ***sslot = dir == 0 ? &e->d_coop_sq_fw : &e->d_coop_sq_bw;
-                KH_HIP_E(hipMalloc((void **)sslot, sizeof(cplx *) * 3));
-                KH_HIP_E(hipMemcpy((void *)*sslot, sq3.data(), sizeof(cplx *) * 3, hipMemcpyHostToDevice));
-            }
-        }
-        KH_HIP_E(hipGetLastError());
-#ifdef KH_WITH_C4W
-        if (coop_sq && e->coop_cols == 2 && e->L == 1 && bw[1] != nullptr && kh_c4_groups(e->N) <= 30 &&
-            getenv("KH_COOP4W") != nullptr && atoi(getenv("KH_COOP4W")) != 0) {
-            // the same five tables in the fragment order of kh_coop4w.h
-            const int NG = kh_c4_groups(e->N);
-            const size_t elems = kh_c4_table_elems(e->coop_G, NG), frag = (size_t)e->coop_G * KH_C4_WAVES * NG * 64;
-            std::map<const void *, const cplx *> perm4;
-            auto permuted4 = [&](const cplx *src, const cplx **out) -> hipError_t {
-                *out = nullptr;
-                if (src == nullptr) return hipSuccess;
-                auto it = perm4.find(src);
-                if (it == perm4.end()) {
-                    cplx *dst = nullptr;
-                    const hipError_t err = hipMalloc(&dst, sizeof(cplx) * elems + sizeof(unsigned int) * e->coop_G * KH_C4_WAVES);
-                    if (err != hipSuccess) return err;
-                    e->owned.push_back(dst);
-                    const hipError_t merr = hipMemset(dst, 0, sizeof(cplx) * elems);
-                    if (merr != hipSuccess) return merr;
-                    kh_c4_permute_kernel<<<(unsigned)((frag + 255) / 256), 256>>>(src, dst, e->N, e->coop_G, NG);
-                    kh_c4_mask_kernel<<<e->coop_G * KH_C4_WAVES, 64>>>(dst, (unsigned int *)(dst + elems), NG);
-                    it = perm4.emplace(src, dst).first;
-                }
-                *out = it->second;
-                return hipSuccess;
-            };
-            for (int dir = 0; dir < 2; ++dir) {
-                const std::vector<const cplx *> &tab = dir == 0 ? fw : bw;
-                std::vector<const cplx *> fops(2, nullptr), sq3(3, nullptr), nat(3, nullptr);
-                for (int o = 0; o < 2; ++o) KH_HIP_E(permuted4(tab[o], &fops[o]));
-                KH_HIP_E(hipMemcpy(nat.data(), dir == 0 ? e->d_sq_fw : e->d_sq_bw, sizeof(cplx *) * 3, hipMemcpyDeviceToHost));
-                for (int i = 0; i < 3; ++i) KH_HIP_E(permuted4(nat[i], &sq3[i]));
-                const cplx ***fslot = dir == 0 ? &e->d_c4_fops_fw : &e->d_c4_fops_bw;
-                const cplx ***sslot = dir == 0 ? &e->d_c4_sq_fw : &e->d_c4_sq_bw;
-                KH_HIP_E(hipMalloc((void **)fslot, sizeof(cplx *) * 2));
-                KH_HIP_E(hipMemcpy((void *)*fslot, fops.data(), sizeof(cplx *) * 2, hipMemcpyHostToDevice));
-                KH_HIP_E(hipMalloc((void **)sslot, sizeof(cplx *) * 3));
-                KH_HIP_E(hipMemcpy((void *)*sslot, sq3.data(), sizeof(cplx *) * 3, hipMemcpyHostToDevice));
-            }
-            KH_HIP_E(hipGetLastError());
-            e->coop4w = true;
-            e->c4_NG = NG;
-        }
-#endif
-        if (coop_sq && bw[1] != nullptr && !(getenv("KH_COOP_NO_ADJ") && atoi(getenv("KH_COOP_NO_ADJ")))) {
-            e->coop_adj = true;
-            e->coop_adj_op = bw[1];
-            KH_HIP_E(hipMalloc(&e->d_coop_adj_nz, (size_t)e->coop_G * e->coop_G));
-            kh_coop_adj_mask_kernel<<<e->coop_G * e->coop_G, 256>>>(bw[1], e->N, e->coop_G, e->d_coop_adj_nz);
-            KH_HIP_E(hipGetLastError());
-        }
-    }
-    {  // (every kernel family but the cooperative one reads the series tables)
-        std::vector<double> tab(KH_MAX_DEGREE + 1), c0(KH_MAX_DEGREE + 1), rows((size_t)(KH_MAX_DEGREE + 1) * KH_Q2_ROWS * 2),
-            ratios((size_t)(KH_MAX_DEGREE + 1) * KH_RATIO_STRIDE);
-        // the cooperative kernels (A^2 chain, one control): a term is a cross-workgroup round, so the Chebyshev form
-        // is used up to theta = 4 and also for generators that are anti-Hermitian only up to a small defect
-        e->coop_series = e->kind == KIND_COOP && coop_sq && e->imag_defect >= 0.0 && e->imag_defect <= 0.05;
-        if (e->coop_series) {
-            kh_build_real_spectrum_rows(e->tol, tab.data(), c0.data(), rows.data(), ratios.data(), 4.0, e->imag_defect);
-        } else if (ell_ok && (e->real_spectrum || (e->imag_defect >= 0.0 && e->imag_defect <= 0.05)) &&
-                   !(getenv("KH_NEAR_IMAG") && atoi(getenv("KH_NEAR_IMAG")) == 0)) {
-            // sparse operators in the padded row form: a term costs a workgroup-wide round, so one long sub-step beats
-            // several short ones: the Chebyshev form up to theta = 6.  Measured on the reference's three-states problem
-            // (scripts/exp_ell_cap.py, theta = 4.4 ... 7.9 per step, 3 iterations x 3 sweeps x 2000 steps): tau within
-            // 6e-14 and the pulses within 7e-15 of the same run with theta <= 1 per sub-step, for caps 4, 5, 6 and 8
-            // alike; KH_ELL_CAP: A/B switch
-            double cap = KH_ELL_THETA_CAP;
-            if (const char *d = getenv("KH_ELL_CAP")) cap = atof(d) > 0.0 && atof(d) < cap ? atof(d) : cap;  // (as theta_max above)
-            kh_build_real_spectrum_rows(e->tol, tab.data(), c0.data(), rows.data(), ratios.data(), cap,
-                                        e->real_spectrum ? 0.0 : e->imag_defect);
-        } else if (e->real_spectrum) {
-            kh_build_real_spectrum_rows(e->tol, tab.data(), c0.data(), rows.data(), ratios.data());
-        } else if (e->imag_defect > 0.0 && e->imag_defect <= 0.05 && !(getenv("KH_NEAR_IMAG") && atoi(getenv("KH_NEAR_IMAG")) == 0)) {
-            // the same form, with the margin for the Hermitian defect, for the other kernel families (weakly damped
-            // Liouvillians, Hamiltonians with a small anti-Hermitian part); KH_NEAR_IMAG=0: Taylor (A/B switch)
-            kh_build_real_spectrum_rows(e->tol, tab.data(), c0.data(), rows.data(), ratios.data(), 2.0, e->imag_defect);
-        } else {
-            kh_build_degree_table(e->tol, tab.data());
-            kh_build_taylor_rows(c0.data(), rows.data(), ratios.data());
-        }
-        KH_HIP_E(hipMalloc(&e->d_ratios, sizeof(double) * ratios.size()));
-        KH_HIP_E(hipMemcpy(e->d_ratios, ratios.data(), sizeof(double) * ratios.size(), hipMemcpyHostToDevice));
-        KH_HIP_E(hipMalloc(&e->d_q2_theta, sizeof(double) * tab.size()));
-        KH_HIP_E(hipMalloc(&e->d_q2_c0, sizeof(double) * c0.size()));
-        KH_HIP_E(hipMalloc(&e->d_q2_rows, sizeof(double) * rows.size()));
-        KH_HIP_E(hipMemcpy(e->d_q2_theta, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice));
-        KH_HIP_E(hipMemcpy(e->d_q2_c0, c0.data(), sizeof(double) * c0.size(), hipMemcpyHostToDevice));
-        KH_HIP_E(hipMemcpy(e->d_q2_rows, rows.data(), sizeof(double) * rows.size(), hipMemcpyHostToDevice));
-    }
-    if (e->kind_store == KIND_TILE_Q2)
-        KH_HIP_E(hipFuncSetAttribute((const void *)kh_q2_sweep_store, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)kh_q2_lds_bytes()));
-    if (e->kind == KIND_TILE_Q2) {
-        KH_HIP_E(hipFuncSetAttribute((const void *)kh_q2_forward_update<false, false>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)kh_q2_lds_bytes()));
-        KH_HIP_E(hipFuncSetAttribute((const void *)kh_q2_forward_update<false, true>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)kh_q2_lds_bytes()));
-        KH_HIP_E(hipFuncSetAttribute((const void *)kh_q2_forward_update<false, true, true>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)kh_q2_lds_bytes()));
-        KH_HIP_E(hipFuncSetAttribute((const void *)kh_q2_forward_update<false, false, true>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)kh_q2_lds_bytes()));
-        KH_HIP_E(hipFuncSetAttribute((const void *)kh_q2_forward_update<true, false, true>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)kh_q2_lds_bytes()));
-        KH_HIP_E(hipFuncSetAttribute((const void *)kh_q2_forward_update<true, false>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)kh_q2_lds_bytes()));
-
-    }
-
-    if (e->kind == KIND_TILE_Q2 && !e->mini && e->K > 1) {
-        // every workgroup of the single-launch update sweep must be resident at once: ask the occupancy of the kernel
-        // as built (registers, LDS) instead of assuming one per CU; if it does not fit, the generic kernels (which
-        // loop over objectives inside at most #CUs workgroups) take over
-        // (every instantiation a sweep of this engine may launch: one GPU / sharded, first / second order, sums on
-        // either side -- their register footprints differ)
-        const void *forms[] = {(const void *)kh_q2_forward_update<false, true, true>, (const void *)kh_q2_forward_update<false, false, true>,
-                               (const void *)kh_q2_forward_update<true, false, true>, (const void *)kh_q2_forward_update<false, true>,
-                               (const void *)kh_q2_forward_update<false, false>,      (const void *)kh_q2_forward_update<true, false>};
-        int rc = KH_OK;
-        for (const void *f : forms)
-            if (rc == KH_OK) rc = check_residency(e, f, KH_Q2_THREADS, kh_q2_lds_bytes(), e->K, "kh_q2_forward_update");
-        if (rc != KH_OK) {
-            e->kind = KIND_GENERIC;  // (the plain sweeps keep the q2 kernel: its workgroups do not wait for each other)
-            e->grid_update = e->K < max_wgs ? e->K : max_wgs;
-        }
-    }
-
-    // ---- ensembles (kh_ens.h): one drift, control operators equal up to a real scale, N <= 64, one control, more
-    // objectives than CUs (from 257 on it beats the two-workgroups-per-CU tile kernels too: 10.7 against 11.1 us per interval at
-    // K = 512).  KH_ENS=0: off;
-    // KH_ENS=1: for any K (testing); KH_ENS_MINK: smallest K that takes it; KH_ENS_NCG: column groups (testing)
-    {
-        const char *ens_env = getenv("KH_ENS");
-        const int ens_mode = ens_env ? atoi(ens_env) : -1;
-        int min_k = 257;  // (one objective per CU: the two-terms-per-phase kernels, 4.8 us per interval against 10.2 here)
-        if (const char *d = getenv("KH_ENS_MINK")) min_k = atoi(d);
-        const bool want = ens_mode == 1 || (ens_mode != 0 && force == nullptr && e->K >= min_k);
-        if (want && csr_fw == nullptr && e->N <= KH_TILE_N && e->L == 1 && fw[1] != nullptr) {
-            int ncg = 0;
-            for (int c = 1; c <= KH_ENS_MAXCG; c *= 2)
-                if ((e->K + 2 * c - 1) / (2 * c) <= max_wgs) {
-                    ncg = c;
-                    break;
-                }
-            if (const char *d = getenv("KH_ENS_NCG")) {
-                const int c = atoi(d);
-                if ((c == 1 || c == 2 || c == 4 || c == 8) && (e->K + 2 * c - 1) / (2 * c) <= max_wgs) ncg = c;
-            }
-            if (ncg > 0) {
-                // reference element: the largest component of objective 0's control operator
-                std::vector<cplx> ref((size_t)e->N * e->N);
-                KH_HIP_E(hipMemcpy(ref.data(), fw[1], sizeof(cplx) * ref.size(), hipMemcpyDeviceToHost));
-                int ref_idx = 0, ref_comp = 0;
-                double best = 0.0;
-                for (size_t i = 0; i < ref.size(); ++i) {
-                    if (fabs(ref[i].x) > best) best = fabs(ref[i].x), ref_idx = (int)i, ref_comp = 0;
-                    if (fabs(ref[i].y) > best) best = fabs(ref[i].y), ref_idx = (int)i, ref_comp = 1;
-                }
-                if (best > 0.0) {
-                    int *d_flags = nullptr, flags[2] = {1, 1};
-                    KH_HIP_E(hipMalloc(&e->d_ens_scale, sizeof(double) * e->K));
-                    KH_HIP_E(hipMalloc(&d_flags, sizeof(flags)));
-                    hipError_t err = hipMemset(d_flags, 0, sizeof(flags));
-                    if (err == hipSuccess) {
-                        kh_ens_detect_kernel<<<e->K, 256>>>(e->d_ops_fw, e->K, e->N, ref_idx, ref_comp, e->d_ens_scale, d_flags);
-                        err = hipGetLastError();  // (the launch's own verdict, not whatever the copy below reports)
-                        if (err == hipSuccess) err = hipMemcpy(flags, d_flags, sizeof(flags), hipMemcpyDeviceToHost);
-                    }
-                    (void)hipFree(d_flags);
-                    KH_HIP_E(err);
-                    if (flags[0] == 0 && flags[1] == 0) {
-                        e->ens = true;
-                        e->ens2 = !(getenv("KH_ENS2") && atoi(getenv("KH_ENS2")) == 0);
-                        e->ens_ncg = ncg;
-                        e->ens_G = (e->K + 2 * ncg - 1) / (2 * ncg);
-                        e->ens_H0 = fw[0];
-                        e->ens_H1 = fw[1];
-                    }
-                }
-            }
-        }
-        if (e->ens) {  // all ens_G workgroups resident at once?  (as the q2 path asks for its instantiations)
-            const void *forms[2] = {nullptr, nullptr};
-            switch (e->ens_ncg) {
-                case 1: forms[0] = (const void *)kh_ens_forward_update<1, false>, forms[1] = (const void *)kh_ens_forward_update<1, true>; break;
-                case 2: forms[0] = (const void *)kh_ens_forward_update<2, false>, forms[1] = (const void *)kh_ens_forward_update<2, true>; break;
-                case 4: forms[0] = (const void *)kh_ens_forward_update<4, false>, forms[1] = (const void *)kh_ens_forward_update<4, true>; break;
-                default: forms[0] = (const void *)kh_ens_forward_update<8, false>, forms[1] = (const void *)kh_ens_forward_update<8, true>; break;
-            }
-            int rc = KH_OK;
-            for (const void *f : forms) {
-                if (rc == KH_OK) rc = ensure_dynamic_lds(e, f, kh_ens_lds_bytes(e->ens_ncg));
-                if (rc == KH_OK) rc = check_residency(e, f, KH_ENS_THREADS, kh_ens_lds_bytes(e->ens_ncg), e->ens_G, "kh_ens_forward_update");
-            }
-            if (rc != KH_OK) e->ens = false;
-        }
-    }
-
-    // ---- workspaces
-    KH_HIP_E(hipMalloc(&e->d_phi, sizeof(cplx) * (size_t)e->K * e->N));
-    const int Lx = e->L > 0 ? e->L : 1;
-    const int slot_wgs = e->kind == KIND_COOP && e->coop_G * e->coop_Y > e->grid_update ? e->coop_G * e->coop_Y
-                                                                                         : e->grid_update;
-    e->slots_bytes = sizeof(kh_u64) * 2 * (size_t)slot_wgs * Lx * 2;
-    KH_HIP_E(hipMalloc(&e->d_slots, e->slots_bytes));
-    KH_HIP_E(hipMalloc(&e->d_abort, 2 * sizeof(unsigned int)));  // [0] abort flag, [1] (KH_TIMING) polling rounds
-    KH_HIP_E(hipMemset(e->d_abort, 0, 2 * sizeof(unsigned int)));
-    KH_HIP_E(hipMalloc(&e->d_wait_ticks, 4 * sizeof(unsigned long long)));
-    KH_HIP_E(hipMemset(e->d_wait_ticks, 0, 4 * sizeof(unsigned long long)));
-    KH_HIP_E(hipMalloc(&e->d_stats, sizeof(double) * 68));
-    KH_HIP_E(hipMemset(e->d_stats, 0, sizeof(double) * 68));
-    KH_HIP_E(hipMalloc(&e->d_wg_partial, sizeof(double) * (size_t)e->grid_update * Lx));
-    KH_HIP_E(hipMalloc(&e->d_step_partial, sizeof(double) * Lx));
-    KH_HIP_E(hipDeviceSynchronize());
-#undef KH_HIP_E
     *out = e;
     return KH_OK;
 }
@@ -1464,29 +1446,125 @@ extern "C" int kh_engine_create_csr(const kh_problem_csr *pc, kh_engine **out) {
 // launches
 // ---------------------------------------------------------------------------
 
-template <int RPT, int LT>
-static int launch_tile_store(kh_engine *e, const KhSweepArgs &p, const double *pulses, const cplx *in,
-                             cplx *store, cplx *out, int direction, hipStream_t st) {
-    constexpr size_t lds = KhTileLds<RPT, LT>::bytes(KhTileLds<RPT, LT>::STORE);  // operator tiles parked in LDS
-    const int rc = ensure_dynamic_lds(e, (const void *)kh_tile_sweep_store<RPT, LT>, lds);
-    if (rc != KH_OK) return rc;
-    launch_plain<kh_tile_sweep_store<RPT, LT>>(dim3(e->K), dim3(512 / RPT), lds, st, p, pulses, in, store, out, direction);
-    return KH_OK;
+// Runtime value -> template parameters: each mapping is written once and called by the plain sweep and the update
+// sweep alike, with std::integral_constant / std::bool_constant arguments (`decltype(x)::value` in the callee).
+template <int V>
+using KhInt = std::integral_constant<int, V>;
+
+template <class F>
+static int with_bool(bool b, F &&f) {
+    return b ? f(std::true_type{}) : f(std::false_type{});
 }
 
-template <int RPT>
-static int dispatch_tile_store(kh_engine *e, const KhSweepArgs &p, const double *pulses, const cplx *in,
-                               cplx *store, cplx *out, int direction, hipStream_t st) {
-    switch (e->L) {
-        case 1: return launch_tile_store<RPT, 1>(e, p, pulses, in, store, out, direction, st);
-        case 2: return launch_tile_store<1, 2>(e, p, pulses, in, store, out, direction, st);
-        case 3: return launch_tile_store<1, 3>(e, p, pulses, in, store, out, direction, st);
-        case 4: return launch_tile_store<1, 4>(e, p, pulses, in, store, out, direction, st);
+// register-tile kernels (kh_tile64.h, kh_tile64s.h): 1..4 controls
+template <class F>
+static int with_tile_L(int L, F &&f) {
+    switch (L) {
+        case 1: return f(KhInt<1>{});
+        case 2: return f(KhInt<2>{});
+        case 3: return f(KhInt<3>{});
+        case 4: return f(KhInt<4>{});
         default: return kh_fail(KH_ERR_UNSUPPORTED, "tile kernels handle 1..4 controls");
     }
 }
 
-static KhExchange exchange_args(const kh_engine *e, bool internal_exchange);
+// ... rows per thread: two (256-thread workgroups) only with one control
+template <class F>
+static int with_tile(bool rpt2, int L, F &&f) {
+    return with_tile_L(L, [&](auto lt) {
+        if constexpr (decltype(lt)::value == 1)
+            return rpt2 ? f(KhInt<2>{}, lt) : f(KhInt<1>{}, lt);
+        else
+            return f(KhInt<1>{}, lt);
+    });
+}
+
+// tile64x kernels (kh_tile64x.h): five to eight controls
+template <class F>
+static int with_tx(int L, F &&f) {
+    switch (L) {
+        case 5: return f(KhInt<5>{});
+        case 6: return f(KhInt<6>{});
+        case 7: return f(KhInt<7>{});
+        default: return f(KhInt<8>{});
+    }
+}
+
+// tilen kernels (kh_tilen.h): elements per lane; the control operator in registers only up to N = 96
+template <class F>
+static int with_tn(int EP, bool h1reg, F &&f) {
+    switch (EP) {
+        case 20: return h1reg ? f(KhInt<20>{}, std::true_type{}) : f(KhInt<20>{}, std::false_type{});
+        case 24: return h1reg ? f(KhInt<24>{}, std::true_type{}) : f(KhInt<24>{}, std::false_type{});
+        case 28: return f(KhInt<28>{}, std::false_type{});
+        default: return f(KhInt<32>{}, std::false_type{});
+    }
+}
+
+// padded-row kernels (kh_ell.h): (threads, rows per lane, row width, streamed form).  One row per lane where the rows'
+// entries fit the register budget of that many waves (512 threads: 256 VGPRs, 768: 168, 1024: 128), else two rows
+// per lane of a 512-thread workgroup; (12: drift + two controls of a Lindbladian -- the reference's notebook 06 has
+// 11.2 entries per row; every padded slot is a gather and four multiply-adds per term); N > 1024: <= 8 entries per
+// row (build_ell_host)
+template <class F>
+static int with_ell(int N, int E, bool stream, F &&f) {
+    using F_ = std::false_type;
+    if (stream) return f(KhInt<512>{}, KhInt<KH_ELLS_RPL>{}, KhInt<4>{}, std::true_type{});
+    if (N <= 512) {
+        if (E <= 8) return f(KhInt<512>{}, KhInt<1>{}, KhInt<8>{}, F_{});
+        if (E <= 12) return f(KhInt<512>{}, KhInt<1>{}, KhInt<12>{}, F_{});
+        if (E <= 16) return f(KhInt<512>{}, KhInt<1>{}, KhInt<16>{}, F_{});
+        if (E <= 24) return f(KhInt<512>{}, KhInt<1>{}, KhInt<24>{}, F_{});
+        return f(KhInt<512>{}, KhInt<1>{}, KhInt<32>{}, F_{});
+    }
+    if (N <= 768 && E <= 16) {
+        if (E <= 8) return f(KhInt<768>{}, KhInt<1>{}, KhInt<8>{}, F_{});
+        if (E <= 12) return f(KhInt<768>{}, KhInt<1>{}, KhInt<12>{}, F_{});
+        return f(KhInt<768>{}, KhInt<1>{}, KhInt<16>{}, F_{});
+    }
+    if (N > 1024) return N <= 1536 ? f(KhInt<512>{}, KhInt<3>{}, KhInt<8>{}, F_{}) : f(KhInt<512>{}, KhInt<4>{}, KhInt<8>{}, F_{});
+    if (E <= 8) return f(KhInt<1024>{}, KhInt<1>{}, KhInt<8>{}, F_{});
+    return E <= 12 ? f(KhInt<512>{}, KhInt<2>{}, KhInt<12>{}, F_{}) : f(KhInt<512>{}, KhInt<2>{}, KhInt<16>{}, F_{});
+}
+
+// cooperative kernels (kh_coop.h): operator-fragment slots per lane, objectives per workgroup
+template <class F>
+static int with_coop(int cols, int ks, F &&f) {
+    auto by_ks = [&](auto c) { return ks <= 8 ? f(KhInt<8>{}, c) : f(KhInt<16>{}, c); };
+    if (cols == 2) return by_ks(KhInt<2>{});
+    if (cols == 4) return by_ks(KhInt<4>{});
+    return by_ks(KhInt<16>{});
+}
+
+// V_lk = H_lk^+ chi_k for the whole co-state store [L][K][nt][N] (kh_generic.h, kh_gen_adjoint_side), in front of an
+// update sweep that reads its sums from there
+static int gen_adjoint_side(kh_engine *e, const cplx *chi_store, int L, hipStream_t st) {
+    const dim3 grid((unsigned)(e->K * L), (unsigned)((e->nt + KH_GEN_ADJ_POINTS - 1) / KH_GEN_ADJ_POINTS));
+    kh_gen_adjoint_side<<<grid, KH_GEN_ADJ_THREADS, 0, st>>>(e->d_ops_bw, chi_store, e->d_gen_adj, e->K, e->N, L, e->nt);
+    KH_HIP(hipGetLastError());
+    return KH_OK;
+}
+
+static KhExchange exchange_args(const kh_engine *e, bool internal_exchange) {
+    KhExchange ex;
+    ex.slots = e->d_slots;
+    ex.abort_flag = e->d_abort;
+    ex.G = (e->plan.kind == KIND_COOP && internal_exchange) ? e->plan.coop_G * e->plan.coop_Y : e->plan.grid_update;
+    ex.timeout_ticks = e->sw.timeout_ticks;
+    // across GPUs the ranks are separate processes: a host-side hiccup of one of them (garbage collection, page
+    // faults) must not look like a lost peer and demote the whole run to the per-interval path
+    if (e->p2p_ready && internal_exchange && !e->sw.timeout_set && ex.timeout_ticks < 1000000000LL)
+        ex.timeout_ticks = 1000000000LL;  // 10 s
+    ex.peer_windows = e->d_p2p_peers;
+    ex.my_window = e->p2p_window;
+    ex.world = (e->p2p_ready && internal_exchange) ? e->p2p_world : 1;
+    ex.rank = e->p2p_rank;
+    ex.epoch_base = e->p2p_epoch_base;
+    ex.first_poll_delay = e->sw.poll_delay;
+    ex.fail_at = (ex.world > 1 && e->p2p_rank == e->sw.p2p_fail_rank && e->p2p_sweeps + 1 == e->sw.p2p_fail_sweep) ? e->sw.p2p_fail_at : -1;
+    ex.wait_ticks = ex.world > 1 ? e->d_wait_ticks : nullptr;
+    return ex;
+}
 
 static KhCoopArgs coop_args(const kh_engine *e, bool backward) {
     KhCoopArgs c;
@@ -1494,283 +1572,174 @@ static KhCoopArgs coop_args(const kh_engine *e, bool backward) {
     c.sq = backward ? e->d_coop_sq_bw : e->d_coop_sq_fw;  // (NULL unless staged: one control)
     c.vbuf = e->d_coop_vbuf;
     c.epoch_base = 0;  // the buffer is cleared before every launch
-    c.G = e->coop_G;
-    c.Y = e->coop_Y;
-    c.ks = e->coop_ks;
-    c.cols = e->coop_cols;
-    c.first_poll_delay = e->coop_poll_delay;
-    c.xcd_rows = e->coop_xcd ? e->coop_G : 0;
+    c.G = e->plan.coop_G;
+    c.Y = e->plan.coop_Y;
+    c.ks = e->plan.coop_ks;
+    c.cols = e->plan.coop_cols;
+    c.first_poll_delay = e->sw.coop_poll_delay;
+    c.xcd_rows = e->plan.coop_xcd ? e->plan.coop_G : 0;
     c.xcc = e->d_coop_xcc;
     c.local = 0;
     c.ring_mask = KH_COOP_RING - 1;
     for (int i = 0; i < 5; ++i) c.tab[i] = nullptr;  // (resolved in the kernel)
-    c.ser_theta = e->coop_series ? e->d_q2_theta : nullptr;
-    c.ser_c0 = e->coop_series ? e->d_q2_c0 : nullptr;
-    c.ser_rows = e->coop_series ? e->d_q2_rows : nullptr;
+    c.ser_theta = e->plan.coop_series ? e->d_q2_theta : nullptr;
+    c.ser_c0 = e->plan.coop_series ? e->d_q2_c0 : nullptr;
+    c.ser_rows = e->plan.coop_series ? e->d_q2_rows : nullptr;
     return c;
 }
 
-// The cooperative kernels are launched with one column group per XCD where that is possible: a one-dimensional
-// grid of 8 G blocks of which only G Y do anything (kh_coop_place).  The cooperative-launch validation counts all
-// 8 G of them, so on a device (or partition, or CU mask) with fewer resident workgroups than that the launch is
-// refused although the G Y real ones would fit: the placement is then given up for good (two-dimensional (G, Y)
-// grid, memory-side exchange) and the launch repeated.
-template <class Launch>
-static int launch_coop_placed(kh_engine *e, Launch &&launch) {
-    int rc = launch(e->coop_xcd ? dim3(8 * e->coop_G) : dim3(e->coop_G, e->coop_Y));
-    if (rc == KH_ERR_UNSUPPORTED && e->coop_xcd) {
-        e->coop_xcd = false;
-        rc = launch(dim3(e->coop_G, e->coop_Y));
-    }
-    return rc;
-}
-
-#ifdef KH_WITH_C4W
-static KhCoopArgs c4_args(const kh_engine *e, bool backward) {
-    KhCoopArgs c = coop_args(e, backward);
-    c.fops = backward ? e->d_c4_fops_bw : e->d_c4_fops_fw;
-    c.sq = backward ? e->d_c4_sq_bw : e->d_c4_sq_fw;
-    c.ks = e->c4_NG;
-    return c;
-}
-
-template <int MAXG>
-static int launch_c4_store(kh_engine *e, const KhSweepArgs &p, const double *pulses, const cplx *in, cplx *store,
-                           cplx *out, int direction, hipStream_t st) {
-    const size_t lds = kh_c4_lds_bytes(MAXG);
-    const int rc = ensure_dynamic_lds(e, (const void *)kh_c4_sweep_store<MAXG>, lds);
-    if (rc != KH_OK) return rc;
+// A cooperative kernel: its LDS limit raised (for the largest fragment count of the instantiation), the exchange
+// buffers cleared, and launched with one column group per XCD where that is possible: a one-dimensional grid of 8 G
+// blocks of which only G Y do anything (kh_coop_place).  The cooperative-launch validation counts all 8 G of them, so
+// on a device (or partition, or CU mask) with fewer resident workgroups than that the launch is refused although the
+// G Y real ones would fit: the placement is then given up for good (two-dimensional (G, Y) grid, memory-side
+// exchange) and the launch repeated.
+template <auto Kernel, int COLS, class... Rest>
+static int launch_coop(kh_engine *e, hipStream_t st, bool backward, const KhSweepArgs &p, Rest... rest) {
+    KhPlan &pl = e->plan;
+    KH_TRY(ensure_dynamic_lds(e, (const void *)Kernel, kh_coop_lds_bytes(COLS <= 4 ? 16 : 15, COLS)));
     KH_HIP(hipMemsetAsync(e->d_coop_vbuf, 0, e->coop_vbuf_bytes, st));
-    KH_HIP(hipMemsetAsync(e->d_coop_xcc, 0, sizeof(unsigned int) * (size_t)e->coop_G * e->coop_Y, st));
-    return launch_coop_placed(e, [&](dim3 grid) {
-        return launch_persistent<kh_c4_sweep_store<MAXG>>(e, grid, dim3(KH_C4_THREADS), lds, st, p, c4_args(e, direction < 0),
-                                 exchange_args(e, true), pulses, in, store, out, direction);
-    });
+    KH_HIP(hipMemsetAsync(e->d_coop_xcc, 0, sizeof(unsigned int) * (size_t)pl.coop_G * pl.coop_Y, st));
+    auto launch = [&](dim3 grid) {  // (coop_args: the placement as it stands)
+        return launch_persistent<Kernel>(e, grid, dim3(KH_COOP_THREADS), kh_coop_lds_bytes(pl.coop_ks, COLS), st, p,
+                                         coop_args(e, backward), rest...);
+    };
+    int rc2 = launch(pl.coop_xcd ? dim3(8 * pl.coop_G) : dim3(pl.coop_G, pl.coop_Y));
+    if (rc2 == KH_ERR_UNSUPPORTED && pl.coop_xcd) {
+        pl.coop_xcd = false;
+        rc2 = launch(dim3(pl.coop_G, pl.coop_Y));
+    }
+    return rc2;
 }
 
-#endif
-
+// (16 operator slots per lane x 16 objectives per workgroup: the A^2 chain's second resident fragment does not fit the
+// register file -- 245 .. 343 spilled values --, the engine does not stage the A^2 tables for that shape)
 template <int MAXKS, int COLS>
 static int launch_coop_store(kh_engine *e, const KhSweepArgs &p, const double *pulses, const cplx *in, cplx *store,
                              cplx *out, int direction, hipStream_t st) {
-    // (16 operator slots per lane x 16 objectives per workgroup: the A^2 chain's second resident fragment does not fit
-    // the register file -- 245 .. 343 spilled values --, the engine does not stage the A^2 tables for that shape)
-    constexpr bool SQ_FORMS = !(MAXKS == 16 && COLS == 16);
-    const bool sq = SQ_FORMS && (direction < 0 ? e->d_coop_sq_bw : e->d_coop_sq_fw) != nullptr;
-    int rc = KH_OK;
-    if constexpr (SQ_FORMS)
-        rc = ensure_dynamic_lds(e, (const void *)kh_coop_sweep_store<MAXKS, COLS, true>, kh_coop_lds_bytes(COLS <= 4 ? 16 : 15, COLS));
-    if (rc == KH_OK)
-        rc = ensure_dynamic_lds(e, (const void *)kh_coop_sweep_store<MAXKS, COLS, false>, kh_coop_lds_bytes(COLS <= 4 ? 16 : 15, COLS));
-    if (rc != KH_OK) return rc;
-    KH_HIP(hipMemsetAsync(e->d_coop_vbuf, 0, e->coop_vbuf_bytes, st));
-    KH_HIP(hipMemsetAsync(e->d_coop_xcc, 0, sizeof(unsigned int) * (size_t)e->coop_G * e->coop_Y, st));
-    return launch_coop_placed(e, [&](dim3 grid) {
-        if constexpr (SQ_FORMS)
-            if (sq)
-                return launch_persistent<kh_coop_sweep_store<MAXKS, COLS, true>>(e, grid, dim3(KH_COOP_THREADS), kh_coop_lds_bytes(e->coop_ks, COLS), st, p,
-                                         coop_args(e, direction < 0), exchange_args(e, true), pulses, in, store, out, direction);
-        return launch_persistent<kh_coop_sweep_store<MAXKS, COLS, false>>(e, grid, dim3(KH_COOP_THREADS), kh_coop_lds_bytes(e->coop_ks, COLS), st, p,
-                                 coop_args(e, direction < 0), exchange_args(e, true), pulses, in, store, out, direction);
-    });
+    const bool bw = direction < 0;
+    const KhExchange ex = exchange_args(e, true);
+    if constexpr (!(MAXKS == 16 && COLS == 16))
+        if ((bw ? e->d_coop_sq_bw : e->d_coop_sq_fw) != nullptr)
+            return launch_coop<kh_coop_sweep_store<MAXKS, COLS, true>, COLS>(e, st, bw, p, ex, pulses, in, store, out, direction);
+    return launch_coop<kh_coop_sweep_store<MAXKS, COLS, false>, COLS>(e, st, bw, p, ex, pulses, in, store, out, direction);
 }
 
 template <int MAXKS, int COLS>
 static int launch_coop_update(kh_engine *e, const KhSweepArgs &p, const KhUpdateArgs &u_in, const KhExchange &ex,
                               hipStream_t st) {
     KhUpdateArgs u = u_in;
-    if (e->coop_adj && u.sigma == nullptr && e->L == 1 && e->d_coop_sq_fw != nullptr && e->d_coop_adj == nullptr) {
+    const bool so = u.sigma != nullptr;
+    if (e->plan.coop_adj && !so && e->L == 1 && e->d_coop_sq_fw != nullptr && e->d_coop_adj == nullptr) {
         // V = H_1^+ X needs a second buffer of the co-state store's size; it is an optimisation (one round per interval
         // less): without the memory the sweep takes the sums by one more round, as it did before the form existed
         const size_t bytes = sizeof(cplx) * (size_t)e->K * e->nt * e->N;
         if (hipMalloc(&e->d_coop_adj, bytes) != hipSuccess) {
             (void)hipGetLastError();
             e->d_coop_adj = nullptr;
-            e->coop_adj = false;
+            e->plan.coop_adj = false;
         }
     }
-    constexpr bool SQ_FORMS = !(MAXKS == 16 && COLS == 16);  // (see launch_coop_store)
-    const bool sq = SQ_FORMS && e->d_coop_sq_fw != nullptr;
-    const bool adj = e->coop_adj && u.sigma == nullptr && e->L == 1 && sq;
-    const void *func = u.sigma != nullptr ? (const void *)kh_coop_forward_update<MAXKS, COLS, true, false, false>
-                                          : (const void *)kh_coop_forward_update<MAXKS, COLS, false, false, false>;
-    if constexpr (SQ_FORMS) {
-        if (u.sigma != nullptr && sq)
-            func = (const void *)kh_coop_forward_update<MAXKS, COLS, true, false, true>;
-        else if (adj)
-            func = ex.world == 1 && e->coop_single ? (const void *)kh_coop_forward_update<MAXKS, COLS, false, true, true, false>
-                                                   : (const void *)kh_coop_forward_update<MAXKS, COLS, false, true, true>;
-        else if (u.sigma == nullptr && sq)
-            func = (const void *)kh_coop_forward_update<MAXKS, COLS, false, false, true>;
-    }
-    const int rc = ensure_dynamic_lds(e, func, kh_coop_lds_bytes(COLS <= 4 ? 16 : 15, COLS));
-    if (rc != KH_OK) return rc;
-    if (adj) {
-        // V = H_1^+ X over the whole co-state store, block-sparse on the matrix cores (kh_coop.h)
-        const long long M = (long long)e->K * e->nt;
-        const unsigned blocks = (unsigned)((M + 63) / 64);
-        kh_coop_adjoint_side<<<blocks, KH_COOP_ADJ_THREADS, 0, st>>>(e->coop_adj_op, e->d_coop_adj_nz, u.chi_store, e->d_coop_adj,
-                                                                     e->N, e->coop_G, M);
-        KH_HIP(hipGetLastError());
-        u.adj_store = e->d_coop_adj;
-    }
-    KH_HIP(hipMemsetAsync(e->d_coop_vbuf, 0, e->coop_vbuf_bytes, st));
-    KH_HIP(hipMemsetAsync(e->d_coop_xcc, 0, sizeof(unsigned int) * (size_t)e->coop_G * e->coop_Y, st));
-    return launch_coop_placed(e, [&](dim3 grid) {
-        const size_t lds = kh_coop_lds_bytes(e->coop_ks, COLS);
-        const KhCoopArgs ca = coop_args(e, false);
-        if constexpr (SQ_FORMS) {
-            if (adj && ex.world == 1 && e->coop_single)
-                return launch_persistent<kh_coop_forward_update<MAXKS, COLS, false, true, true, false>>(e, grid, dim3(KH_COOP_THREADS), lds, st, p, ca, u, ex);
-            if (adj) return launch_persistent<kh_coop_forward_update<MAXKS, COLS, false, true, true>>(e, grid, dim3(KH_COOP_THREADS), lds, st, p, ca, u, ex);
-            if (u.sigma != nullptr && sq)
-                return launch_persistent<kh_coop_forward_update<MAXKS, COLS, true, false, true>>(e, grid, dim3(KH_COOP_THREADS), lds, st, p, ca, u, ex);
-            if (u.sigma == nullptr && sq)
-                return launch_persistent<kh_coop_forward_update<MAXKS, COLS, false, false, true>>(e, grid, dim3(KH_COOP_THREADS), lds, st, p, ca, u, ex);
+    if constexpr (!(MAXKS == 16 && COLS == 16)) {  // (see launch_coop_store)
+        if (e->d_coop_sq_fw != nullptr && e->plan.coop_adj && !so && e->L == 1) {
+            // V = H_1^+ X over the whole co-state store, block-sparse on the matrix cores (kh_coop.h)
+            const long long M = (long long)e->K * e->nt;
+            kh_coop_adjoint_side<<<(unsigned)((M + 63) / 64), KH_COOP_ADJ_THREADS, 0, st>>>(e->coop_adj_op, e->d_coop_adj_nz, u.chi_store,
+                                                                                          e->d_coop_adj, e->N, e->plan.coop_G, M);
+            KH_HIP(hipGetLastError());
+            u.adj_store = e->d_coop_adj;
+            if (ex.world == 1 && e->sw.coop_single)
+                return launch_coop<kh_coop_forward_update<MAXKS, COLS, false, true, true, false>, COLS>(e, st, false, p, u, ex);
+            return launch_coop<kh_coop_forward_update<MAXKS, COLS, false, true, true>, COLS>(e, st, false, p, u, ex);
         }
-        if (u.sigma != nullptr)
-            return launch_persistent<kh_coop_forward_update<MAXKS, COLS, true, false, false>>(e, grid, dim3(KH_COOP_THREADS), lds, st, p, ca, u, ex);
-        return launch_persistent<kh_coop_forward_update<MAXKS, COLS, false, false, false>>(e, grid, dim3(KH_COOP_THREADS), lds, st, p, ca, u, ex);
-    });
+        if (e->d_coop_sq_fw != nullptr)
+            return so ? launch_coop<kh_coop_forward_update<MAXKS, COLS, true, false, true>, COLS>(e, st, false, p, u, ex)
+                      : launch_coop<kh_coop_forward_update<MAXKS, COLS, false, false, true>, COLS>(e, st, false, p, u, ex);
+    }
+    return so ? launch_coop<kh_coop_forward_update<MAXKS, COLS, true, false, false>, COLS>(e, st, false, p, u, ex)
+              : launch_coop<kh_coop_forward_update<MAXKS, COLS, false, false, false>, COLS>(e, st, false, p, u, ex);
 }
 
+// the plain sweeps (forward with storage, backward): one family per engine, kind_store
 static int sweep_store(kh_engine *e, bool backward, const double *pulses, const cplx *in, cplx *store, cplx *out,
                        hipStream_t st) {
+    const KhPlan &pl = e->plan;
     const KhSweepArgs p = sweep_args(e, backward);
     const int direction = backward ? -1 : +1;
+    const cplx *const *sq = backward ? e->d_sq_bw : e->d_sq_fw;
+    const int grid_cus = e->K < e->num_cus ? e->K : e->num_cus;  // (objectives in turns: at most one workgroup per CU)
     KH_HIP(hipMemsetAsync(e->d_stats, 0, sizeof(double) * 4, st));
     int rc = KH_OK;
-    if (e->kind_store == KIND_TILE_Q2 && e->quad) {
-        launch_plain<kh_quad_sweep_store>(dim3(1), dim3(64), 0, st, p, backward ? e->d_sq_bw : e->d_sq_fw, pulses, in, store, out, direction);
-    } else if (e->kind_store == KIND_TILE_Q2 && e->mini) {
-        launch_plain<kh_mini_sweep_store>(dim3(e->K), dim3(64), 0, st, p, backward ? e->d_sq_bw : e->d_sq_fw, pulses, in, store, out, direction);
-#ifdef KH_WITH_Q4
-    } else if (e->kind_store == KIND_TILE_Q2 && e->use_q4) {
-        rc = ensure_dynamic_lds(e, (const void *)kh_q4_sweep_store, kh_q4_lds_bytes());
-        if (rc == KH_OK)
-            launch_plain<kh_q4_sweep_store>(dim3(e->K), dim3(KH_Q4_THREADS), kh_q4_lds_bytes(), st, 
-                p, backward ? e->d_sq_bw : e->d_sq_fw, pulses, in, store, out, direction);
-#endif
-    } else if (e->kind_store == KIND_TILEN) {
-        const cplx *const *tabs = backward ? e->d_tn_bw : e->d_tn_fw;
-        const int grid = e->K < e->num_cus ? e->K : e->num_cus;
-        const size_t lds = kh_tn_lds_bytes();
-#define KH_TN_STORE(EP, HR) launch_plain<kh_tn_sweep_store<EP, HR>>(dim3(grid), dim3(KH_TN_THREADS), lds, st, p, tabs, pulses, in, store, out, direction)
-        if (e->N <= 80) {
-            if (e->tn_h1reg) KH_TN_STORE(20, true); else KH_TN_STORE(20, false);
-        } else if (e->N <= 96) {
-            if (e->tn_h1reg) KH_TN_STORE(24, true); else KH_TN_STORE(24, false);
-        } else if (e->N <= 112) {
-            KH_TN_STORE(28, false);
-        } else {
-            KH_TN_STORE(32, false);
+    switch (pl.kind_store) {
+        case KIND_TILE_Q2:
+            if (pl.quad)
+                launch_plain<kh_quad_sweep_store>(dim3(1), dim3(64), 0, st, p, sq, pulses, in, store, out, direction);
+            else if (pl.mini)
+                launch_plain<kh_mini_sweep_store>(dim3(e->K), dim3(64), 0, st, p, sq, pulses, in, store, out, direction);
+            else
+                launch_plain<kh_q2_sweep_store>(dim3(e->K), dim3(KH_Q2_THREADS), kh_q2_lds_bytes(), st, p, sq, pulses, in, store, out, direction);
+            break;
+        case KIND_TILEN: {
+            const cplx *const *tabs = backward ? e->d_tn_bw : e->d_tn_fw;
+            rc = with_tn(pl.tn_EP, pl.tn_h1reg, [&](auto ep, auto hr) {
+                launch_plain<kh_tn_sweep_store<decltype(ep)::value, decltype(hr)::value>>(dim3(grid_cus), dim3(KH_TN_THREADS), kh_tn_lds_bytes(),
+                                                                                          st, p, tabs, pulses, in, store, out, direction);
+                return KH_OK;
+            });
+            break;
         }
-#undef KH_TN_STORE
-    } else if (e->kind_store == KIND_TILEX) {
-        const int grid = e->K < e->num_cus ? e->K : e->num_cus;
-        const cplx *const *tabs = backward ? e->d_tx_bw : e->d_tx_fw;
-#define KH_TX_STORE(LT)                                                                                                    \
-    do {                                                                                                                   \
-        rc = ensure_dynamic_lds(e, (const void *)kh_tx_sweep_store<LT>, kh_tx_lds_bytes());                                \
-        if (rc == KH_OK)                                                                                                   \
-            launch_plain<kh_tx_sweep_store<LT>>(dim3(grid), dim3(KH_TX_THREADS), kh_tx_lds_bytes(), st, p, tabs, pulses, in, \
-                                                store, out, direction);                                                    \
-    } while (0)
-        switch (e->L) {
-            case 5: KH_TX_STORE(5); break;
-            case 6: KH_TX_STORE(6); break;
-            case 7: KH_TX_STORE(7); break;
-            default: KH_TX_STORE(8); break;
+        case KIND_TILEX: {
+            const cplx *const *tabs = backward ? e->d_tx_bw : e->d_tx_fw;
+            rc = with_tx(e->L, [&](auto lt) {
+                return launch_plain_lds<kh_tx_sweep_store<decltype(lt)::value>>(e, dim3(grid_cus), dim3(KH_TX_THREADS), kh_tx_lds_bytes(), st,
+                                                                                p, tabs, pulses, in, store, out, direction);
+            });
+            break;
         }
-#undef KH_TX_STORE
-    } else if (e->kind_store == KIND_ELL) {
-        const KhEll *ells = backward ? e->d_ell_bw : e->d_ell_fw;
-        const int grid = e->ell_stream ? (e->K < e->num_cus ? e->K : e->num_cus) : (e->K < 4 * e->num_cus ? e->K : 4 * e->num_cus);
-        const size_t lds = kh_ell_lds_bytes(e->ell_stream);
-        // (two vector buffers of KH_ELL_NMAX elements: more than the 64 KiB a kernel gets without asking)
-#define KH_ELL_STORE(T, R, EM)                                                                                        \
-    do {                                                                                                              \
-        rc = ensure_dynamic_lds(e, (const void *)kh_ell_sweep_store<T, R, EM>, lds);                                  \
-        if (rc == KH_OK)                                                                                              \
-            launch_plain<kh_ell_sweep_store<T, R, EM>>(dim3(grid), dim3(T), lds, st, p, ells, e->d_ell_off, e->d_ell_vals, \
-                                                       pulses, in, store, out, direction, (cplx *)nullptr, 0LL);     \
-    } while (0)
-        // one row per lane where the rows' entries fit the register budget of that many waves (512 threads: 256 VGPRs,
-        // 768: 168, 1024: 128), else two rows per lane of a 512-thread workgroup
-        if (e->ell_stream) {
-            rc = ensure_dynamic_lds(e, (const void *)kh_ell_sweep_store<512, KH_ELLS_RPL, 4, true>, lds);
-            if (rc == KH_OK)
-                launch_plain<kh_ell_sweep_store<512, KH_ELLS_RPL, 4, true>>(dim3(grid), dim3(512), lds, st, p, ells, e->d_ell_off,
-                                                                             e->d_ell_vals, pulses, in, store, out, direction,
-                                                                             e->d_ell_scratch, e->ell_scratch_stride);
-        } else if (e->N <= 512) {
-            if (e->ell_E <= 8) KH_ELL_STORE(512, 1, 8);
-            else if (e->ell_E <= 12) KH_ELL_STORE(512, 1, 12);
-            else if (e->ell_E <= 16) KH_ELL_STORE(512, 1, 16);
-            else if (e->ell_E <= 24) KH_ELL_STORE(512, 1, 24);
-            else KH_ELL_STORE(512, 1, 32);
-        } else if (e->N <= 768 && e->ell_E <= 16) {
-            // (12: drift + two controls of a Lindbladian -- the reference's notebook 06 has 11.2 entries per row; every
-            // padded slot is a gather and four multiply-adds per term)
-            if (e->ell_E <= 8) KH_ELL_STORE(768, 1, 8);
-            else if (e->ell_E <= 12) KH_ELL_STORE(768, 1, 12);
-            else KH_ELL_STORE(768, 1, 16);
-        } else if (e->N > 1024) {  // (<= 8 entries per row: build_ell_host)
-            if (e->N <= 1536) KH_ELL_STORE(512, 3, 8);
-            else KH_ELL_STORE(512, 4, 8);
-        } else if (e->ell_E <= 8) {
-            KH_ELL_STORE(1024, 1, 8);
-        } else {
-            if (e->ell_E <= 12) KH_ELL_STORE(512, 2, 12);
-            else KH_ELL_STORE(512, 2, 16);
+        case KIND_ELL: {
+            const KhEll *ells = backward ? e->d_ell_bw : e->d_ell_fw;
+            const int grid = pl.ell_stream ? grid_cus : (e->K < 4 * e->num_cus ? e->K : 4 * e->num_cus);
+            // (two vector buffers of KH_ELL_NMAX elements: more than the 64 KiB a kernel gets without asking)
+            const size_t lds = kh_ell_lds_bytes(pl.ell_stream);
+            rc = with_ell(e->N, pl.ell_E, pl.ell_stream, [&](auto t, auto r, auto em, auto stm) {
+                constexpr int T = decltype(t)::value;
+                return launch_plain_lds<kh_ell_sweep_store<T, decltype(r)::value, decltype(em)::value, decltype(stm)::value>>(
+                    e, dim3(grid), dim3(T), lds, st, p, ells, e->d_ell_off, e->d_ell_vals, pulses, in, store, out, direction,
+                    e->d_ell_scratch, e->ell_scratch_stride);
+            });
+            break;
         }
-#undef KH_ELL_STORE
-    } else if (e->kind_store == KIND_TILE_Q2) {
-        launch_plain<kh_q2_sweep_store>(dim3(e->K), dim3(KH_Q2_THREADS), kh_q2_lds_bytes(), st, 
-            p, backward ? e->d_sq_bw : e->d_sq_fw, pulses, in, store, out, direction);
-    } else if (e->kind_store == KIND_TILE_RPT2) {
-        rc = dispatch_tile_store<2>(e, p, pulses, in, store, out, direction, st);
-    } else if (e->kind_store == KIND_TILE_RPT1) {
-        rc = dispatch_tile_store<1>(e, p, pulses, in, store, out, direction, st);
-#ifdef KH_WITH_C4W
-    } else if (e->kind_store == KIND_COOP && e->coop4w) {
-        rc = e->c4_NG <= 8    ? launch_c4_store<8>(e, p, pulses, in, store, out, direction, st)
-             : e->c4_NG <= 16 ? launch_c4_store<16>(e, p, pulses, in, store, out, direction, st)
-             : e->c4_NG <= 26 ? launch_c4_store<26>(e, p, pulses, in, store, out, direction, st)
-                              : launch_c4_store<30>(e, p, pulses, in, store, out, direction, st);
-        if (rc == KH_ERR_UNSUPPORTED) {
-            e->kind_store = KIND_GENERIC;
-            return sweep_store(e, backward, pulses, in, store, out, st);
+        case KIND_TILE_RPT2:
+        case KIND_TILE_RPT1:
+            rc = with_tile(pl.kind_store == KIND_TILE_RPT2, e->L, [&](auto rpt, auto lt) {
+                constexpr int RPT = decltype(rpt)::value, LT = decltype(lt)::value;
+                constexpr size_t lds = KhTileLds<RPT, LT>::bytes(KhTileLds<RPT, LT>::STORE);  // operator tiles parked in LDS
+                return launch_plain_lds<kh_tile_sweep_store<RPT, LT>>(e, dim3(e->K), dim3(512 / RPT), lds, st, p, pulses, in, store, out, direction);
+            });
+            break;
+        case KIND_COOP:
+            rc = with_coop(pl.coop_cols, pl.coop_ks, [&](auto ks, auto cols) {
+                return launch_coop_store<decltype(ks)::value, decltype(cols)::value>(e, p, pulses, in, store, out, direction, st);
+            });
+            if (rc == KH_ERR_UNSUPPORTED) {
+                // not even the G x Y grid can be resident at once (fewer CUs than expected): the plain sweeps need no
+                // cross-workgroup exchange at all, so the per-objective generic kernel takes them over from here on
+                e->plan.kind_store = KIND_GENERIC;
+                return sweep_store(e, backward, pulses, in, store, out, st);
+            }
+            break;
+        default: {
+            if (!e->gen_fits) return kh_fail(KH_ERR_UNSUPPORTED, "N=%d: the generic kernels' vectors do not fit LDS", e->N);
+            // (the workgroups loop over the objectives: no more of them than the device runs at once -- each may own an
+            // N x N scratch generator)
+            const int grid = e->K < 2 * e->num_cus ? e->K : 2 * e->num_cus;
+            ensure_gen_scratch(e, grid);
+            KhSweepArgs pg = p;
+            pg.gen_scratch = e->d_gen_scratch;
+            pg.gen_scratch_wgs = e->gen_scratch_wgs;
+            rc = launch_plain_lds<kh_gen_sweep_store>(e, dim3(grid), dim3(KH_GEN_THREADS), kh_gen_lds_bytes(e->N, e->d_csr_fw == nullptr), st, pg,
+                                                      pulses, in, store, out, direction);
         }
-#endif
-    } else if (e->kind_store == KIND_COOP) {
-        if (e->coop_cols == 2)
-            rc = e->coop_ks <= 8 ? launch_coop_store<8, 2>(e, p, pulses, in, store, out, direction, st)
-                                 : launch_coop_store<16, 2>(e, p, pulses, in, store, out, direction, st);
-        else if (e->coop_cols == 4)
-            rc = e->coop_ks <= 8 ? launch_coop_store<8, 4>(e, p, pulses, in, store, out, direction, st)
-                                 : launch_coop_store<16, 4>(e, p, pulses, in, store, out, direction, st);
-        else
-            rc = e->coop_ks <= 8 ? launch_coop_store<8, 16>(e, p, pulses, in, store, out, direction, st)
-                                 : launch_coop_store<16, 16>(e, p, pulses, in, store, out, direction, st);
-        if (rc == KH_ERR_UNSUPPORTED) {
-            // not even the G x Y grid can be resident at once (fewer CUs than expected): the plain sweeps need no
-            // cross-workgroup exchange at all, so the per-objective generic kernel takes them over from here on
-            e->kind_store = KIND_GENERIC;
-            return sweep_store(e, backward, pulses, in, store, out, st);
-        }
-    } else {
-        if (!e->gen_fits) return kh_fail(KH_ERR_UNSUPPORTED, "N=%d: the generic kernels' vectors do not fit LDS", e->N);
-        const size_t lds = kh_gen_lds_bytes(e->N, e->d_csr_fw == nullptr);
-        rc = ensure_dynamic_lds(e, (const void *)kh_gen_sweep_store, lds);
-        // (the workgroups loop over the objectives: no more of them than the device runs at once -- each may own an
-        // N x N scratch generator)
-        const int grid = e->K < 2 * e->num_cus ? e->K : 2 * e->num_cus;
-        ensure_gen_scratch(e, grid);
-        KhSweepArgs pg = p;
-        pg.gen_scratch = e->d_gen_scratch;
-        pg.gen_scratch_wgs = e->gen_scratch_wgs;
-        if (rc == KH_OK) launch_plain<kh_gen_sweep_store>(dim3(grid), dim3(KH_GEN_THREADS), lds, st, pg, pulses, in, store, out, direction);
     }
     if (rc != KH_OK) return rc;
     KH_HIP(hipGetLastError());
@@ -1795,59 +1764,220 @@ extern "C" int kh_backward_store(kh_engine *e, const kh_cdouble *chi_T_dev, cons
                        (hipStream_t)stream);
 }
 
+// ---- the update sweep: one route per call (update_route), one small launcher per family
+
+enum KhRoute { ROUTE_ENS, ROUTE_ENS2, ROUTE_STREAM, ROUTE_QUAD, ROUTE_MINI, ROUTE_Q2, ROUTE_COOP, ROUTE_TILEN, ROUTE_ELL, ROUTE_TILE, ROUTE_TILEX, ROUTE_GENERIC };
+
+// Which launcher runs an update call.  whole: the single launch over all intervals; stepwise: one interval per launch
+// (host- or device-indexed: the same route); so: second order; reduced_G: kh_set_update_workgroups; world: ranks of the
+// in-kernel exchange; have_sq: the A^2 tables are staged; adj_store(): the adjoint-side store can be had (ensure_gen_adj,
+// asked only where a family would read it -- its allocation happens at the first such call).
+template <class AdjStore>
+static KhRoute update_route(const KhPlan &p, int K, bool stepwise, bool whole, bool so, int reduced_G, int world,
+                            bool have_sq, AdjStore &&adj_store) {
+    if (p.ens && whole) {
+        // first order, four objectives per workgroup (512 < K <= 1024): the A^2 chain with the update sums on the adjoint
+        // side (kh_ens2_forward_update; KH_ENS2=0: the term-by-term kernel, A/B switch and what second order and the other
+        // column-group counts run -- with one column group it measured 2 % slower, with 4 and 8 its operands do not fit)
+        int G = 0;
+        const int ncg = p.ens_cols(K, reduced_G, &G);
+        return !so && ncg == 2 && p.ens2 && have_sq && adj_store() ? ROUTE_ENS2 : ROUTE_ENS;
+    }
+    if ((p.stream || (reduced_G > 0 && reduced_G < p.grid_update && world == 1)) && whole) return ROUTE_STREAM;
+    if (p.kind == KIND_TILE_Q2 && p.quad && whole) return ROUTE_QUAD;
+    if (p.kind == KIND_TILE_Q2 && p.mini && whole) return ROUTE_MINI;
+    if (!stepwise) {
+        switch (p.kind) {
+            case KIND_TILE_Q2: return ROUTE_Q2;
+            case KIND_COOP: return ROUTE_COOP;
+            case KIND_TILEN: return ROUTE_TILEN;
+            case KIND_ELL: return ROUTE_ELL;
+            default: break;
+        }
+    }
+    // One launch per interval (sharded sweep): every launch re-stages its operator tiles, so the q2 kernels (5 tiles,
+    // 320 KiB per objective) lose to the plain tile kernel (2 tiles) there -- measured 39 vs ~20 us per interval.
+    if (p.kind == KIND_TILE_RPT1 || p.kind == KIND_TILE_RPT2 || p.kind == KIND_TILE_Q2) return ROUTE_TILE;
+    if (p.tx_update && whole && !so && reduced_G == 0 && p.grid_update >= K && adj_store()) return ROUTE_TILEX;
+    return ROUTE_GENERIC;
+}
+
+// the ensemble kernels (ens2: the A^2 chain with the sums on the adjoint side)
+static int update_ens(kh_engine *e, const KhSweepArgs &p, const KhUpdateArgs &u, const KhExchange &ex, hipStream_t st, bool ens2) {
+    KhExchange exe = ex;
+    const int ncg = e->plan.ens_cols(e->K, e->reduced_G, &exe.G);
+    KhEnsArgs en;
+    en.H0 = e->ens_H0;
+    en.H1 = e->ens_H1;
+    en.scale = e->d_ens_scale;
+    e->last_update_grid = exe.G;
+    if (ens2) {
+        KH_TRY(gen_adjoint_side(e, u.chi_store, 1, st));
+        KhUpdateArgs ua = u;
+        ua.adj_store = e->d_gen_adj;
+        // (the interval's first pass sits between the sums' stores and the first poll: no head start on top -- 16.08 -> 15.75 us)
+        if (!e->sw.poll_delay_set) exe.first_poll_delay = 0;
+        return launch_persistent_lds<kh_ens2_forward_update<2>>(e, dim3(exe.G), dim3(KH_ENS_THREADS), kh_ens2_lds_bytes(ncg), st, p, en,
+                                                                e->d_sq_fw, ua, exe);
+    }
+    return with_ens(ncg, [&](auto c) {
+        return with_bool(u.sigma != nullptr, [&](auto s) {
+            constexpr int NCG = decltype(c)::value;
+            return launch_persistent<kh_ens_forward_update<NCG, decltype(s)::value>>(e, dim3(exe.G), dim3(KH_ENS_THREADS),
+                                                                                     kh_ens_lds_bytes(NCG), st, p, en, u, exe);
+        });
+    });
+}
+
+// more objectives than co-resident workgroups -- or (kh_set_update_workgroups) fewer workgroups than the register-tile
+// family of this engine would use: G workgroups walk through K / G objectives each (kh_tile64s.h)
+static int update_stream(kh_engine *e, const KhSweepArgs &p, const KhUpdateArgs &u, const KhExchange &ex, hipStream_t st) {
+    int G = e->plan.stream ? e->plan.stream_G : e->plan.grid_update;
+    if (e->reduced_G > 0 && e->reduced_G < G) G = e->reduced_G;
+    KhExchange exs = ex;
+    exs.G = G;
+    exs.world = 1;
+    e->last_update_grid = G;
+    return with_tile_L(e->L, [&](auto lt) {
+        return with_bool(u.sigma != nullptr, [&](auto so) {
+            return with_bool(e->N == KH_TILE_N, [&](auto n64) {
+                return launch_persistent<kh_stream_forward_update<decltype(lt)::value, decltype(so)::value, decltype(n64)::value>>(
+                    e, dim3(G), dim3(512), 0, st, p, u, exs);
+            });
+        });
+    });
+}
+
+static int update_mini(kh_engine *e, const KhSweepArgs &p, const KhUpdateArgs &u, const KhExchange &ex, hipStream_t st, bool quad) {
+    return with_bool(u.sigma != nullptr, [&](auto so) {
+        constexpr bool SO = decltype(so)::value;
+        if (quad)
+            launch_plain<kh_quad_forward_update<SO>>(dim3(1), dim3(64), 0, st, p, e->d_sq_fw, u, ex);
+        else
+            launch_plain<kh_mini_forward_update<SO>>(dim3(1), dim3(64 * e->K), 0, st, p, e->d_sq_fw, u, ex);
+        return KH_OK;
+    });
+}
+
+static int update_q2(kh_engine *e, const KhSweepArgs &p, const KhUpdateArgs &u, const KhExchange &ex, hipStream_t st) {
+    const dim3 g(e->K), b(KH_Q2_THREADS);
+    const size_t lds = kh_q2_lds_bytes();
+    // (KH_Q2_SINGLE=0: the instantiations with the cross-GPU stage on one GPU too -- A/B switch)
+    const bool single = ex.world == 1 && e->sw.q2_single;
+    if (u.sigma != nullptr)
+        return single ? launch_persistent<kh_q2_forward_update<true, false, true>>(e, g, b, lds, st, p, e->d_sq_fw, u, ex)
+                      : launch_persistent<kh_q2_forward_update<true, false>>(e, g, b, lds, st, p, e->d_sq_fw, u, ex);
+    if (u.adj_sign != 0.0) {
+        KhExchange exa = ex;
+        exa.first_poll_delay = e->sw.adj_poll_delay;
+        // (the default form on one GPU: an instantiation without the cross-GPU stage)
+        return single ? launch_persistent<kh_q2_forward_update<false, true, true>>(e, g, b, lds, st, p, e->d_sq_fw, u, exa)
+                      : launch_persistent<kh_q2_forward_update<false, true>>(e, g, b, lds, st, p, e->d_sq_fw, u, exa);
+    }
+    return single ? launch_persistent<kh_q2_forward_update<false, false, true>>(e, g, b, lds, st, p, e->d_sq_fw, u, ex)
+                  : launch_persistent<kh_q2_forward_update<false, false>>(e, g, b, lds, st, p, e->d_sq_fw, u, ex);
+}
+
+static int update_tilen(kh_engine *e, const KhSweepArgs &p, const KhUpdateArgs &u, const KhExchange &ex, hipStream_t st) {
+    const bool so = u.sigma != nullptr;
+    // first order with the control operators NOT in registers (several controls, or N > 96): the update sums on the
+    // adjoint side, H_lk^+ chi_k for the whole store in front of the sweep (kh_generic.h, kh_gen_adjoint_side) instead
+    // of L streamed control products per interval (N = 100, L = 6: 60 of the update sweep's 106 us per interval)
+    KhUpdateArgs ut = u;
+    if (!so && !e->plan.tn_h1reg && ensure_gen_adj(e)) {
+        KH_TRY(gen_adjoint_side(e, u.chi_store, e->L, st));
+        ut.adj_store = e->d_gen_adj;
+    }
+    // (several waves poll side by side: a later first poll, as for the tile64x kernels -- N = 100, L = 6: 68.8 -> 64.9 us per
+    // interval, N = 81, L = 4: 38.2 -> 35.5; KH_POLL_DELAY overrides)
+    KhExchange ext = ex;
+    if (!e->sw.poll_delay_set && e->L >= 2) ext.first_poll_delay = e->L == 2 ? 32 : 64;
+    return with_tn(e->plan.tn_EP, e->plan.tn_h1reg, [&](auto ep, auto hr) {
+        return with_bool(so, [&](auto s) {
+            return launch_persistent<kh_tn_forward_update<decltype(ep)::value, decltype(s)::value, decltype(hr)::value>>(
+                e, dim3(e->K), dim3(KH_TN_THREADS), kh_tn_lds_bytes(), st, p, (const cplx *const *)e->d_tn_fw, ut, ext);
+        });
+    });
+}
+
+static int update_ell(kh_engine *e, const KhSweepArgs &p, const KhUpdateArgs &u, const KhExchange &ex, hipStream_t st) {
+    const size_t lds = kh_ell_lds_bytes(e->plan.ell_stream);
+    return with_ell(e->N, e->plan.ell_E, e->plan.ell_stream, [&](auto t, auto r, auto em, auto stm) {
+        return with_bool(u.sigma != nullptr, [&](auto so) {
+            constexpr int T = decltype(t)::value;
+            return launch_persistent_lds<kh_ell_forward_update<T, decltype(r)::value, decltype(em)::value, decltype(so)::value, decltype(stm)::value>>(
+                e, dim3(e->K), dim3(T), lds, st, p, (const KhEll *)e->d_ell_fw, (const int *)e->d_ell_off, (const cplx *)e->d_ell_vals, u, ex,
+                e->d_ell_scratch, e->ell_scratch_stride);
+        });
+    });
+}
+
 template <int RPT, int LT>
 static int launch_tile_update(kh_engine *e, const KhSweepArgs &p, const KhUpdateArgs &u, const KhExchange &ex,
                               hipStream_t st) {
     constexpr size_t lds = KhTileLds<RPT, LT>::bytes(KhTileLds<RPT, LT>::UPDATE);
-    const void *func = u.sigma != nullptr ? (const void *)kh_tile_forward_update<RPT, LT, true>
-                                          : (const void *)kh_tile_forward_update<RPT, LT, false>;
-    const int rc = ensure_dynamic_lds(e, func, lds);
-    if (rc != KH_OK) return rc;
-    if (!u.internal_exchange) {  // one launch per interval (sharded sweep): nothing waits inside the kernel
-        if (u.sigma != nullptr)
-            launch_plain<kh_tile_forward_update<RPT, LT, true>>(dim3(e->K), dim3(512 / RPT), lds, st, p, u, ex);
-        else
-            launch_plain<kh_tile_forward_update<RPT, LT, false>>(dim3(e->K), dim3(512 / RPT), lds, st, p, u, ex);
-        return KH_OK;
-    }
-    KhExchange exl = ex;
-    // several controls: L waves gather side by side (kh_tile64.h) and a failed polling round costs L times the loads,
-    // so the stores get a longer head start -- measured best on config-5 shapes: 24 / 28 / 32 x 64 cycles for L = 2 / 3 / 4
-    // (update sweep 7.47 / - / 9.86 us per interval against 7.92 / - / 11.21 with 16)
-    if (LT >= 2 && !e->poll_delay_set) exl.first_poll_delay = 24 + 4 * (LT - 2);
-    if (exl.world == 1 && exl.G > 1 && e->tile_single) {
-        const void *fs = u.sigma != nullptr ? (const void *)kh_tile_forward_update<RPT, LT, true, true>
-                                            : (const void *)kh_tile_forward_update<RPT, LT, false, true>;
-        const int rcs = ensure_dynamic_lds(e, fs, lds);
-        if (rcs != KH_OK) return rcs;
-        if (u.sigma != nullptr)
-            return launch_persistent<kh_tile_forward_update<RPT, LT, true, true>>(e, dim3(e->K), dim3(512 / RPT), lds, st, p, u, exl);
-        return launch_persistent<kh_tile_forward_update<RPT, LT, false, true>>(e, dim3(e->K), dim3(512 / RPT), lds, st, p, u, exl);
-    }
-    if (u.sigma != nullptr)
-        return launch_persistent<kh_tile_forward_update<RPT, LT, true>>(e, dim3(e->K), dim3(512 / RPT), lds, st, p, u, exl);
-    return launch_persistent<kh_tile_forward_update<RPT, LT, false>>(e, dim3(e->K), dim3(512 / RPT), lds, st, p, u, exl);
+    const dim3 g(e->K), b(512 / RPT);
+    return with_bool(u.sigma != nullptr, [&](auto so) {
+        constexpr bool SO = decltype(so)::value;
+        if (!u.internal_exchange)  // one launch per interval (sharded sweep): nothing waits inside the kernel
+            return launch_plain_lds<kh_tile_forward_update<RPT, LT, SO>>(e, g, b, lds, st, p, u, ex);
+        KhExchange exl = ex;
+        // several controls: L waves gather side by side (kh_tile64.h) and a failed polling round costs L times the loads,
+        // so the stores get a longer head start -- measured best on config-5 shapes: 24 / 28 / 32 x 64 cycles for L = 2 / 3 / 4
+        // (update sweep 7.47 / - / 9.86 us per interval against 7.92 / - / 11.21 with 16)
+        if (LT >= 2 && !e->sw.poll_delay_set) exl.first_poll_delay = 24 + 4 * (LT - 2);
+        if (exl.world == 1 && exl.G > 1 && e->sw.tile_single)
+            return launch_persistent_lds<kh_tile_forward_update<RPT, LT, SO, true>>(e, g, b, lds, st, p, u, exl);
+        return launch_persistent_lds<kh_tile_forward_update<RPT, LT, SO>>(e, g, b, lds, st, p, u, exl);
+    });
 }
 
-static KhExchange exchange_args(const kh_engine *e, bool internal_exchange) {
-    KhExchange ex;
-    ex.slots = e->d_slots;
-    ex.abort_flag = e->d_abort;
-    ex.G = (e->kind == KIND_COOP && internal_exchange) ? e->coop_G * e->coop_Y : e->grid_update;
-    ex.timeout_ticks = e->timeout_ticks;
-    // across GPUs the ranks are separate processes: a host-side hiccup of one of them (garbage collection, page
-    // faults) must not look like a lost peer and demote the whole run to the per-interval path
-    if (e->p2p_ready && internal_exchange && !e->timeout_set && ex.timeout_ticks < 1000000000LL)
-        ex.timeout_ticks = 1000000000LL;  // 10 s
-    ex.peer_windows = e->d_p2p_peers;
-    ex.my_window = e->p2p_window;
-    ex.world = (e->p2p_ready && internal_exchange) ? e->p2p_world : 1;
-    ex.rank = e->p2p_rank;
-    ex.epoch_base = e->p2p_epoch_base;
-    ex.first_poll_delay = e->poll_delay;
-    ex.fail_at = (ex.world > 1 && e->p2p_rank == e->p2p_fail_rank && e->p2p_sweeps + 1 == e->p2p_fail_sweep) ? e->p2p_fail_at : -1;
-    ex.wait_ticks = ex.world > 1 ? e->d_wait_ticks : nullptr;
-    return ex;
+static int update_generic(kh_engine *e, const KhSweepArgs &p, const KhUpdateArgs &u, const KhExchange &ex, hipStream_t st) {
+    if (!e->gen_fits)
+        return kh_fail(KH_ERR_UNSUPPORTED, "N=%d: this form of the update sweep needs the generic kernels, whose vectors do not fit LDS", e->N);
+    const size_t lds = kh_gen_lds_bytes(e->N, e->d_csr_fw == nullptr);
+    int rc = ensure_dynamic_lds(e, (const void *)kh_gen_forward_update, lds);
+    ensure_gen_scratch(e, e->plan.grid_update);
+    if (rc != KH_OK) return rc;
+    KhSweepArgs pg = p;
+    pg.gen_scratch = e->d_gen_scratch;
+    pg.gen_scratch_wgs = e->gen_scratch_wgs;
+    // first order, dense operators: V_lk = H_lk^+ chi_k for the whole store in front of the sweep -- at the sweep's first
+    // launch (the single launch, or kh_update_begin's); the launches of a stepwise sweep that follow reuse it
+    KhUpdateArgs ug = u;
+    const bool first_launch = u.internal_exchange || (u.n_dev == nullptr && u.n_begin == 0 && u.n_end == 0);
+    if (first_launch) {
+        e->gen_adj_ready = false;
+        if (u.sigma == nullptr && e->d_csr_fw == nullptr && ensure_gen_adj(e)) {
+            KH_TRY(gen_adjoint_side(e, u.chi_store, e->L, st));
+            e->gen_adj_ready = true;
+        }
+    }
+    if (e->gen_adj_ready && u.sigma == nullptr) ug.adj_store = e->d_gen_adj;
+    const dim3 g(e->plan.grid_update), b(KH_GEN_THREADS);
+    if (!ug.internal_exchange) {
+        launch_plain<kh_gen_forward_update>(g, b, lds, st, pg, ug, ex);
+        return KH_OK;
+    }
+    return launch_persistent<kh_gen_forward_update>(e, g, b, lds, st, pg, ug, ex);
+}
+
+// five to eight controls, N <= 64, one resident workgroup per objective, first order: the register-tile form with
+// streamed operators (kh_tile64x.h); V_lk = H_lk^+ chi_k for the whole store in front of the sweep
+static int update_tilex(kh_engine *e, const KhSweepArgs &p, const KhUpdateArgs &u, const KhExchange &ex, hipStream_t st) {
+    KH_TRY(gen_adjoint_side(e, u.chi_store, e->L, st));
+    KhUpdateArgs ux = u;
+    ux.adj_store = e->d_gen_adj;
+    KhExchange exx = ex;
+    exx.G = e->K;
+    // (five to eight waves poll side by side: their first poll later than the register-tile kernels' -- measured best at
+    // K = 256, N = 64: 32 / 44 / 64 / 64 for L = 5 / 6 / 7 / 8, profiles/r06/ab_tile64x.txt; KH_POLL_DELAY overrides)
+    if (!e->sw.poll_delay_set) exx.first_poll_delay = e->L <= 5 ? 32 : e->L == 6 ? 44 : 64;
+    e->last_update_grid = e->K;
+    return with_tx(e->L, [&](auto lt) {
+        return launch_persistent_lds<kh_tx_forward_update<decltype(lt)::value>>(e, dim3(e->K), dim3(KH_TX_THREADS), kh_tx_lds_bytes(), st, p,
+                                                                                (const cplx *const *)e->d_tx_fw, ux, exx);
+    });
 }
 
 static int launch_update(kh_engine *e, const KhUpdateArgs &u, hipStream_t st) {
@@ -1855,245 +1985,32 @@ static int launch_update(kh_engine *e, const KhUpdateArgs &u, hipStream_t st) {
     const KhExchange ex = exchange_args(e, u.internal_exchange != 0);
     if (u.internal_exchange) KH_HIP(hipMemsetAsync(e->d_slots, 0, e->slots_bytes, st));
     if (u.internal_exchange && ex.world > 1) KH_HIP(hipMemsetAsync(e->d_wait_ticks, 0, 2 * sizeof(unsigned long long), st));
-    // One launch per interval (sharded sweep): every launch re-stages its operator
-    // tiles, so the q2 kernels (5 tiles, 320 KiB per objective) lose to the
-    // plain tile kernel (2 tiles) there -- measured 39 vs ~20 us per interval.
     const bool stepwise = !u.internal_exchange;
-    int rc = KH_OK;
     const bool whole = !stepwise && u.n_begin == 0 && u.n_end == e->nt - 1;
     e->last_update_grid = 0;
-    if (e->ens && whole) {
-        int ncg = e->ens_ncg, G = e->ens_G;
-        if (e->reduced_G > 0)  // fewer, wider workgroups (kh_set_update_workgroups)
-            while (G > e->reduced_G && ncg < KH_ENS_MAXCG) ncg *= 2, G = (e->K + 2 * ncg - 1) / (2 * ncg);
-        KhExchange exe = ex;
-        exe.G = G;
-        KhEnsArgs en;
-        en.H0 = e->ens_H0;
-        en.H1 = e->ens_H1;
-        en.scale = e->d_ens_scale;
-        const dim3 g(G), b(KH_ENS_THREADS);
-        e->last_update_grid = G;
-        const size_t lds = kh_ens_lds_bytes(ncg);
-        const bool so = u.sigma != nullptr;
-        // first order, four objectives per workgroup (512 < K <= 1024): the A^2 chain with the update sums on the adjoint
-        // side (kh_ens2_forward_update; KH_ENS2=0: the term-by-term kernel, A/B switch and what second order and the other
-        // column-group counts run -- with one column group it measured 2 % slower, with 4 and 8 its operands do not fit)
-        if (!so && ncg == 2 && e->ens2 && e->d_sq_fw != nullptr && ensure_gen_adj(e)) {
-            const dim3 agrid((unsigned)e->K, (unsigned)((e->nt + KH_GEN_ADJ_POINTS - 1) / KH_GEN_ADJ_POINTS));
-            kh_gen_adjoint_side<<<agrid, KH_GEN_ADJ_THREADS, 0, st>>>(e->d_ops_bw, u.chi_store, e->d_gen_adj, e->K, e->N, 1, e->nt);
-            KH_HIP(hipGetLastError());
-            KhUpdateArgs ua = u;
-            ua.adj_store = e->d_gen_adj;
-            const size_t lds2 = kh_ens2_lds_bytes(ncg);
-            rc = ensure_dynamic_lds(e, (const void *)kh_ens2_forward_update<2>, lds2);
-            // (the interval's first pass sits between the sums' stores and the first poll: no head start on top -- 16.08 -> 15.75 us)
-            KhExchange exe2 = exe;
-            if (!e->poll_delay_set) exe2.first_poll_delay = 0;
-            if (rc == KH_OK) rc = launch_persistent<kh_ens2_forward_update<2>>(e, g, b, lds2, st, p, en, e->d_sq_fw, ua, exe2);
-        } else
-#define KH_ENS_UPDATE(NCG)                                                                          \
-    (so ? launch_persistent<kh_ens_forward_update<NCG, true>>(e, g, b, lds, st, p, en, u, exe)      \
-        : launch_persistent<kh_ens_forward_update<NCG, false>>(e, g, b, lds, st, p, en, u, exe))
-        switch (ncg) {
-            case 1: rc = KH_ENS_UPDATE(1); break;
-            case 2: rc = KH_ENS_UPDATE(2); break;
-            case 4: rc = KH_ENS_UPDATE(4); break;
-            default: rc = KH_ENS_UPDATE(8); break;
-        }
-#undef KH_ENS_UPDATE
-    } else if ((e->stream || (e->reduced_G > 0 && e->reduced_G < e->grid_update && ex.world == 1)) && whole) {
-        // more objectives than co-resident workgroups -- or (kh_set_update_workgroups) fewer workgroups than the
-        // register-tile family of this engine would use: G workgroups walk through K / G objectives each
-        int G = e->stream ? e->stream_G : e->grid_update;
-        if (e->reduced_G > 0 && e->reduced_G < G) G = e->reduced_G;
-        KhExchange exs = ex;
-        exs.G = G;
-        exs.world = 1;
-        const dim3 g(G), b(512);
-        e->last_update_grid = G;
-        const bool so = u.sigma != nullptr;
-#define KH_STREAM_UPDATE_N(LT, N64)                                                                                \
-    (so ? launch_persistent<kh_stream_forward_update<LT, true, N64>>(e, g, b, 0, st, p, u, exs)                   \
-        : launch_persistent<kh_stream_forward_update<LT, false, N64>>(e, g, b, 0, st, p, u, exs))
-#define KH_STREAM_UPDATE(LT) (e->N == KH_TILE_N ? KH_STREAM_UPDATE_N(LT, true) : KH_STREAM_UPDATE_N(LT, false))
-        switch (e->L) {
-            case 1: rc = KH_STREAM_UPDATE(1); break;
-            case 2: rc = KH_STREAM_UPDATE(2); break;
-            case 3: rc = KH_STREAM_UPDATE(3); break;
-            case 4: rc = KH_STREAM_UPDATE(4); break;
-            default: return kh_fail(KH_ERR_UNSUPPORTED, "tile kernels handle 1..4 controls");
-        }
-#undef KH_STREAM_UPDATE
-#undef KH_STREAM_UPDATE_N
-    } else if (e->kind == KIND_TILE_Q2 && e->quad && !stepwise && u.n_begin == 0 && u.n_end == e->nt - 1) {
-        if (u.sigma != nullptr)
-            launch_plain<kh_quad_forward_update<true>>(dim3(1), dim3(64), 0, st, p, e->d_sq_fw, u, ex);
-        else
-            launch_plain<kh_quad_forward_update<false>>(dim3(1), dim3(64), 0, st, p, e->d_sq_fw, u, ex);
-    } else if (e->kind == KIND_TILE_Q2 && e->mini && !stepwise && u.n_begin == 0 && u.n_end == e->nt - 1) {
-        if (u.sigma != nullptr)
-            launch_plain<kh_mini_forward_update<true>>(dim3(1), dim3(64 * e->K), 0, st, p, e->d_sq_fw, u, ex);
-        else
-            launch_plain<kh_mini_forward_update<false>>(dim3(1), dim3(64 * e->K), 0, st, p, e->d_sq_fw, u, ex);
-    } else if (e->kind == KIND_TILE_Q2 && !stepwise) {
-        const dim3 g(e->K), b(KH_Q2_THREADS);
-        // (KH_Q2_SINGLE=0: the instantiations with the cross-GPU stage on one GPU too -- A/B switch)
-        const bool single = ex.world == 1 && e->q2_single;
-        if (u.sigma != nullptr && single)
-            rc = launch_persistent<kh_q2_forward_update<true, false, true>>(e, g, b, kh_q2_lds_bytes(), st, p, e->d_sq_fw, u, ex);
-        else if (u.sigma != nullptr)
-            rc = launch_persistent<kh_q2_forward_update<true, false>>(e, g, b, kh_q2_lds_bytes(), st, p, e->d_sq_fw, u, ex);
-        else if (u.adj_sign != 0.0) {
-            KhExchange exa = ex;
-            exa.first_poll_delay = e->adj_poll_delay;
-            if (single)  // (the default form on one GPU: an instantiation without the cross-GPU stage)
-                rc = launch_persistent<kh_q2_forward_update<false, true, true>>(e, g, b, kh_q2_lds_bytes(), st, p, e->d_sq_fw, u, exa);
-            else
-                rc = launch_persistent<kh_q2_forward_update<false, true>>(e, g, b, kh_q2_lds_bytes(), st, p, e->d_sq_fw, u, exa);
-        } else if (single)
-            rc = launch_persistent<kh_q2_forward_update<false, false, true>>(e, g, b, kh_q2_lds_bytes(), st, p, e->d_sq_fw, u, ex);
-        else
-            rc = launch_persistent<kh_q2_forward_update<false, false>>(e, g, b, kh_q2_lds_bytes(), st, p, e->d_sq_fw, u, ex);
-    } else if (e->kind == KIND_COOP && !stepwise) {
-        if (e->coop_cols == 2)
-            rc = e->coop_ks <= 8 ? launch_coop_update<8, 2>(e, p, u, ex, st) : launch_coop_update<16, 2>(e, p, u, ex, st);
-        else if (e->coop_cols == 4)
-            rc = e->coop_ks <= 8 ? launch_coop_update<8, 4>(e, p, u, ex, st) : launch_coop_update<16, 4>(e, p, u, ex, st);
-        else
-            rc = e->coop_ks <= 8 ? launch_coop_update<8, 16>(e, p, u, ex, st) : launch_coop_update<16, 16>(e, p, u, ex, st);
-    } else if (e->kind == KIND_TILEN && !stepwise) {
-        const dim3 g(e->K), b(KH_TN_THREADS);
-        const size_t lds = kh_tn_lds_bytes();
-        const bool so = u.sigma != nullptr;
-        // first order with the control operators NOT in registers (several controls, or N > 96): the update sums on the
-        // adjoint side, H_lk^+ chi_k for the whole store in front of the sweep (kh_generic.h, kh_gen_adjoint_side) instead
-        // of L streamed control products per interval (N = 100, L = 6: 60 of the update sweep's 106 us per interval)
-        KhUpdateArgs ut = u;
-        if (!so && !e->tn_h1reg && ensure_gen_adj(e)) {
-            const dim3 agrid((unsigned)(e->K * e->L), (unsigned)((e->nt + KH_GEN_ADJ_POINTS - 1) / KH_GEN_ADJ_POINTS));
-            kh_gen_adjoint_side<<<agrid, KH_GEN_ADJ_THREADS, 0, st>>>(e->d_ops_bw, u.chi_store, e->d_gen_adj, e->K, e->N, e->L, e->nt);
-            KH_HIP(hipGetLastError());
-            ut.adj_store = e->d_gen_adj;
-        }
-        const KhUpdateArgs &u = ut;
-        // (several waves poll side by side: a later first poll, as for the tile64x kernels -- N = 100, L = 6: 68.8 -> 64.9 us per
-        // interval, N = 81, L = 4: 38.2 -> 35.5; KH_POLL_DELAY overrides)
-        KhExchange ext = ex;
-        if (!e->poll_delay_set && e->L >= 2) ext.first_poll_delay = e->L == 2 ? 32 : 64;
-        const KhExchange &ex = ext;
-#define KH_TN_UPDATE(EP, HR)                                                                                                  \
-    (so ? launch_persistent<kh_tn_forward_update<EP, true, HR>>(e, g, b, lds, st, p, (const cplx *const *)e->d_tn_fw, u, ex) \
-        : launch_persistent<kh_tn_forward_update<EP, false, HR>>(e, g, b, lds, st, p, (const cplx *const *)e->d_tn_fw, u, ex))
-        if (e->N <= 80)
-            rc = e->tn_h1reg ? KH_TN_UPDATE(20, true) : KH_TN_UPDATE(20, false);
-        else if (e->N <= 96)
-            rc = e->tn_h1reg ? KH_TN_UPDATE(24, true) : KH_TN_UPDATE(24, false);
-        else
-            rc = e->N <= 112 ? KH_TN_UPDATE(28, false) : KH_TN_UPDATE(32, false);
-#undef KH_TN_UPDATE
-    } else if (e->kind == KIND_ELL && !stepwise) {
-        const dim3 g(e->K);
-        const size_t lds = kh_ell_lds_bytes(e->ell_stream);
-        const bool so = u.sigma != nullptr;
-#define KH_ELL_UPDATE_SO(T, R, EM, SO)                                                                                            \
-    (ensure_dynamic_lds(e, (const void *)kh_ell_forward_update<T, R, EM, SO>, lds) != KH_OK                                        \
-         ? KH_ERR_HIP                                                                                                              \
-         : launch_persistent<kh_ell_forward_update<T, R, EM, SO>>(e, g, dim3(T), lds, st, p, (const KhEll *)e->d_ell_fw,            \
-                                                                  (const int *)e->d_ell_off, (const cplx *)e->d_ell_vals, u, ex,    \
-                                                                  (cplx *)nullptr, 0LL))
-#define KH_ELL_UPDATE(T, R, EM) (so ? KH_ELL_UPDATE_SO(T, R, EM, true) : KH_ELL_UPDATE_SO(T, R, EM, false))
-        if (e->ell_stream) {
-            rc = ensure_dynamic_lds(e, so ? (const void *)kh_ell_forward_update<512, KH_ELLS_RPL, 4, true, true>
-                                          : (const void *)kh_ell_forward_update<512, KH_ELLS_RPL, 4, false, true>, lds);
-            if (rc == KH_OK)
-                rc = so ? launch_persistent<kh_ell_forward_update<512, KH_ELLS_RPL, 4, true, true>>(
-                              e, g, dim3(512), lds, st, p, (const KhEll *)e->d_ell_fw, (const int *)e->d_ell_off,
-                              (const cplx *)e->d_ell_vals, u, ex, e->d_ell_scratch, e->ell_scratch_stride)
-                        : launch_persistent<kh_ell_forward_update<512, KH_ELLS_RPL, 4, false, true>>(
-                              e, g, dim3(512), lds, st, p, (const KhEll *)e->d_ell_fw, (const int *)e->d_ell_off,
-                              (const cplx *)e->d_ell_vals, u, ex, e->d_ell_scratch, e->ell_scratch_stride);
-        } else if (e->N <= 512)
-            rc = e->ell_E <= 8 ? KH_ELL_UPDATE(512, 1, 8) : e->ell_E <= 12 ? KH_ELL_UPDATE(512, 1, 12)
-                 : e->ell_E <= 16 ? KH_ELL_UPDATE(512, 1, 16) : e->ell_E <= 24 ? KH_ELL_UPDATE(512, 1, 24) : KH_ELL_UPDATE(512, 1, 32);
-        else if (e->N <= 768 && e->ell_E <= 16)
-            rc = e->ell_E <= 8 ? KH_ELL_UPDATE(768, 1, 8) : e->ell_E <= 12 ? KH_ELL_UPDATE(768, 1, 12) : KH_ELL_UPDATE(768, 1, 16);
-        else if (e->N > 1024)
-            rc = e->N <= 1536 ? KH_ELL_UPDATE(512, 3, 8) : KH_ELL_UPDATE(512, 4, 8);
-        else if (e->ell_E <= 8)
-            rc = KH_ELL_UPDATE(1024, 1, 8);
-        else
-            rc = e->ell_E <= 12 ? KH_ELL_UPDATE(512, 2, 12) : KH_ELL_UPDATE(512, 2, 16);
-#undef KH_ELL_UPDATE
-#undef KH_ELL_UPDATE_SO
-    } else if (e->kind != KIND_GENERIC && e->kind != KIND_COOP && e->kind != KIND_ELL && e->kind != KIND_TILEN) {
-        const bool rpt2 = e->kind == KIND_TILE_RPT2;
-        switch (e->L) {
-            case 1: rc = rpt2 ? launch_tile_update<2, 1>(e, p, u, ex, st) : launch_tile_update<1, 1>(e, p, u, ex, st); break;
-            case 2: rc = launch_tile_update<1, 2>(e, p, u, ex, st); break;
-            case 3: rc = launch_tile_update<1, 3>(e, p, u, ex, st); break;
-            case 4: rc = launch_tile_update<1, 4>(e, p, u, ex, st); break;
-            default: return kh_fail(KH_ERR_UNSUPPORTED, "tile kernels handle 1..4 controls");
-        }
-    } else if (e->tx_update && whole && u.sigma == nullptr && e->reduced_G == 0 && e->grid_update >= e->K && ensure_gen_adj(e)) {
-        // five to eight controls, N <= 64, one resident workgroup per objective, first order: the register-tile form with
-        // streamed operators (kh_tile64x.h); V_lk = H_lk^+ chi_k for the whole store in front of the sweep as below
-        const dim3 agrid((unsigned)(e->K * e->L), (unsigned)((e->nt + KH_GEN_ADJ_POINTS - 1) / KH_GEN_ADJ_POINTS));
-        kh_gen_adjoint_side<<<agrid, KH_GEN_ADJ_THREADS, 0, st>>>(e->d_ops_bw, u.chi_store, e->d_gen_adj, e->K, e->N, e->L, e->nt);
-        KH_HIP(hipGetLastError());
-        KhUpdateArgs ux = u;
-        ux.adj_store = e->d_gen_adj;
-        KhExchange exx = ex;
-        exx.G = e->K;
-        // (five to eight waves poll side by side: their first poll later than the register-tile kernels' -- measured best at
-        // K = 256, N = 64: 32 / 44 / 64 / 64 for L = 5 / 6 / 7 / 8, profiles/r06/ab_tile64x.txt; KH_POLL_DELAY overrides)
-        if (!e->poll_delay_set) exx.first_poll_delay = e->L <= 5 ? 32 : e->L == 6 ? 44 : 64;
-        e->last_update_grid = e->K;
-#define KH_TX_UPDATE(LT)                                                                                              \
-    do {                                                                                                              \
-        rc = ensure_dynamic_lds(e, (const void *)kh_tx_forward_update<LT>, kh_tx_lds_bytes());                        \
-        if (rc == KH_OK)                                                                                              \
-            rc = launch_persistent<kh_tx_forward_update<LT>>(e, dim3(e->K), dim3(KH_TX_THREADS), kh_tx_lds_bytes(), st, p, \
-                                                             (const cplx *const *)e->d_tx_fw, ux, exx);                \
-    } while (0)
-        switch (e->L) {
-            case 5: KH_TX_UPDATE(5); break;
-            case 6: KH_TX_UPDATE(6); break;
-            case 7: KH_TX_UPDATE(7); break;
-            default: KH_TX_UPDATE(8); break;
-        }
-#undef KH_TX_UPDATE
-    } else {
-        if (!e->gen_fits)
-            return kh_fail(KH_ERR_UNSUPPORTED, "N=%d: this form of the update sweep needs the generic kernels, whose vectors do not fit LDS", e->N);
-        const size_t lds = kh_gen_lds_bytes(e->N, e->d_csr_fw == nullptr);
-        rc = ensure_dynamic_lds(e, (const void *)kh_gen_forward_update, lds);
-        ensure_gen_scratch(e, e->grid_update);
-        KhSweepArgs pg = p;
-        pg.gen_scratch = e->d_gen_scratch;
-        pg.gen_scratch_wgs = e->gen_scratch_wgs;
-        // first order, dense operators: V_lk = H_lk^+ chi_k for the whole store in front of the sweep (kh_generic.h,
-        // kh_gen_adjoint_side) -- at the sweep's first launch (the single launch, or kh_update_begin's); the launches
-        // of a stepwise sweep that follow reuse it
-        KhUpdateArgs ug = u;
-        if (rc == KH_OK) {
-            const bool first_launch = u.internal_exchange || (u.n_dev == nullptr && u.n_begin == 0 && u.n_end == 0);
-            if (first_launch) {
-                e->gen_adj_ready = false;
-                if (u.sigma == nullptr && e->d_csr_fw == nullptr && ensure_gen_adj(e)) {
-                    const dim3 grid((unsigned)(e->K * e->L), (unsigned)((e->nt + KH_GEN_ADJ_POINTS - 1) / KH_GEN_ADJ_POINTS));
-                    kh_gen_adjoint_side<<<grid, KH_GEN_ADJ_THREADS, 0, st>>>(e->d_ops_bw, u.chi_store, e->d_gen_adj, e->K, e->N,
-                                                                              e->L, e->nt);
-                    KH_HIP(hipGetLastError());
-                    e->gen_adj_ready = true;
-                }
-            }
-            if (e->gen_adj_ready && u.sigma == nullptr) ug.adj_store = e->d_gen_adj;
-        }
-        if (rc == KH_OK && !ug.internal_exchange)
-            launch_plain<kh_gen_forward_update>(dim3(e->grid_update), dim3(KH_GEN_THREADS), lds, st, pg, ug, ex);
-        else if (rc == KH_OK)
-            rc = launch_persistent<kh_gen_forward_update>(e, dim3(e->grid_update), dim3(KH_GEN_THREADS), lds, st, pg, ug, ex);
+    int rc = KH_OK;
+    switch (update_route(e->plan, e->K, stepwise, whole, u.sigma != nullptr, e->reduced_G, ex.world, e->d_sq_fw != nullptr,
+                         [e] { return ensure_gen_adj(e); })) {
+        case ROUTE_ENS: rc = update_ens(e, p, u, ex, st, false); break;
+        case ROUTE_ENS2: rc = update_ens(e, p, u, ex, st, true); break;
+        case ROUTE_STREAM: rc = update_stream(e, p, u, ex, st); break;
+        case ROUTE_QUAD: rc = update_mini(e, p, u, ex, st, true); break;
+        case ROUTE_MINI: rc = update_mini(e, p, u, ex, st, false); break;
+        case ROUTE_Q2: rc = update_q2(e, p, u, ex, st); break;
+        case ROUTE_COOP:
+            rc = with_coop(e->plan.coop_cols, e->plan.coop_ks, [&](auto ks, auto cols) {
+                return launch_coop_update<decltype(ks)::value, decltype(cols)::value>(e, p, u, ex, st);
+            });
+            break;
+        case ROUTE_TILEN: rc = update_tilen(e, p, u, ex, st); break;
+        case ROUTE_ELL: rc = update_ell(e, p, u, ex, st); break;
+        case ROUTE_TILE:
+            rc = with_tile(e->plan.kind == KIND_TILE_RPT2, e->L, [&](auto rpt, auto lt) {
+                return launch_tile_update<decltype(rpt)::value, decltype(lt)::value>(e, p, u, ex, st);
+            });
+            break;
+        case ROUTE_TILEX: rc = update_tilex(e, p, u, ex, st); break;
+        case ROUTE_GENERIC: rc = update_generic(e, p, u, ex, st); break;
     }
     if (rc != KH_OK) return rc;
     KH_HIP(hipGetLastError());
@@ -2128,6 +2045,22 @@ static KhUpdateArgs update_args(kh_engine *e, const kh_cdouble *chi_store, const
     return u;
 }
 
+// One interval per launch (no in-kernel exchange): [n_begin, n_end) or, with n_dev, the interval read on the device;
+// then, if `reduce`, the workgroups' sums summed in a fixed order into `partial`
+static int update_interval(kh_engine *e, KhUpdateArgs u, const double *D, int n_begin, int n_end, int32_t *n_dev,
+                           double *partial, bool reduce, hipStream_t st) {
+    u.internal_exchange = 0;
+    u.D_in = D;
+    u.n_dev = n_dev;
+    u.n_begin = n_begin;
+    u.n_end = n_end;
+    KH_TRY(launch_update(e, u, st));
+    if (!reduce) return KH_OK;
+    kh_reduce_partials<<<1, 64, 0, st>>>(e->d_wg_partial, e->plan.grid_update, e->L, partial, n_dev);
+    KH_HIP(hipGetLastError());
+    return KH_OK;
+}
+
 extern "C" int kh_forward_update(kh_engine *e, const kh_cdouble *chi_store_dev, const double *chi_norms_dev,
                                  const kh_cdouble *init_dev, const double *guess_dev, const double *shape_dev,
                                  const double *lambda_dev, double *opt_dev, kh_cdouble *psi_T_dev, double *g_a_dev,
@@ -2139,7 +2072,7 @@ extern "C" int kh_forward_update(kh_engine *e, const kh_cdouble *chi_store_dev, 
     if (e->L < 1) return kh_fail(KH_ERR_INVALID, "no controls to update");
     if (opt_dev == guess_dev) return kh_fail(KH_ERR_INVALID, "opt_dev must not alias guess_dev");
     hipStream_t st = (hipStream_t)stream;
-    if (e->stepwise_only && !e->stream && !e->ens) {
+    if (e->plan.per_interval()) {
         // one launch per interval; on one GPU the "all-reduced" sums are the local ones (kh_reduce_partials has
         // summed the workgroups' pieces in a fixed order)
         KH_HIP(hipMemsetAsync(e->d_stats, 0, sizeof(double) * 4, st));
@@ -2150,7 +2083,7 @@ extern "C" int kh_forward_update(kh_engine *e, const kh_cdouble *chi_store_dev, 
                                 g_a_dev, e->d_step_partial, stream);
         if (rc == KH_OK) rc = kh_update_end(e, psi_T_dev, stream);
         e->last_intervals = e->nt - 1;
-        e->last_wgs = e->grid_update;
+        e->last_wgs = e->plan.grid_update;
         return rc;
     }
 #ifdef KH_TIMING
@@ -2161,15 +2094,14 @@ extern "C" int kh_forward_update(kh_engine *e, const kh_cdouble *chi_store_dev, 
     KH_HIP(hipMemcpyAsync(e->d_phi, init_dev, sizeof(cplx) * (size_t)e->K * e->N, hipMemcpyDeviceToDevice, st));
     KhUpdateArgs u =
         update_args(e, chi_store_dev, chi_norms_dev, guess_dev, shape_dev, lambda_dev, opt_dev, g_a_dev);
-    int rc = launch_update(e, u, st);
-    if (rc != KH_OK) return rc;
+    KH_TRY(launch_update(e, u, st));
     if (e->p2p_ready) {
         e->p2p_epoch_base += (unsigned int)e->nt;  // every rank advances identically
         e->p2p_sweeps += 1;
     }
     KH_HIP(hipMemcpyAsync(psi_T_dev, e->d_phi, sizeof(cplx) * (size_t)e->K * e->N, hipMemcpyDeviceToDevice, st));
     e->last_intervals = e->nt - 1;
-    e->last_wgs = e->last_update_grid > 0 ? e->last_update_grid : e->grid_update;
+    e->last_wgs = e->last_update_grid > 0 ? e->last_update_grid : e->plan.grid_update;
     return KH_OK;
 }
 
@@ -2177,39 +2109,27 @@ extern "C" int kh_forward_update(kh_engine *e, const kh_cdouble *chi_store_dev, 
 // compute units, so the sweep's workgroups were not all resident at once) before it gives up on the single launch.
 extern "C" int kh_set_update_workgroups(kh_engine *e, int32_t max_workgroups, int32_t *chosen) {
     if (e == nullptr || max_workgroups < 0) return kh_fail(KH_ERR_INVALID, "bad argument");
-    if (chosen != nullptr) *chosen = e->ens ? e->ens_G : (e->stream ? e->stream_G : e->grid_update);
+    if (chosen != nullptr) *chosen = e->plan.single_grid();
     if (max_workgroups == 0) {
         e->reduced_G = 0;
         return KH_OK;
     }
     if (e->p2p_ready) return kh_fail(KH_ERR_UNSUPPORTED, "sharded sweeps keep their grid (all ranks must agree on the form)");
+    const KhPlan &p = e->plan;
     int G = 0;
-    if (e->ens) {
+    if (p.ens) {
         const int widest = (e->K + 2 * KH_ENS_MAXCG - 1) / (2 * KH_ENS_MAXCG);
         if (max_workgroups < widest)
             return kh_fail(KH_ERR_UNSUPPORTED, "the ensemble kernel needs at least %d workgroups for %d objectives", widest, e->K);
-        int ncg = e->ens_ncg;
-        G = e->ens_G;
-        while (G > max_workgroups && ncg < KH_ENS_MAXCG) ncg *= 2, G = (e->K + 2 * ncg - 1) / (2 * ncg);
-        const void *forms[2] = {nullptr, nullptr};
-        switch (ncg) {
-            case 1: forms[0] = (const void *)kh_ens_forward_update<1, false>, forms[1] = (const void *)kh_ens_forward_update<1, true>; break;
-            case 2: forms[0] = (const void *)kh_ens_forward_update<2, false>, forms[1] = (const void *)kh_ens_forward_update<2, true>; break;
-            case 4: forms[0] = (const void *)kh_ens_forward_update<4, false>, forms[1] = (const void *)kh_ens_forward_update<4, true>; break;
-            default: forms[0] = (const void *)kh_ens_forward_update<8, false>, forms[1] = (const void *)kh_ens_forward_update<8, true>; break;
-        }
-        for (const void *f : forms) {
-            const int rc = ensure_dynamic_lds(e, f, kh_ens_lds_bytes(ncg));
-            if (rc != KH_OK) return rc;
-        }
+        const void *forms[2];
+        KH_TRY(ens_forms(e, p.ens_cols(e->K, max_workgroups, &G), forms));
     } else {
-        const bool tile_family = (e->kind == KIND_TILE_Q2 && !e->mini) || e->kind == KIND_TILE_RPT1 || e->kind == KIND_TILE_RPT2;
-        if (!tile_family || e->d_csr_fw != nullptr || e->N > KH_TILE_N || e->L < 1 || e->L > 4)
+        if (!p.tile_family() || e->d_csr_fw != nullptr || e->N > KH_TILE_N || e->L < 1 || e->L > 4)
             return kh_fail(KH_ERR_UNSUPPORTED, "only the register-tile families (N <= 64, 1..4 controls) have a form with fewer workgroups");
         const int fewest = (e->K + KH_STREAM_MMAX - 1) / KH_STREAM_MMAX;
         if (max_workgroups < fewest)
             return kh_fail(KH_ERR_UNSUPPORTED, "%d objectives need at least %d workgroups (%d per workgroup)", e->K, fewest, KH_STREAM_MMAX);
-        G = e->stream ? e->stream_G : e->grid_update;
+        G = p.stream ? p.stream_G : p.grid_update;
         if (max_workgroups < G) G = max_workgroups;
     }
     e->reduced_G = max_workgroups;
@@ -2245,14 +2165,8 @@ extern "C" int kh_update_begin(kh_engine *e, const kh_cdouble *chi_store_dev, co
     KH_HIP(hipMemcpyAsync(opt_dev, guess_dev, sizeof(double) * (size_t)e->L * (e->nt - 1),
                           hipMemcpyDeviceToDevice, st));
     KH_HIP(hipMemsetAsync(g_a_dev, 0, sizeof(double) * e->L, st));
-    KhUpdateArgs u = update_args(e, chi_store_dev, chi_norms_dev, guess_dev, nullptr, nullptr, opt_dev, g_a_dev);
-    u.internal_exchange = 0;
-    u.n_begin = u.n_end = 0;
-    int rc = launch_update(e, u, st);
-    if (rc != KH_OK) return rc;
-    kh_reduce_partials<<<1, 64, 0, st>>>(e->d_wg_partial, e->grid_update, e->L, partial_dev, nullptr);
-    KH_HIP(hipGetLastError());
-    return KH_OK;
+    const KhUpdateArgs u = update_args(e, chi_store_dev, chi_norms_dev, guess_dev, nullptr, nullptr, opt_dev, g_a_dev);
+    return update_interval(e, u, nullptr, 0, 0, nullptr, partial_dev, true, st);
 }
 
 extern "C" int kh_update_step(kh_engine *e, int32_t n, const double *D_dev, const kh_cdouble *chi_store_dev,
@@ -2264,20 +2178,8 @@ extern "C" int kh_update_step(kh_engine *e, int32_t n, const double *D_dev, cons
         return kh_fail(KH_ERR_INVALID, "null argument");
     if (e->guess_dev == nullptr) return kh_fail(KH_ERR_INVALID, "kh_update_begin was not called");
     if (n < 0 || n >= e->nt - 1) return kh_fail(KH_ERR_INVALID, "interval %d out of range", n);
-    hipStream_t st = (hipStream_t)stream;
-    KhUpdateArgs u =
-        update_args(e, chi_store_dev, chi_norms_dev, e->guess_dev, shape_dev, lambda_dev, opt_dev, g_a_dev);
-    u.internal_exchange = 0;
-    u.D_in = D_dev;
-    u.n_begin = n;
-    u.n_end = n + 1;
-    int rc = launch_update(e, u, st);
-    if (rc != KH_OK) return rc;
-    if (n + 1 < e->nt - 1) {
-        kh_reduce_partials<<<1, 64, 0, st>>>(e->d_wg_partial, e->grid_update, e->L, partial_dev, nullptr);
-        KH_HIP(hipGetLastError());
-    }
-    return KH_OK;
+    const KhUpdateArgs u = update_args(e, chi_store_dev, chi_norms_dev, e->guess_dev, shape_dev, lambda_dev, opt_dev, g_a_dev);
+    return update_interval(e, u, D_dev, n, n + 1, nullptr, partial_dev, n + 1 < e->nt - 1, (hipStream_t)stream);
 }
 
 extern "C" int kh_update_step_dev(kh_engine *e, int32_t *n_dev, const double *D_dev,
@@ -2289,19 +2191,8 @@ extern "C" int kh_update_step_dev(kh_engine *e, int32_t *n_dev, const double *D_
         g_a_dev == nullptr || partial_dev == nullptr)
         return kh_fail(KH_ERR_INVALID, "null argument");
     if (e->guess_dev == nullptr) return kh_fail(KH_ERR_INVALID, "kh_update_begin was not called");
-    hipStream_t st = (hipStream_t)stream;
-    KhUpdateArgs u =
-        update_args(e, chi_store_dev, chi_norms_dev, e->guess_dev, shape_dev, lambda_dev, opt_dev, g_a_dev);
-    u.internal_exchange = 0;
-    u.D_in = D_dev;
-    u.n_dev = n_dev;
-    u.n_begin = 0;  // overridden on the device
-    u.n_end = 1;
-    int rc = launch_update(e, u, st);
-    if (rc != KH_OK) return rc;
-    kh_reduce_partials<<<1, 64, 0, st>>>(e->d_wg_partial, e->grid_update, e->L, partial_dev, n_dev);
-    KH_HIP(hipGetLastError());
-    return KH_OK;
+    const KhUpdateArgs u = update_args(e, chi_store_dev, chi_norms_dev, e->guess_dev, shape_dev, lambda_dev, opt_dev, g_a_dev);
+    return update_interval(e, u, D_dev, 0, 1, n_dev, partial_dev, true, (hipStream_t)stream);  // (n_begin: overridden on the device)
 }
 
 extern "C" int kh_update_end(kh_engine *e, kh_cdouble *psi_T_dev, void *stream) {
@@ -2311,7 +2202,6 @@ extern "C" int kh_update_end(kh_engine *e, kh_cdouble *psi_T_dev, void *stream) 
     e->guess_dev = nullptr;
     return KH_OK;
 }
-
 
 // ---------------------------------------------------------------------------
 // cross-GPU exchange windows (sharded objectives, one rank per GPU)
@@ -2351,7 +2241,7 @@ extern "C" int kh_p2p_create_window(kh_engine *e, int32_t world, int32_t rank, u
     const int Lx = e->L > 0 ? e->L : 1;
     if (world * Lx * 2 > 64 || Lx > KH_MAX_L)
         return kh_fail(KH_ERR_UNSUPPORTED, "world * L = %d exceeds the 32 exchange lanes (or more than %d controls)", world * Lx, KH_MAX_L);
-    if (e->stepwise_only && !e->ens)  // (the caller falls back to kh_update_step + an all-reduce per interval)
+    if (!e->plan.exchanges_in_kernel())  // (the caller falls back to kh_update_step + an all-reduce per interval)
         return kh_fail(KH_ERR_UNSUPPORTED, "%d objectives per GPU are not co-resident: no in-kernel exchange", e->K);
     if (e->p2p_window != nullptr) return kh_fail(KH_ERR_INVALID, "window already created");
     e->p2p_world = world;
@@ -2533,8 +2423,7 @@ extern "C" int kh_debug_occupy(kh_engine *e, int32_t workgroups, double millisec
     if (e == nullptr || workgroups < 1 || !(milliseconds >= 0.0) || milliseconds > 1000.0)
         return kh_fail(KH_ERR_INVALID, "bad argument");
     const size_t lds = 128 * 1024;
-    const int rc = ensure_dynamic_lds(e, (const void *)kh_occupy_kernel, lds);
-    if (rc != KH_OK) return rc;
+    KH_TRY(ensure_dynamic_lds(e, (const void *)kh_occupy_kernel, lds));
     kh_occupy_kernel<<<workgroups, 512, lds, (hipStream_t)stream>>>((long long)(milliseconds * 1e5), (int *)e->d_abort + 0);
     KH_HIP(hipGetLastError());
     return KH_OK;
