@@ -15,6 +15,11 @@ wall time of one timed step (``--steps`` of them, after ``--warmup`` untimed
 ones).  ``--dump-outputs DIR`` writes what the last timed step returned to the
 caller as ``DIR/<name>.npy`` (``dump_outputs``).
 
+A plain run measures the headline alone: set-up, warm-up, the timed steps, the
+dump if asked for, the line.  Everything else listed below -- the side
+measurements of other configurations, transports and sizes, the CPU baseline --
+runs only with ``--full``.
+
 For N > 1 there is one rank per GPU.  Either a launcher provides them
 (``python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N``:
 RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment), or -- plain
@@ -24,7 +29,8 @@ their return code.  The headline line keeps the per-GPU work fixed (``"scaling":
 "weak"``, what the driver's contract asks of a path that shards over independent
 units): 256 objectives PER GPU -- at N = 1 BASELINE config 5 itself --, the L update
 sums crossing the GPUs once per time interval inside the persistent kernels
-(peer-mapped windows over xGMI).  The same JSON line carries
+(peer-mapped windows over xGMI).  The line carries ``"n_ranks_seen"``
+(``torch.distributed.get_world_size()``) and, per rank, ``"ranks"``; with ``--full`` also
 * ``"strong"``: BASELINE config 5 to the letter on N GPUs, 256 objectives IN TOTAL
   sharded over the ranks, 256/N per GPU (``--scaling strong`` makes that one the
   headline instead; the sweeps are bound by the latency of a time step, not by the
@@ -34,17 +40,17 @@ sums crossing the GPUs once per time interval inside the persistent kernels
   of the interval loop), a few iterations,
 * ``"config4"`` (N = 2, 4, 8): three iterations of BASELINE config 4 -- quoted on 2 and 4
   GPUs -- with its 16 density matrices sharded over the ranks (cooperative matrix-core
-  kernels, update sums through the peer windows),
-* ``"n_ranks_seen"``: ``torch.distributed.get_world_size()``.
+  kernels, update sums through the peer windows).
 Each of these side measurements runs under a watchdog (``--rccl-leg-timeout``): if one
 hangs or fails, the headline line is printed with an ``"error"`` entry in its place.
-At N = 1 the line carries instead, measured after the headline and not part of
+At N = 1 the ``--full`` line carries instead, measured after the headline and not part of
 ``value``: ``"config4"`` (three iterations of BASELINE config 4, 16 density
 matrices under one 400-dim Liouvillian: the cooperative fp64 matrix-core
 kernels; ``--no-config4`` skips it, ``--workload c4`` makes it the line itself)
 and the two variants SURVEY.md 8d asks for, ``"L4"`` (four controls) and
 ``"distinct"`` (256 distinct random drifts), three iterations each, ``"L8"`` (eight controls)
-(``--no-variants`` skips them).
+(``--no-variants`` skips them), ``"N96"``, ``"K1024"``, ``"K1024_distinct"``, ``"sparse"``
+(``--no-sparse``) and ``"cpu_baseline"`` (``--no-cpu-baseline``).
 """
 import argparse
 import gc
@@ -473,19 +479,24 @@ def main():
                          "single-GPU variant line for profiles/, not the headline")
     ap.add_argument('--scaling', choices=['weak', 'strong'], default='weak',
                     help='weak (default): --K objectives per GPU; strong: --K objectives in total over all GPUs = BASELINE '
-                         'config 5 to the letter.  The other one is measured too and reported under "strong" / "weak" of '
-                         'the same line (at one GPU they are the same job)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+                         'config 5 to the letter.  With --full the other one is measured too and reported under "strong" / '
+                         '"weak" of the same line (at one GPU they are the same job)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, run every side measurement too (CPU baseline, the other configurations, '
+                         'scaling, transport and sizes; see the module docstring); a plain run measures the headline alone')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
     ap.add_argument('--no-config4', action='store_true',
-                    help='skip the short run of BASELINE config 4 (the one matrix-core workload) that the default '
-                         'single-GPU line carries under "config4"')
+                    help='with --full: skip the short run of BASELINE config 4 (the one matrix-core workload) that the '
+                         'line carries under "config4"')
     ap.add_argument('--no-variants', action='store_true',
-                    help='skip the short L=4 and distinct-drift runs the default single-GPU line carries under "L4" / "distinct"')
+                    help='with --full: skip the short runs of other controls, drifts, N and K the single-GPU line '
+                         'carries under "L4" / "distinct" / "L8" / "N96" / "K1024" / "K1024_distinct"')
     ap.add_argument('--no-sparse', action='store_true',
-                    help='skip the sparse-operator leg the default single-GPU line carries under "sparse" (the reference\'s '
-                         'notebook 06 through DensityMatrixODEPropagator)')
+                    help='with --full: skip the sparse-operator leg the single-GPU line carries under "sparse" (the '
+                         'reference\'s notebook 06 through DensityMatrixODEPropagator)')
     ap.add_argument('--no-rccl-leg', action='store_true',
-                    help='multi-rank runs: skip the extra measurement with one RCCL all-reduce per time interval ("rccl")')
+                    help='with --full, multi-rank runs: skip the extra measurement with one RCCL all-reduce per time '
+                         'interval ("rccl")')
     ap.add_argument('--rccl-leg-timeout', type=int, default=240, help='seconds the "rccl" side measurement may take')
     ap.add_argument('--force-dist', action='store_true',
                     help='run the multi-GPU code path (stepwise sweep + RCCL all-reduce per interval) even on 1 rank')
@@ -869,7 +880,7 @@ def main():
 
     if world == 1 or args.scaling == 'strong':
         name_the_baseline_job(out if rank == 0 else None)
-    if world > 1 and args.workload == 'c5':
+    if args.full and world > 1 and args.workload == 'c5':
         # the same job with the other partitioning of the objectives (see the module docstring) -- like every side
         # measurement of a sharded run under the watchdog: the headline line above must get out whatever happens here
         second = guarded(other, args.rccl_leg_timeout, lambda: measure(other))
@@ -884,7 +895,7 @@ def main():
                 if k in second:
                     out[other][k] = second[k]
     rccl = None
-    if (world > 1 or args.force_dist) and args.workload == 'c5' and not args.no_rccl_leg:
+    if args.full and (world > 1 or args.force_dist) and args.workload == 'c5' and not args.no_rccl_leg:
         # the north star's transport: one RCCL all-reduce of the L update sums per time interval (kh_update_begin /
         # step_dev / end with HIP-graph replay) instead of the peer windows inside the persistent kernel.
         rccl = guarded('rccl', args.rccl_leg_timeout,
@@ -892,7 +903,7 @@ def main():
         if rank == 0 and rccl is not None:
             out['rccl'] = rccl
             rccl = None
-    if world > 1 and 16 % world == 0 and args.workload == 'c5' and not args.no_config4:
+    if args.full and world > 1 and 16 % world == 0 and args.workload == 'c5' and not args.no_config4:
         # BASELINE config 4 is quoted on 2 and 4 GPUs: its 16 density matrices sharded over the ranks (16 / N each: the
         # cooperative matrix-core kernels with fewer column groups per GPU, the update sums across the GPUs through the
         # peer windows), three iterations.  Not part of `value`.
@@ -902,18 +913,18 @@ def main():
     if rank == 0:
         if rccl is not None:
             out['rccl'] = rccl
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(args)
             out['speedup_vs_cpu_baseline'] = out['value'] / out['cpu_baseline']['value']
             if out['cpu_baseline'].get('reference_loop'):
                 out['speedup_vs_reference_loop_single_process'] = out['value'] / out['cpu_baseline']['reference_loop']['props_per_s']
     headline_shape = args.workload == 'c5' and args.K == 256 and args.N == 64 and args.L == 1 and not args.distinct
-    if world == 1 and group is None and headline_shape:
+    if args.full and world == 1 and group is None and headline_shape:
         if not args.no_config4:
             # BASELINE config 4 (16 density matrices under one 400-dim Liouvillian: the cooperative fp64 MFMA kernels),
             # three iterations after the headline measurement, in this process (a second process on the GPU while this
-            # one holds its context measured 2x slower): so that the default line -- the one the driver records -- also
-            # carries a number for the one workload whose propagator is a dense product.  Not part of `value`.
+            # one holds its context measured 2x slower): so that the full line also carries a number for the one
+            # workload whose propagator is a dense product.  Not part of `value`.
             out['config4'] = leg(workload='c4', steps=3, warmup=1, pmc_case='config4')
         if not args.no_variants:
             # "L=1 (also report L=4)" and "a second variant with K distinct random H0_k"

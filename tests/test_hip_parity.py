@@ -2390,8 +2390,34 @@ def test_bench_dump_outputs_match_the_oracle(tmp_path):
 
 
 @pytest.mark.no_oracle
+def test_bench_plain_run_measures_the_headline_alone():
+    """``python bench.py --gpus 1`` without ``--full`` on the headline's shape (256 objectives, N = 64, one control; a
+    shortened grid): the line carries the headline and its own kernel figures, and none of the side measurements that
+    only ``--full`` runs."""
+    import json
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1', '--nt', '101']
+    proc = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert proc.returncode == 0, proc.stderr[-2000:]
+    lines = [ln for ln in proc.stdout.splitlines() if ln.startswith('{')]
+    assert len(lines) == 1, proc.stdout[-2000:]
+    rec = json.loads(lines[0])
+    assert rec['n_gpus'] == 1 and rec['steps'] == 2 and rec['warmup'] == 1 and rec['value'] > 0 and rec['ms_per_step'] > 0
+    assert rec['unit'] == 'props/s' and rec['higher_is_better'] is True and rec['dtype'] == 'f64'
+    assert rec['config']['objectives'] == 256 and rec['config']['kernel'] == 'tile64q2/512'
+    assert rec['kernels']['update_sweep_ms'] > 0 and rec['roofline']['frac'] > 0
+    side = {'cpu_baseline', 'speedup_vs_cpu_baseline', 'config4', 'L4', 'distinct', 'L8', 'N96', 'K1024',
+            'K1024_distinct', 'sparse', 'strong', 'weak', 'rccl'}
+    assert not side & set(rec), sorted(side & set(rec))
+    assert not rec.get('degraded', False)
+
+
+@pytest.mark.no_oracle
 def test_bench_self_launches_two_ranks(tmp_path):
-    """``python bench.py --gpus 2`` with no launcher and no WORLD_SIZE in the environment -- the form the driver's
+    """``python bench.py --gpus 2 --full`` with no launcher and no WORLD_SIZE in the environment -- the form the driver's
     scaling run uses -- must start its ranks itself, print ONE JSON line from rank 0 and exit 0.  Here both ranks
     share the one GPU (host collectives over gloo, picked automatically; the in-kernel peer windows as on a node).
     The line must carry the headline (weak scaling), the strong-scaling measurement, the RCCL-per-interval leg and
@@ -2404,7 +2430,7 @@ def test_bench_self_launches_two_ranks(tmp_path):
     env.pop('KH_DIST_BACKEND', None)
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     # (--K 128: the two ranks' workgroups must be resident on the ONE GPU at the same time -- 2 x 128 fill it)
-    cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1',
+    cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--full',
            '--no-cpu-baseline', '--nt', '201', '--K', '128']
     proc = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert proc.returncode == 0, proc.stderr[-2000:]
@@ -2428,7 +2454,7 @@ def test_bench_self_launches_two_ranks(tmp_path):
 
 @pytest.mark.no_oracle
 def test_bench_two_gpus_strong_scaling_where_the_box_has_them():
-    """``python bench.py --gpus 2 --scaling strong`` on a box with at least two GPUs: BASELINE config 5 to the letter (256
+    """``python bench.py --gpus 2 --scaling strong --full`` on a box with at least two GPUs: BASELINE config 5 to the letter (256
     objectives in total, 128 per GPU) with one rank per device -- RCCL underneath, the sums through peer windows over
     xGMI.  Skipped on the one-GPU box these tests were written on (the same command line with ranks sharing the device
     is test_bench_self_launches_two_ranks)."""
@@ -2444,7 +2470,7 @@ def test_bench_two_gpus_strong_scaling_where_the_box_has_them():
     env.pop('KH_DIST_BACKEND', None)
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--scaling', 'strong', '--steps', '2', '--warmup', '1',
-           '--no-cpu-baseline', '--nt', '401']
+           '--full', '--no-cpu-baseline', '--nt', '401']
     proc = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert proc.returncode == 0, proc.stderr[-2000:]
     rec = json.loads([ln for ln in proc.stdout.splitlines() if ln.startswith('{')][0])
@@ -2476,7 +2502,7 @@ def _check_rank_diagnostics(rec, world):
 
 @pytest.mark.no_oracle
 def test_bench_gpus_8_dry_run_on_one_gpu(tmp_path):
-    """``python bench.py --gpus 8`` -- the driver's SCALE command at its largest N -- as a dry run: 8 ranks sharing the one
+    """``python bench.py --gpus 8 --full`` -- the driver's SCALE command at its largest N -- as a dry run: 8 ranks sharing the one
     GPU, 32 objectives each (config 5's 8-GPU partition: 256 workgroups in total, all co-resident), a shortened grid.
     The weak (headline), strong and rccl legs must be there, nothing degraded, the peer windows used, far inside the
     driver's 1 800 s.  (The config-4 leg is exercised with two ranks in test_bench_self_launches_two_ranks and at world 8
@@ -2494,7 +2520,7 @@ def test_bench_gpus_8_dry_run_on_one_gpu(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     env.pop('KH_DIST_BACKEND', None)
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '8', '--steps', '2', '--warmup', '1',
+    cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '8', '--steps', '2', '--warmup', '1', '--full',
            '--no-cpu-baseline', '--nt', '101', '--K', '32', '--no-config4']
     t0 = time.time()
     proc = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1200)
