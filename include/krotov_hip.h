@@ -129,9 +129,24 @@ typedef struct kh_problem_csr {
 
 int kh_engine_create_csr(const kh_problem_csr *problem, kh_engine **out);
 
+/* Objectives of different dimension or kind in ONE engine (the reference treats every objective on its own,
+ * optimize.py:254-261, 806-911; they meet only in the sum of the pulse update, :454-470): one launch per sweep, the
+ * generic kernels' mixed form (kh_engine_kernel: "generic/mixed").
+ *   problem->N        the stride S = max(dims) of every state buffer; problem->is_super is ignored
+ *   dims     [K]      host: N_k of objective k
+ *   is_super [K]      host: 0 Hilbert space (f = -i, mu factor 1), 1 Liouville space (f = 1, mu factor i)
+ *   problem->ops[k*(1+L)+j]  a dense row-major dims[k] x dims[k] operator (NULL where a control is absent)
+ * Every entry point takes the buffer shapes documented for it, [K][N] and [K][nt][N], at stride S.  Padding contract:
+ * the sweeps read the first N_k entries of objective k's states and may find anything behind them; every state they
+ * write (stored trajectories, psi_T, the second-order store) holds exact zeros behind them.  kh_tau and
+ * kh_chi_boundary run at stride S: their targets must be zero behind N_k.  Dense operators only; Taylor series and the
+ * update sums on the forward side; not sharded (kh_p2p_create_window refuses), kh_set_update_workgroups answers
+ * KH_ERR_UNSUPPORTED.  KH_ERR_UNSUPPORTED for S > 2540 (the generic kernels' LDS) and more than 32 controls. */
+int kh_engine_create_mixed(const kh_problem *problem, const int32_t *dims, const int32_t *is_super, kh_engine **out);
+
 /* Which kernel family the engine selected: "tile64q2/512", "tile64/512", "tile64/256", "tile64/stream" (more objectives
  * than stay co-resident: one launch, the operators streamed; KH_NO_STREAM=1: "tile64/512 per interval"), "mini16/wave", "mini4/wave", "coop16/mfma", "tile128/512" (per-objective operators, 64 < N <= 128), "ell/csr"
- * (sparse operators with the matrix in registers), "generic" or "generic/csr". */
+ * (sparse operators with the matrix in registers), "generic", "generic/csr" or "generic/mixed" (kh_engine_create_mixed). */
 const char *kh_engine_kernel(const kh_engine *engine);
 
 /* Forward propagation of K states over the whole grid under fixed pulses.

@@ -68,6 +68,8 @@ SYMBOLS = {
     'kh_version': (ctypes.c_char_p, []),
     'kh_engine_create': (ctypes.c_int, [ctypes.POINTER(kh_problem), ctypes.POINTER(_P)]),
     'kh_engine_create_csr': (ctypes.c_int, [ctypes.POINTER(kh_problem_csr), ctypes.POINTER(_P)]),
+    'kh_engine_create_mixed': (ctypes.c_int, [ctypes.POINTER(kh_problem), ctypes.POINTER(ctypes.c_int32),
+                                              ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_P)]),
     'kh_engine_destroy': (None, [_P]),
     'kh_engine_kernel': (ctypes.c_char_p, [_P]),
     'kh_forward_store': (ctypes.c_int, [_P, _P, _P, _P, _P, _P]),

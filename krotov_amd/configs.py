@@ -21,6 +21,8 @@ __all__ = [
     'config_c3',
     'config_c4',
     'config_c5',
+    'config_mixed',
+    'mixed_to_objectives',
     'spec_to_objectives',
     'liouvillian_dense',
     'herm',
@@ -408,4 +410,103 @@ def spec_to_objectives(spec, krotov_module, column_states=True):
         c: dict(lambda_a=spec.lambda_a, update_shape=spec.update_shape)
         for c in spec.controls
     }
+    return objectives, pulse_options
+
+
+# --------------------------------------------------------------------------
+# Objectives of different dimension or kind, one shared control u(t)
+# --------------------------------------------------------------------------
+
+
+def _ladder(d):
+    """a + a^dagger of a d-level ladder."""
+    a = np.diag(np.sqrt(np.arange(1, d, dtype=np.float64)), 1).astype(np.complex128)
+    return a, a + a.conj().T
+
+
+def _ket(d, i):
+    v = np.zeros((d, 1), dtype=np.complex128)
+    v[i, 0] = 1.0
+    return v
+
+
+def _dm(d, i):
+    return _ket(d, i) @ _ket(d, i).conj().T
+
+
+def config_mixed(case='dims', nt=201, T=5.0, lambda_a=2.0, chi='re', seed=7):
+    """One control u(t) shared by objectives of different dimension and kind (seeded).
+
+    ``case='dims'``: a 3-level ladder ket, a 5-level ket (random Hermitian drift and drive) and a driven, damped qutrit
+    density matrix under a Lindblad Liouvillian (N = 3, 5, 9).  ``case='same_n'``: a 4-level ket next to a damped qubit
+    density matrix (both N = 4, different kinds).  ``case='wide'``: a 40-level ket next to a 100-level ket (N_k > 96:
+    the generic kernels' scratch generator).
+
+    Returns a :class:`ProblemSpec` whose per-objective lists ``H0``, ``Hc``, ``init``, ``target`` hold each objective's
+    own operators (N_k x N_k) and states (kets (N_k, 1), density matrices (d, d)); ``kinds[k]``: Liouville space;
+    ``dims[k]``: N_k.  :func:`mixed_to_objectives` builds the objectives.
+    """
+    rng = np.random.default_rng(seed)
+    H0, Hc, init, target, kinds = [], [], [], [], []
+
+    def ket_obj(H, H1, i0, i1):
+        d = H.shape[0]
+        H0.append(H)
+        Hc.append([H1])
+        init.append(_ket(d, i0))
+        target.append(_ket(d, i1))
+        kinds.append(False)
+
+    def dm_obj(H, H1, c_ops, i0, i1):
+        d = H.shape[0]
+        H0.append(liouvillian_dense(H, c_ops))
+        Hc.append([liouvillian_dense(H1)])
+        init.append(_dm(d, i0))
+        target.append(_dm(d, i1))
+        kinds.append(True)
+
+    if case == 'dims':
+        _, x3 = _ladder(3)
+        ket_obj(np.diag([0.0, 1.0, 1.9]).astype(np.complex128), x3, 0, 1)
+        ket_obj(herm(rng, 5, 1.0), herm(rng, 5, 0.5), 0, 1)
+        a, x = _ladder(3)
+        dm_obj(np.diag([0.0, 1.0, 2.05]).astype(np.complex128), x, [np.sqrt(0.02) * a], 0, 1)
+    elif case == 'same_n':
+        _, x4 = _ladder(4)
+        ket_obj(np.diag([0.0, 1.0, 1.95, 2.85]).astype(np.complex128), x4, 0, 1)
+        a, x = _ladder(2)
+        dm_obj(np.diag([0.5, -0.5]).astype(np.complex128), x, [np.sqrt(0.03) * a], 1, 0)
+    elif case == 'wide':
+        for d in (40, 100):
+            ket_obj(herm(rng, d, 1.0), herm(rng, d, 0.5), 0, 1)
+    else:
+        raise ValueError("unknown case %r" % case)
+
+    def guess(t, args):
+        return 0.2 * _shapes.flattop(t, t_start=0, t_stop=T, t_rise=0.3 * T / 5.0, func='blackman')
+
+    def update_shape(t):
+        return _shapes.flattop(t, t_start=0, t_stop=T, t_rise=0.3 * T / 5.0, func='blackman')
+
+    spec = ProblemSpec.__new__(ProblemSpec)
+    spec.__dict__.update(
+        name='mixed_%s' % case, H0=H0, Hc=Hc, init=init, target=target, kinds=kinds,
+        dims=[h.shape[0] for h in H0], is_super=kinds, tlist=np.linspace(0.0, T, nt), controls=[guess],
+        update_shape=update_shape, lambda_a=lambda_a, chi=chi, weights=None)
+    spec.K, spec.L, spec.N = len(H0), 1, max(spec.dims)
+    return spec
+
+
+def mixed_to_objectives(spec, krotov_module, vectorized=False):
+    """``(objectives, pulse_options)`` of a :func:`config_mixed` spec.  ``vectorized``: density matrices handed over
+    as column-stacked (d*d, 1) vectors (the reference's numpy mode, whose propagator multiplies the Liouvillian into
+    the state array), else as (d, d) matrices."""
+    objectives = []
+    for k in range(spec.K):
+        H = [spec.H0[k]] + [[spec.Hc[k][l], spec.controls[l]] for l in range(spec.L)]
+        psi0, tgt = spec.init[k], spec.target[k]
+        if vectorized and spec.kinds[k]:
+            psi0, tgt = _vec(psi0).reshape(-1, 1), _vec(tgt).reshape(-1, 1)
+        objectives.append(krotov_module.Objective(initial_state=psi0, target=tgt, H=H))
+    pulse_options = {c: dict(lambda_a=spec.lambda_a, update_shape=spec.update_shape) for c in spec.controls}
     return objectives, pulse_options

@@ -41,6 +41,16 @@ struct KhSweepArgs {
     int gen_scratch_wgs;
 };
 
+// Mixed engines (kh_engine_create_mixed): objectives of different dimension or kind in one launch.  KhSweepArgs::N is
+// then the stride S = max N_k of every [K][N] / [K][nt][N] buffer; objective k works on its first N_k entries and the
+// kernels write exact zeros behind them.  Uniform engines pass an empty KhMixedArgs (the MIXED = false instantiations
+// never read it).
+struct KhMixedArgs {
+    const int *dims;   // [K] N_k
+    const cplx *f;     // [K] equation-of-motion factor of the launch's direction: -i / +i (Hilbert), 1 (Liouville)
+    const cplx *mu;    // [K] mu factor of the update sums: 1 (Hilbert) or i (Liouville), mu.py:130-134
+};
+
 // LDS layout (dynamic): xa[N] xb[N] acc[N] chi[N] + scratch [+ the interval's generator A(eps), N x N, where it fits]
 // Everything per control is an LDS array of KH_GEN_MAX_L entries (thread l works on control l): the generic kernels take
 // up to KH_GEN_MAX_L = 32 controls (the reference loops over any number of pulses, optimize.py:454-477; the
@@ -219,11 +229,12 @@ __device__ __forceinline__ void kh_gen_rows4_staged(const cplx *A, int N, int ro
 }
 
 // acc <- exp(f * A(eps) * dt) acc, A = H0 + sum eps_l H_l, by s Taylor
-// sub-steps of degree m.  All threads of the workgroup call this.
-__device__ __forceinline__ int kh_gen_expm_action(const KhSweepArgs &p, const cplx *const *ops_k,
-                                                  const KhCsr *csr_k, const double *norms_k, const double *eps,
-                                                  double dt, const KhGenLds &s) {
-    const int tid = threadIdx.x, N = p.N, L = p.L;
+// sub-steps of degree m; N: the objective's dimension (p.N but on mixed engines), f = (fre, fim).  All threads of the
+// workgroup call this.
+__device__ __forceinline__ int kh_gen_expm_action(const KhSweepArgs &p, int N, double fre, double fim,
+                                                  const cplx *const *ops_k, const KhCsr *csr_k, const double *norms_k,
+                                                  const double *eps, double dt, const KhGenLds &s) {
+    const int tid = threadIdx.x, L = p.L;
     const int grp = tid >> 4, c16 = tid & 15;  // 16 groups of 16 lanes
     double theta = norms_k[0];
     for (int l = 0; l < L; ++l) theta += fabs(eps[l]) * norms_k[1 + l];
@@ -242,7 +253,7 @@ __device__ __forceinline__ int kh_gen_expm_action(const KhSweepArgs &p, const cp
     // workgroup only, its barrier orders both; the reads then stream ONE matrix per term instead of 1 + L)
     cplx *gen = s.A;
     if (gen == nullptr && csr_k == nullptr && p.gen_scratch != nullptr && (int)blockIdx.x < p.gen_scratch_wgs)
-        gen = p.gen_scratch + (size_t)blockIdx.x * N * N;
+        gen = p.gen_scratch + (size_t)blockIdx.x * p.N * p.N;  // (one S x S matrix per workgroup)
     const bool staged = gen != nullptr && csr_k == nullptr;
     if (staged) kh_gen_build_generator(ops_k, eps, L, N, gen);
     for (int sub = 0; sub < nsub; ++sub) {
@@ -255,7 +266,7 @@ __device__ __forceinline__ int kh_gen_expm_action(const KhSweepArgs &p, const cp
         cplx *xin = s.xa, *xout = s.xb;
         for (int j = 1; j <= m; ++j) {
             const double hj = h * ratio[j];
-            const cplx coef = c_make(p.fre * hj, p.fim * hj);
+            const cplx coef = c_make(fre * hj, fim * hj);
             if (staged) {
                 for (int row0 = 0; row0 < N; row0 += 64) {
                     cplx d[4];
@@ -291,28 +302,40 @@ __device__ __forceinline__ int kh_gen_expm_action(const KhSweepArgs &p, const cp
     return nsub * m;
 }
 
+// dst[0, NS) <- src[0, N) and, on mixed engines, exact zeros in [N, NS) (uniform engines: N == NS).  All threads.
+template <bool MIXED>
+__device__ __forceinline__ void kh_gen_put(cplx *__restrict__ dst, const cplx *src, int N, int NS) {
+    if (MIXED) {
+        for (int i = threadIdx.x; i < NS; i += KH_GEN_THREADS) dst[i] = i < N ? src[i] : c_make(0.0, 0.0);
+    } else {
+        for (int i = threadIdx.x; i < N; i += KH_GEN_THREADS) dst[i] = src[i];
+    }
+}
+
 // ---------------------------------------------------------------------------
 // plain propagation with storage (backward sweep, iteration-0 forward sweep)
 // ---------------------------------------------------------------------------
 // direction +1: n = 0..nt-2, state index n -> n+1 (optimize.py:806-846)
 // direction -1: n = nt-2..0, state index n+1 -> n (optimize.py:849-886)
+// MIXED: objective k has its own dimension mx.dims[k] and factor mx.f[k] (kh_engine_create_mixed)
+template <bool MIXED>
 __global__ void __launch_bounds__(KH_GEN_THREADS)
-kh_gen_sweep_store(KhSweepArgs p, const double *__restrict__ pulses, const cplx *__restrict__ state_in,
-                   cplx *__restrict__ store, cplx *__restrict__ state_out, int direction)
-#if KH_DEFINES(KH_TU_GENERIC)
-{
+kh_gen_sweep_store(KhSweepArgs p, KhMixedArgs mx, const double *__restrict__ pulses, const cplx *__restrict__ state_in,
+                   cplx *__restrict__ store, cplx *__restrict__ state_out, int direction) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const KhGenLds s = kh_gen_carve(smem, p.N, p.csr == nullptr);
-    const int tid = threadIdx.x, N = p.N, L = p.L, nt = p.nt;
+    const int tid = threadIdx.x, NS = p.N, L = p.L, nt = p.nt;
     double matvecs = 0.0;
     for (int k = blockIdx.x; k < p.K; k += gridDim.x) {
         const cplx *const *ops_k = p.ops + (size_t)k * (1 + L);
         const double *norms_k = p.op_norms + (size_t)k * (1 + L);
-        for (int i = tid; i < N; i += KH_GEN_THREADS) s.acc[i] = state_in[(size_t)k * N + i];
+        const int N = MIXED ? mx.dims[k] : NS;
+        const double fre = MIXED ? mx.f[k].x : p.fre, fim = MIXED ? mx.f[k].y : p.fim;
+        for (int i = tid; i < N; i += KH_GEN_THREADS) s.acc[i] = state_in[(size_t)k * NS + i];
         __syncthreads();
         if (store != nullptr) {
             const int idx0 = direction > 0 ? 0 : nt - 1;
-            for (int i = tid; i < N; i += KH_GEN_THREADS) store[((size_t)k * nt + idx0) * N + i] = s.acc[i];
+            kh_gen_put<MIXED>(store + ((size_t)k * nt + idx0) * NS, s.acc, N, NS);
         }
         for (int step = 0; step < nt - 1; ++step) {
             const int n = direction > 0 ? step : nt - 2 - step;
@@ -320,22 +343,18 @@ kh_gen_sweep_store(KhSweepArgs p, const double *__restrict__ pulses, const cplx 
             // step's readers are behind the barrier that ends its last term)
             if (tid < L) s.eps[tid] = pulses[(size_t)tid * (nt - 1) + n];
             __syncthreads();
-            matvecs += kh_gen_expm_action(p, ops_k, p.csr ? p.csr + (size_t)k * (1 + L) : nullptr, norms_k, s.eps,
-                                          p.dt[n], s);
+            matvecs += kh_gen_expm_action(p, N, fre, fim, ops_k, p.csr ? p.csr + (size_t)k * (1 + L) : nullptr, norms_k,
+                                          s.eps, p.dt[n], s);
             if (store != nullptr) {
                 const int idx = direction > 0 ? n + 1 : n;
-                for (int i = tid; i < N; i += KH_GEN_THREADS) store[((size_t)k * nt + idx) * N + i] = s.acc[i];
+                kh_gen_put<MIXED>(store + ((size_t)k * nt + idx) * NS, s.acc, N, NS);
             }
         }
-        if (state_out != nullptr)
-            for (int i = tid; i < N; i += KH_GEN_THREADS) state_out[(size_t)k * N + i] = s.acc[i];
+        if (state_out != nullptr) kh_gen_put<MIXED>(state_out + (size_t)k * NS, s.acc, N, NS);
         __syncthreads();
     }
     if (tid == 0 && p.stats != nullptr) atomicAdd(p.stats, matvecs);
 }
-#else
-    ;  // (defined in the translation unit that owns it: kh_common.h, KH_DEFINES)
-#endif
 
 // ---------------------------------------------------------------------------
 // forward sweep with sequential pulse update (optimize.py:444-508)
@@ -497,22 +516,24 @@ __device__ __forceinline__ void kh_gen_partials_adj(const KhSweepArgs &p, const 
 }
 
 // Im( mu * norm_k * <chi_k(t_n) | H_l phi_k> ) summed over this workgroup's objectives, for every control l -> s.part[l]
-// (LDS; complete behind the function's last barrier).
-__device__ __forceinline__ void kh_gen_partials(const KhSweepArgs &p, const KhUpdateArgs &u, int n,
+// (LDS; complete behind the function's last barrier).  MIXED: objective k's own dimension and mu factor.
+template <bool MIXED>
+__device__ __forceinline__ void kh_gen_partials(const KhSweepArgs &p, const KhUpdateArgs &u, const KhMixedArgs &mx, int n,
                                                 const KhGenLds &s, bool resident = false) {
-    const int tid = threadIdx.x, N = p.N, L = p.L, nt = p.nt;
+    const int tid = threadIdx.x, NS = p.N, L = p.L, nt = p.nt;
     const int grp = tid >> 4, c16 = tid & 15, wave = tid >> 6, lane = tid & 63;
     if (tid < L) s.part[tid] = 0.0;
     __syncthreads();
-    if (u.adj_store != nullptr) {
+    if (!MIXED && u.adj_store != nullptr) {
         kh_gen_partials_adj(p, u, n, s, resident);
         return;
     }
     const double zero_eps[1] = {0.0};
     for (int k = blockIdx.x; k < p.K; k += gridDim.x) {
+        const int N = MIXED ? mx.dims[k] : NS;
         for (int i = tid; i < N; i += KH_GEN_THREADS) {
-            s.xa[i] = u.phi[(size_t)k * N + i];
-            s.chi[i] = u.chi_store[((size_t)k * nt + n) * N + i];
+            s.xa[i] = u.phi[(size_t)k * NS + i];
+            s.chi[i] = u.chi_store[((size_t)k * nt + n) * NS + i];
         }
         __syncthreads();
         const double nrm = u.chi_norms[k];
@@ -529,7 +550,7 @@ __device__ __forceinline__ void kh_gen_partials(const KhSweepArgs &p, const KhUp
                     if (c16 == 0 && row < N) {
                         cplx bra = s.chi[row];
                         if (u.sigma != nullptr) {  // second order: + 0.5 sigma <phi - phi_prev | (optimize.py:469)
-                            const cplx prev = u.fw_prev[((size_t)k * nt + n) * N + row];
+                            const cplx prev = u.fw_prev[((size_t)k * nt + n) * NS + row];
                             bra.x = fma(hs, s.xa[row].x - prev.x, bra.x);
                             bra.y = fma(hs, s.xa[row].y - prev.y, bra.y);
                         }
@@ -552,16 +573,18 @@ __device__ __forceinline__ void kh_gen_partials(const KhSweepArgs &p, const KhUp
                 im += s.red[(w * KH_GEN_MAX_L + tid) * 2 + 1];
             }
             // Im(mu * ov) * norm  (optimize.py:466-467, 473)
-            s.part[tid] += nrm * (u.mu_re * im + u.mu_im * re);
+            const double mu_re = MIXED ? mx.mu[k].x : u.mu_re, mu_im = MIXED ? mx.mu[k].y : u.mu_im;
+            s.part[tid] += nrm * (mu_re * im + mu_im * re);
         }
         __syncthreads();
     }
 }
 
+// MIXED (kh_engine_create_mixed): objective k has its own dimension mx.dims[k], factor mx.f[k] and mu factor mx.mu[k];
+// the sums stay on the forward side (no adjoint-side store), the running states in global memory
+template <bool MIXED>
 __global__ void __launch_bounds__(KH_GEN_THREADS)
-kh_gen_forward_update(KhSweepArgs p, KhUpdateArgs u, KhExchange ex)
-#if KH_DEFINES(KH_TU_GENERIC)
-{
+kh_gen_forward_update(KhSweepArgs p, KhUpdateArgs u, KhExchange ex, KhMixedArgs mx) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     if (u.n_dev != nullptr) {
         u.n_begin = *u.n_dev;
@@ -571,7 +594,7 @@ kh_gen_forward_update(KhSweepArgs p, KhUpdateArgs u, KhExchange ex)
     const KhGenLds s = kh_gen_carve(smem, p.N, p.csr == nullptr);
     double *D_sh = s.D;  // all LDS in the dynamic region (keeps its base 16-byte aligned)
     int *ok_sh_p = s.ok;
-    const int tid = threadIdx.x, N = p.N, L = p.L, nt = p.nt;
+    const int tid = threadIdx.x, NS = p.N, L = p.L, nt = p.nt;
     const int wave = tid >> 6, lane = tid & 63;
     double matvecs = 0.0;
     if (tid < L) s.ga[tid] = 0.0;  // (thread l keeps control l's scalars: eps, g_a, partial sum -- all in LDS)
@@ -579,22 +602,21 @@ kh_gen_forward_update(KhSweepArgs p, KhUpdateArgs u, KhExchange ex)
     // One objective per workgroup and the sums on the adjoint side (no stage of the sweep then needs the state in global
     // memory): the running state stays in s.acc from interval to interval -- read once, written back once -- instead of
     // a global round trip in front of and behind every step.
-    const bool resident = (int)gridDim.x >= p.K && u.adj_store != nullptr;
+    const bool resident = !MIXED && (int)gridDim.x >= p.K && u.adj_store != nullptr;
     if (resident && (int)blockIdx.x < p.K) {
-        for (int i = tid; i < N; i += KH_GEN_THREADS) s.acc[i] = u.phi[(size_t)blockIdx.x * N + i];
+        for (int i = tid; i < NS; i += KH_GEN_THREADS) s.acc[i] = u.phi[(size_t)blockIdx.x * NS + i];
         __syncthreads();
     }
     // partial sums of the first interval handled by this launch
     if (u.internal_exchange || u.n_begin == u.n_end) {
         // (stepwise mode enters with the partials of n_begin already reduced in D_in,
         //  except for the begin call n_begin == n_end == 0 which only emits them)
-        if (u.n_begin < nt - 1) kh_gen_partials(p, u, u.n_begin, s, resident);
+        if (u.n_begin < nt - 1) kh_gen_partials<MIXED>(p, u, mx, u.n_begin, s, resident);
     }
     if (!u.internal_exchange && u.n_begin == u.n_end) {
         if (tid < L) u.wg_partial[(size_t)blockIdx.x * L + tid] = u.n_begin < nt - 1 ? s.part[tid] : 0.0;
         return;
     }
-
     for (int n = u.n_begin; n < u.n_end; ++n) {
         // ---- cross-objective sum D_l (optimize.py:470) ----
         if (u.internal_exchange) {
@@ -650,24 +672,23 @@ kh_gen_forward_update(KhSweepArgs p, KhUpdateArgs u, KhExchange ex)
         for (int k = blockIdx.x; k < p.K; k += gridDim.x) {
             const cplx *const *ops_k = p.ops + (size_t)k * (1 + L);
             const double *norms_k = p.op_norms + (size_t)k * (1 + L);
+            const int N = MIXED ? mx.dims[k] : NS;
+            const double fre = MIXED ? mx.f[k].x : p.fre, fim = MIXED ? mx.f[k].y : p.fim;
             if (!resident) {
-                for (int i = tid; i < N; i += KH_GEN_THREADS) s.acc[i] = u.phi[(size_t)k * N + i];
+                for (int i = tid; i < N; i += KH_GEN_THREADS) s.acc[i] = u.phi[(size_t)k * NS + i];
                 __syncthreads();
             }
-            if (u.fw_store != nullptr && n == 0)
-                for (int i = tid; i < N; i += KH_GEN_THREADS) u.fw_store[((size_t)k * nt) * N + i] = s.acc[i];
-            matvecs += kh_gen_expm_action(p, ops_k, p.csr ? p.csr + (size_t)k * (1 + L) : nullptr, norms_k, s.eps, dt,
-                                          s);
-            if (!resident || n + 1 == u.n_end)
-                for (int i = tid; i < N; i += KH_GEN_THREADS) u.phi[(size_t)k * N + i] = s.acc[i];
-            if (u.fw_store != nullptr)
-                for (int i = tid; i < N; i += KH_GEN_THREADS) u.fw_store[((size_t)k * nt + n + 1) * N + i] = s.acc[i];
+            if (u.fw_store != nullptr && n == 0) kh_gen_put<MIXED>(u.fw_store + (size_t)k * nt * NS, s.acc, N, NS);
+            matvecs += kh_gen_expm_action(p, N, fre, fim, ops_k, p.csr ? p.csr + (size_t)k * (1 + L) : nullptr, norms_k,
+                                          s.eps, dt, s);
+            if (!resident || n + 1 == u.n_end) kh_gen_put<MIXED>(u.phi + (size_t)k * NS, s.acc, N, NS);
+            if (u.fw_store != nullptr) kh_gen_put<MIXED>(u.fw_store + ((size_t)k * nt + n + 1) * NS, s.acc, N, NS);
             __syncthreads();
         }
         // ---- partial sums of the next interval ----
         if (n + 1 < nt - 1) {
             // phi written above by this same workgroup: visible after the barrier
-            kh_gen_partials(p, u, n + 1, s, resident);
+            kh_gen_partials<MIXED>(p, u, mx, n + 1, s, resident);
             matvecs += (double)L;
         }
     }
@@ -675,9 +696,6 @@ kh_gen_forward_update(KhSweepArgs p, KhUpdateArgs u, KhExchange ex)
     if (blockIdx.x == 0 && tid < L) u.g_a[tid] = (u.internal_exchange ? 0.0 : u.g_a[tid]) + s.ga[tid];
     if (tid == 0 && p.stats != nullptr) atomicAdd(p.stats, matvecs);
 }
-#else
-    ;  // (defined in the translation unit that owns it: kh_common.h, KH_DEFINES)
-#endif
 
 // sum of per-workgroup partials in workgroup order -> out[L]  (stepwise mode)
 __global__ void kh_reduce_partials(const double *__restrict__ wg_partial, int G, int L, double *__restrict__ out,

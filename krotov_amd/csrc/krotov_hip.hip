@@ -199,6 +199,9 @@ struct KhPlan {
 
 struct kh_engine {
     int K, N, L, nt, is_super;
+    // kh_engine_create_mixed: objectives of their own dimension and kind; N is then the stride max N_k of every buffer
+    bool mixed = false;
+    KhMixedArgs mixed_fw{}, mixed_bw{};  // device arrays: dims [K], f [K] per direction, mu [K] (both share dims, mu)
     double tol;
     int device, num_cus;
     KhSwitches sw;
@@ -425,10 +428,11 @@ static int check_residency(const kh_engine *e, const void *func, int threads, si
     return KH_OK;
 }
 
-extern "C" const char *kh_version(void) { return "krotov_hip 0.6 (gfx950; tile64q2, tile64, tile64/stream, tile64x, ens64/mfma, mini16, mini4, coop16/mfma, ell/csr, ellstream/csr, tile128, generic, generic/csr kernels)"; }
+extern "C" const char *kh_version(void) { return "krotov_hip 0.6 (gfx950; tile64q2, tile64, tile64/stream, tile64x, ens64/mfma, mini16, mini4, coop16/mfma, ell/csr, ellstream/csr, tile128, generic, generic/csr, generic/mixed kernels)"; }
 
 extern "C" const char *kh_engine_kernel(const kh_engine *e) {
     if (e == nullptr) return "";
+    if (e->mixed) return "generic/mixed";
     const KhPlan &p = e->plan;
     if (p.ens) return "ens64/mfma";
     switch (p.kind) {
@@ -940,14 +944,14 @@ static int stage_copies(kh_engine *e, KhCopies &copies, const std::vector<const 
 }
 
 // Operator tables: forward pointers as given, adjoints staged once per distinct operator (dense) or as the caller
-// supplies them (CSR); norms, degree table, time steps.
+// supplies them (CSR); norms, degree table, time steps.  dims: [K] each objective's own dimension (mixed engines:
+// its operators are dims[k] x dims[k]), or NULL: every operator is N x N.
 static int stage_operators(kh_engine *e, const kh_problem *pr, const kh_csr *csr_fw, const kh_csr *csr_bw,
-                           std::vector<const cplx *> &fw, std::vector<const cplx *> &bw) {
+                           std::vector<const cplx *> &fw, std::vector<const cplx *> &bw, const int32_t *dims = nullptr) {
     const size_t nops = (size_t)e->K * (1 + e->L);
     fw.assign(nops, nullptr);
     bw.assign(nops, nullptr);
     KhCopies adj;
-    const int tiles = (e->N + 31) / 32;
     for (size_t i = 0; i < nops; ++i) {
         const cplx *src = (const cplx *)pr->ops[i];
         fw[i] = src;
@@ -956,8 +960,10 @@ static int stage_operators(kh_engine *e, const kh_problem *pr, const kh_csr *csr
             bw[i] = (const cplx *)csr_bw[i].data;
             continue;
         }
-        const int rc = adj.get(e, src, nullptr, sizeof(cplx) * (size_t)e->N * e->N, [&](cplx *dst) {
-            kh_adjoint_kernel<<<dim3(tiles, tiles), 256>>>(src, dst, e->N);
+        const int n = dims != nullptr ? dims[i / (size_t)(1 + e->L)] : e->N;
+        const int tiles = (n + 31) / 32;
+        const int rc = adj.get(e, src, nullptr, sizeof(cplx) * (size_t)n * n, [&](cplx *dst) {
+            kh_adjoint_kernel<<<dim3(tiles, tiles), 256>>>(src, dst, n);
             return KH_OK;
         }, &bw[i]);
         if (rc != KH_OK) return rc;
@@ -974,7 +980,13 @@ static int stage_operators(kh_engine *e, const kh_problem *pr, const kh_csr *csr
         KH_TRY(dev_upload(e, &e->d_norms, pr->op_norms, sizeof(double) * nops));
     } else {
         KH_TRY(dev_alloc(e, &e->d_norms, sizeof(double) * nops));
-        kh_fro_norms<<<(unsigned)nops, 256>>>(e->d_ops_fw, (int)nops, e->N, e->d_norms);
+        if (dims == nullptr) {
+            kh_fro_norms<<<(unsigned)nops, 256>>>(e->d_ops_fw, (int)nops, e->N, e->d_norms);
+        } else {
+            const size_t Lp1 = 1 + e->L;
+            for (int k = 0; k < e->K; ++k)
+                kh_fro_norms<<<(unsigned)Lp1, 256>>>(e->d_ops_fw + k * Lp1, (int)Lp1, dims[k], e->d_norms + k * Lp1);
+        }
         KH_HIP(hipGetLastError());
     }
     double tab[KH_MAX_DEGREE + 1];
@@ -1251,6 +1263,8 @@ static int ens_forms(kh_engine *e, int ncg, const void *forms[2]) {
     return KH_OK;
 }
 
+static int stage_workspaces(kh_engine *e);
+
 // Everything but the validation of engine_create; on failure the caller destroys the half-built engine.
 static int engine_build(kh_engine *e, const kh_problem *pr, const kh_csr *csr_fw, const kh_csr *csr_bw) {
     KH_HIP(hipGetDevice(&e->device));
@@ -1355,7 +1369,12 @@ static int engine_build(kh_engine *e, const kh_problem *pr, const kh_csr *csr_fw
         if (rc != KH_OK) p.ens = false;
     }
 
-    // ---- workspaces
+    return stage_workspaces(e);
+}
+
+// the sweeps' workspaces (the plan's grids)
+static int stage_workspaces(kh_engine *e) {
+    const KhPlan &p = e->plan;
     const int Lx = e->L > 0 ? e->L : 1;
     const int slot_wgs = p.kind == KIND_COOP && p.coop_G * p.coop_Y > p.grid_update ? p.coop_G * p.coop_Y : p.grid_update;
     e->slots_bytes = sizeof(kh_u64) * 2 * (size_t)slot_wgs * Lx * 2;
@@ -1375,9 +1394,7 @@ static int engine_build(kh_engine *e, const kh_problem *pr, const kh_csr *csr_fw
 
 // csr_fw / csr_bw: [K*(1+L)] sparse operators and their conjugate transposes (pr->ops then holds their
 // data arrays), or both NULL for dense row-major operators
-static int engine_create(const kh_problem *pr, const kh_csr *csr_fw, const kh_csr *csr_bw, kh_engine **out) {
-    if (pr == nullptr || out == nullptr) return kh_fail(KH_ERR_INVALID, "null argument");
-    *out = nullptr;
+static int validate_problem(const kh_problem *pr) {
     if (pr->K < 1 || pr->N < 1 || pr->L < 0 || pr->nt < 2)
         return kh_fail(KH_ERR_INVALID, "bad sizes K=%d N=%d L=%d nt=%d", pr->K, pr->N, pr->L, pr->nt);
     // (the register-resident families take up to KH_MAX_L controls; with more the generic kernels run, up to KH_GEN_MAX_L)
@@ -1388,6 +1405,13 @@ static int engine_create(const kh_problem *pr, const kh_csr *csr_fw, const kh_cs
     for (int k = 0; k < pr->K; ++k)
         if (pr->ops[(size_t)k * (1 + pr->L)] == nullptr)
             return kh_fail(KH_ERR_INVALID, "objective %d has no drift operator", k);
+    return KH_OK;
+}
+
+static int engine_create(const kh_problem *pr, const kh_csr *csr_fw, const kh_csr *csr_bw, kh_engine **out) {
+    if (pr == nullptr || out == nullptr) return kh_fail(KH_ERR_INVALID, "null argument");
+    *out = nullptr;
+    KH_TRY(validate_problem(pr));
 
     kh_engine *e = new kh_engine();
     e->K = pr->K;
@@ -1440,6 +1464,78 @@ extern "C" int kh_engine_create_csr(const kh_problem_csr *pc, kh_engine **out) {
     pr.tol = pc->tol;
     pr.theta_max = pc->theta_max;
     return engine_create(&pr, pc->ops, pc->ops_adj, out);
+}
+
+// ---- mixed engines (kh_engine_create_mixed): objectives of their own dimension N_k and kind, one launch per sweep
+// The generic kernels' MIXED instantiations for every sweep; Taylor series (no real-spectrum form) and the update sums on
+// the forward side (no adjoint-side store): a first version, kept simple.
+static KhPlan plan_mixed(int K, int num_cus, double theta_max) {
+    KhPlan p;  // (kind = kind_store = KIND_GENERIC, Taylor tables)
+    p.max_wgs = max_update_wgs(num_cus);
+    p.grid_update = K < p.max_wgs ? K : p.max_wgs;
+    p.theta_max = theta_max > 0.0 ? theta_max : 1.0;
+    return p;
+}
+
+static int engine_build_mixed(kh_engine *e, const kh_problem *pr, const int32_t *dims, const int32_t *is_super) {
+    KH_HIP(hipGetDevice(&e->device));
+    hipDeviceProp_t prop;
+    KH_HIP(hipGetDeviceProperties(&prop, e->device));
+    e->num_cus = prop.multiProcessorCount;
+    const size_t gen_lds = kh_gen_lds_bytes(e->N, true);  // (carved for the stride: S <= 2540)
+    if (gen_lds > (size_t)prop.sharedMemPerBlock && gen_lds > 160 * 1024)
+        return kh_fail(KH_ERR_UNSUPPORTED, "stride N=%d needs %zu bytes of LDS", e->N, gen_lds);
+    std::vector<const cplx *> fw, bw;
+    KH_TRY(stage_operators(e, pr, nullptr, nullptr, fw, bw, dims));
+    e->plan = plan_mixed(e->K, e->num_cus, pr->theta_max);
+    e->gen_adj_failed = true;  // (the update sums stay on the forward side)
+    KH_TRY(stage_series(e));
+    // per objective: the equation-of-motion factor of each direction (propagators.py:94-99) and the mu factor (mu.py:130-134)
+    std::vector<cplx> f_fw(e->K), f_bw(e->K), mu(e->K);
+    for (int k = 0; k < e->K; ++k) {
+        const bool super = is_super[k] != 0;
+        f_fw[k] = super ? make_double2(1.0, 0.0) : make_double2(0.0, -1.0);
+        f_bw[k] = super ? make_double2(1.0, 0.0) : make_double2(0.0, 1.0);
+        mu[k] = super ? make_double2(0.0, 1.0) : make_double2(1.0, 0.0);
+    }
+    int *d_dims = nullptr;
+    cplx *d_f_fw = nullptr, *d_f_bw = nullptr, *d_mu = nullptr;
+    KH_TRY(dev_upload(e, &d_dims, dims, sizeof(int) * e->K));
+    KH_TRY(dev_upload(e, &d_f_fw, f_fw.data(), sizeof(cplx) * e->K));
+    KH_TRY(dev_upload(e, &d_f_bw, f_bw.data(), sizeof(cplx) * e->K));
+    KH_TRY(dev_upload(e, &d_mu, mu.data(), sizeof(cplx) * e->K));
+    e->mixed_fw = KhMixedArgs{d_dims, d_f_fw, d_mu};
+    e->mixed_bw = KhMixedArgs{d_dims, d_f_bw, d_mu};
+    return stage_workspaces(e);
+}
+
+extern "C" int kh_engine_create_mixed(const kh_problem *pr, const int32_t *dims, const int32_t *is_super, kh_engine **out) {
+    if (pr == nullptr || dims == nullptr || is_super == nullptr || out == nullptr)
+        return kh_fail(KH_ERR_INVALID, "null argument");
+    *out = nullptr;
+    KH_TRY(validate_problem(pr));
+    int S = 0;
+    for (int k = 0; k < pr->K; ++k) {
+        if (dims[k] < 1) return kh_fail(KH_ERR_INVALID, "dims[%d] = %d", k, dims[k]);
+        S = dims[k] > S ? dims[k] : S;
+    }
+    if (pr->N != S) return kh_fail(KH_ERR_INVALID, "problem->N = %d must be the stride max(dims) = %d", pr->N, S);
+    kh_engine *e = new kh_engine();
+    e->K = pr->K;
+    e->N = pr->N;
+    e->L = pr->L;
+    e->nt = pr->nt;
+    e->is_super = 0;  // (per objective: mixed_fw / mixed_bw)
+    e->mixed = true;
+    e->tol = pr->tol > 0.0 ? pr->tol : ldexp(1.0, -53);
+    e->sw = read_switches();
+    const int rc = engine_build_mixed(e, pr, dims, is_super);
+    if (rc != KH_OK) {
+        kh_engine_destroy(e);
+        return rc;
+    }
+    *out = e;
+    return KH_OK;
 }
 
 // ---------------------------------------------------------------------------
@@ -1737,8 +1833,13 @@ static int sweep_store(kh_engine *e, bool backward, const double *pulses, const 
             KhSweepArgs pg = p;
             pg.gen_scratch = e->d_gen_scratch;
             pg.gen_scratch_wgs = e->gen_scratch_wgs;
-            rc = launch_plain_lds<kh_gen_sweep_store>(e, dim3(grid), dim3(KH_GEN_THREADS), kh_gen_lds_bytes(e->N, e->d_csr_fw == nullptr), st, pg,
-                                                      pulses, in, store, out, direction);
+            const size_t lds = kh_gen_lds_bytes(e->N, e->d_csr_fw == nullptr);
+            if (e->mixed)
+                rc = launch_plain_lds<kh_gen_sweep_store<true>>(e, dim3(grid), dim3(KH_GEN_THREADS), lds, st, pg,
+                                                                backward ? e->mixed_bw : e->mixed_fw, pulses, in, store, out, direction);
+            else
+                rc = launch_plain_lds<kh_gen_sweep_store<false>>(e, dim3(grid), dim3(KH_GEN_THREADS), lds, st, pg, KhMixedArgs{},
+                                                                 pulses, in, store, out, direction);
         }
     }
     if (rc != KH_OK) return rc;
@@ -1936,7 +2037,7 @@ static int update_generic(kh_engine *e, const KhSweepArgs &p, const KhUpdateArgs
     if (!e->gen_fits)
         return kh_fail(KH_ERR_UNSUPPORTED, "N=%d: this form of the update sweep needs the generic kernels, whose vectors do not fit LDS", e->N);
     const size_t lds = kh_gen_lds_bytes(e->N, e->d_csr_fw == nullptr);
-    int rc = ensure_dynamic_lds(e, (const void *)kh_gen_forward_update, lds);
+    int rc = ensure_dynamic_lds(e, e->mixed ? (const void *)kh_gen_forward_update<true> : (const void *)kh_gen_forward_update<false>, lds);
     ensure_gen_scratch(e, e->plan.grid_update);
     if (rc != KH_OK) return rc;
     KhSweepArgs pg = p;
@@ -1955,11 +2056,18 @@ static int update_generic(kh_engine *e, const KhSweepArgs &p, const KhUpdateArgs
     }
     if (e->gen_adj_ready && u.sigma == nullptr) ug.adj_store = e->d_gen_adj;
     const dim3 g(e->plan.grid_update), b(KH_GEN_THREADS);
+    if (e->mixed) {  // (mixed engines: the sums on the forward side -- gen_adj_failed is set at creation)
+        if (!ug.internal_exchange) {
+            launch_plain<kh_gen_forward_update<true>>(g, b, lds, st, pg, ug, ex, e->mixed_fw);
+            return KH_OK;
+        }
+        return launch_persistent<kh_gen_forward_update<true>>(e, g, b, lds, st, pg, ug, ex, e->mixed_fw);
+    }
     if (!ug.internal_exchange) {
-        launch_plain<kh_gen_forward_update>(g, b, lds, st, pg, ug, ex);
+        launch_plain<kh_gen_forward_update<false>>(g, b, lds, st, pg, ug, ex, KhMixedArgs{});
         return KH_OK;
     }
-    return launch_persistent<kh_gen_forward_update>(e, g, b, lds, st, pg, ug, ex);
+    return launch_persistent<kh_gen_forward_update<false>>(e, g, b, lds, st, pg, ug, ex, KhMixedArgs{});
 }
 
 // five to eight controls, N <= 64, one resident workgroup per objective, first order: the register-tile form with
@@ -2238,6 +2346,7 @@ __global__ void kh_p2p_selftest_kernel(KhExchange ex, int L, int rounds, unsigne
 extern "C" int kh_p2p_create_window(kh_engine *e, int32_t world, int32_t rank, unsigned char *ipc_handle_out) {
     if (e == nullptr || ipc_handle_out == nullptr) return kh_fail(KH_ERR_INVALID, "null argument");
     if (world < 1 || rank < 0 || rank >= world) return kh_fail(KH_ERR_INVALID, "bad world/rank %d/%d", rank, world);
+    if (e->mixed) return kh_fail(KH_ERR_UNSUPPORTED, "mixed engines (kh_engine_create_mixed) are not sharded");
     const int Lx = e->L > 0 ? e->L : 1;
     if (world * Lx * 2 > 64 || Lx > KH_MAX_L)
         return kh_fail(KH_ERR_UNSUPPORTED, "world * L = %d exceeds the 32 exchange lanes (or more than %d controls)", world * Lx, KH_MAX_L);

@@ -49,7 +49,14 @@ class HipKrotovEngine:
             objective.  Entries that are the *same object* are uploaded once
             and shared on the device.
         dt: (nt-1,) interval lengths.
-        is_super: operators are Liouvillians acting on column-stacked vec(rho).
+        is_super: operators are Liouvillians acting on column-stacked vec(rho); a bool, or one bool per objective.
+
+    Objectives may differ in dimension (every operator of objective k is N_k x N_k) and in kind (``is_super`` per
+    objective).  Then the engine is a *mixed* one (``kh_engine_create_mixed``, kernel family ``"generic/mixed"``):
+    ``dims`` lists N_k, ``N`` is the stride max N_k of every (K, N) / (K, nt, N) array the sweeps take and return,
+    objective k uses the first N_k entries of its rows and the engine writes zeros behind them (see
+    :func:`krotov_amd.mixed.layout`).  Dense operators only.  When every objective has the same dimension and kind the
+    engine is the uniform one, as before.
         op_norms: optional (K, 1+L) spectral-norm bounds; computed on the host
             with ``numpy.linalg.norm(., 2)`` per distinct operator when omitted.
         device: torch device (default: current CUDA/HIP device).
@@ -61,18 +68,29 @@ class HipKrotovEngine:
         self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
         self.K = len(ops)
         self.L = len(ops[0]) - 1
-        self.is_super = bool(is_super)
+        kinds = [bool(x) for x in is_super] if isinstance(is_super, (list, tuple, np.ndarray)) else [bool(is_super)] * self.K
+        if len(kinds) != self.K:
+            raise ValueError("is_super: %d entries for %d objectives" % (len(kinds), self.K))
         dt = np.ascontiguousarray(np.asarray(dt, dtype=np.float64))
         self.nt = len(dt) + 1
         self._dt = dt
         self._handle = ctypes.c_void_p()
         self._op_tensors = {}
-        self.N = None
         for k, row in enumerate(ops):
             if len(row) != 1 + self.L:
                 raise ValueError("objective %d has %d operators, expected %d" % (k, len(row), 1 + self.L))
+        dims = self._dims_of(ops)
+        self.mixed = len(set(dims)) > 1 or len(set(kinds)) > 1
+        self.dims = dims
+        self.kinds = kinds
+        self.N = max(dims)
+        self.is_super = kinds if self.mixed else kinds[0]
+        sparse = any(_is_sparse(op) for row in ops for op in row)
+        if self.mixed and sparse:
+            raise ValueError("objectives of different dimension or kind need dense operators: "
+                             "sparse (CSR) operators take one dimension and one kind for all objectives")
         with torch.cuda.device(self.device):
-            if any(_is_sparse(op) for row in ops for op in row):
+            if sparse:
                 norms = self._create_sparse(ops, dt, op_norms, tol, theta_max)
             else:
                 norms = self._create_dense(ops, dt, op_norms, tol, theta_max)
@@ -84,13 +102,30 @@ class HipKrotovEngine:
         global _last_engine
         _last_engine = self
 
+    @staticmethod
+    def _dims_of(ops):
+        """N_k of every objective: the size of its operators, which must all agree."""
+        dims = []
+        for k, row in enumerate(ops):
+            n = None
+            for op in row:
+                if op is None:
+                    continue
+                shape = tuple(op.shape) if hasattr(op, 'shape') else np.shape(op)
+                if len(shape) != 2 or shape[0] != shape[1]:
+                    raise ValueError("operators must be square matrices")
+                if n is None:
+                    n = shape[0]
+                elif shape[0] != n:
+                    raise ValueError("objective %d: all its operators must have the same dimension" % k)
+            if n is None:
+                raise ValueError("objective %d has no operators" % k)
+            dims.append(int(n))
+        return dims
+
     def _check_dim(self, shape):
         if len(shape) != 2 or shape[0] != shape[1]:
             raise ValueError("operators must be square matrices")
-        if self.N is None:
-            self.N = shape[0]
-        elif shape[0] != self.N:
-            raise ValueError("all operators must have the same dimension")
 
     def _norms(self, norms, op_norms):
         if op_norms is not None:
@@ -124,13 +159,18 @@ class HipKrotovEngine:
         norms = self._norms(norms, op_norms)
         pr = _lib.kh_problem()
         pr.K, pr.N, pr.L, pr.nt = self.K, self.N, self.L, self.nt
-        pr.is_super = 1 if self.is_super else 0
+        pr.is_super = 1 if (not self.mixed and self.is_super) else 0
         pr.dt = dt.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
         pr.ops = ctypes.cast(ptrs, ctypes.POINTER(ctypes.c_void_p))
         pr.op_norms = norms.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
         pr.tol = float(tol)
         pr.theta_max = float(theta_max)
-        _lib.check(self._lib.kh_engine_create(ctypes.byref(pr), ctypes.byref(self._handle)))
+        if self.mixed:
+            dims = (ctypes.c_int32 * self.K)(*self.dims)
+            kinds = (ctypes.c_int32 * self.K)(*[1 if x else 0 for x in self.kinds])
+            _lib.check(self._lib.kh_engine_create_mixed(ctypes.byref(pr), dims, kinds, ctypes.byref(self._handle)))
+        else:
+            _lib.check(self._lib.kh_engine_create(ctypes.byref(pr), ctypes.byref(self._handle)))
         return norms
 
     def _create_sparse(self, ops, dt, op_norms, tol, theta_max):
@@ -180,7 +220,7 @@ class HipKrotovEngine:
         norms = self._norms(norms, op_norms)
         pr = _lib.kh_problem_csr()
         pr.K, pr.N, pr.L, pr.nt = self.K, self.N, self.L, self.nt
-        pr.is_super = 1 if self.is_super else 0
+        pr.is_super = 1 if self.is_super else 0  # (never mixed: refused above)
         pr.dt = dt.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
         pr.ops = fw
         pr.ops_adj = bw

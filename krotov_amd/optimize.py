@@ -35,7 +35,7 @@ from functools import partial
 import numpy as np
 
 from . import functionals as _functionals
-from ._ingest import obj_type, state_array, state_to_vector, to_dense, to_sparse, vector_to_state
+from ._ingest import state_to_vector, to_dense, to_sparse, vector_to_state
 from .conversions import (
     control_onto_interval,
     discretize,
@@ -51,6 +51,7 @@ from ._lib import KH_ERR_TIMEOUT as _KH_ERR_TIMEOUT, KH_ERR_UNSUPPORTED as _KH_E
 _KH_MAX_CONTROLS = 32  # KH_GEN_MAX_L of krotov_amd/csrc/kh_common.h (the register-resident kernel families: 8)
 _FULL_GRID_PROBE_EVERY = 16  # update sweeps in a row on a reduced grid before the full one is tried again
 from .info_hooks import chain
+from .mixed import layout_of
 from .mu import derivative_wrt_pulse
 from .parallelization import serial_map
 from .propagators import HipExpm, Propagator, expm
@@ -309,10 +310,11 @@ class _LazyStates:
     host, or still on the device and fetched on first access (``fetch``);
     elements are converted to the caller's state type on access."""
 
-    def __init__(self, array, likes, fetch=None):
+    def __init__(self, array, likes, fetch=None, layout=None):
         self._host = array
         self._fetch = fetch
         self._likes = likes
+        self._layout = layout  # (mixed objective lists: rows at the stride, sliced back to N_k)
 
     @property
     def _array(self):
@@ -327,6 +329,8 @@ class _LazyStates:
     def __getitem__(self, k):
         if isinstance(k, slice):
             return [self[i] for i in range(*k.indices(len(self)))]
+        if self._layout is not None:
+            return self._layout.state(self._array[k], k, self._likes[k])
         return vector_to_state(self._array[k], self._likes[k])
 
     def __iter__(self):
@@ -357,10 +361,10 @@ class _DeviceTrajectory:
         n %= nt
         like = o._likes[k]
         if n == nt - 1 and o._final is not None:
-            return vector_to_state(o._final[k], like)
+            return o._state(o._final[k], k, like)
         if not o._k0 <= k < o._k0 + o._t.shape[0]:
             raise IndexError("objective %d lives on another rank; only its final state is available here" % k)
-        return vector_to_state(o._t[k - o._k0, n].cpu().numpy(), like)
+        return o._state(o._t[k - o._k0, n].cpu().numpy(), k, like)
 
     def __iter__(self):
         return (self[n] for n in range(len(self)))
@@ -371,8 +375,14 @@ class _DeviceTrajectories:
     ``sigma.refresh``: (K_loc, nt, N) in HBM, fetched on access.  ``final``: the
     states at T of all objectives of all ranks on the host, if known."""
 
-    def __init__(self, tensor, likes, k0=0, final=None):
+    def __init__(self, tensor, likes, k0=0, final=None, layout=None):
         self._t, self._likes, self._k0, self._final = tensor, likes, k0, final
+        self._layout = layout  # (mixed objective lists: rows at the stride, sliced back to N_k)
+
+    def _state(self, row, k, like):
+        if self._layout is not None:
+            return self._layout.state(row, k, like)
+        return vector_to_state(row, like)
 
     def __len__(self):
         return len(self._likes) if self._final is not None else self._t.shape[0]
@@ -430,6 +440,10 @@ class _HipBackend:
             # the same error on EVERY rank, before any collective (a lone raising rank would leave the
             # others hanging in the first all-gather)
             raise ValueError("%d objectives cannot be sharded over %d ranks" % (K_total, self.world))
+        # every objective's dimension and kind (Hilbert / Liouville), decided per objective over the whole list (the
+        # same on every rank)
+        layout = layout_of(objectives, propagator)
+        self.layout = layout if layout.mixed else None
         self.K_total = K_total
         L = n_controls
         dense = {}
@@ -460,44 +474,31 @@ class _HipBackend:
                 sums[key] = (total, terms)
             return sums[key][0]
 
-        liouville = None
-        for p in props:
-            if isinstance(p, HipExpm) and p.liouville is not None:
-                liouville = bool(p.liouville)
-        ops, first_op = [], None
+        ops = []
         for k in range(self.k0, self.k1):
             obj = objectives[k]
             H = obj.H if isinstance(obj.H, list) else [obj.H]
             drift = [t for t in H if not isinstance(t, list)]
-            if len(drift) == 0:
-                raise ValueError("objective %d has no drift term in H" % k)
-            if first_op is None:
-                first_op = drift[0]
             row = [summed(drift)]
             for l in range(L):
                 where = pulses_mapping[k][0][l]
                 row.append(summed([H[i][0] for i in where]) if len(where) else None)
             ops.append(row)
-        N = ops[0][0].shape[0]
-        if liouville is None:
-            if obj_type(first_op) is not None:
-                liouville = obj_type(first_op) == 'super'
-            else:
-                s0 = state_array(objectives[self.k0].initial_state)
-                liouville = bool(s0.ndim == 2 and s0.shape[0] == s0.shape[1] and s0.shape[0] > 1 and s0.size == N)
-        self.is_super = liouville
+        N = layout.stride
+        self.is_super = layout.kinds[self.k0:self.k1] if layout.mixed else layout.kinds[self.k0]
         self.N, self.L = N, L
         tlist = np.asarray(tlist, dtype=np.float64)
         self.engine = HipKrotovEngine(ops, np.diff(tlist), is_super=self.is_super)
         self.nt = len(tlist)
         self.tlist_host = tlist
         self.likes = [obj.initial_state for obj in objectives]
-        init = [state_to_vector(obj.initial_state, N, self.is_super) for obj in objectives[self.k0:self.k1]]
+        init = [layout.vector(objectives[k].initial_state, k) for k in range(self.k0, self.k1)]
         if any(v is None for v in init):
-            raise ValueError("initial states do not match the operator dimension %d" % N)
+            raise ValueError("initial states do not match the operator dimension %s" % (
+                N if not layout.mixed else "of their objective (%s)" % layout.dims))
         self.init_host = np.array(init)
         self.init = self.engine.dev(self.init_host, torch.complex128)
-        tg = [state_to_vector(obj.target, N, self.is_super) for obj in objectives]
+        tg = [layout.vector(obj.target, k) for k, obj in enumerate(objectives)]
         self.targets_host = None if any(v is None for v in tg) else np.array(tg)
         self.targets = (
             None if self.targets_host is None
@@ -541,6 +542,12 @@ class _HipBackend:
             return self._cached_upload('pulses', host)
         return self.engine.dev(host, self.torch.float64)
 
+    def state_vector(self, state, k):
+        """``state`` of objective k as the engine's row (zero-padded to the stride on mixed lists), or None."""
+        if self.layout is not None:
+            return self.layout.vector(state, k)
+        return state_to_vector(state, self.N, self.is_super)
+
     def _gather_rows(self, local):
         """(K_loc, ...) host array on every rank -> (K_total, ...) on every rank."""
         return gather_rows(local, self.K_total, self.world, self.group, self.engine.device)
@@ -553,7 +560,8 @@ class _HipBackend:
             self.fw_T_dev = self.engine.forward(self._pulses(pulses), self.init)
         fw_states_T = self._final_states(self.fw_T_dev)
         if store:
-            forward_states = _DeviceTrajectories(self.fw_prev, self.likes, self.k0, final=fw_states_T._array)
+            forward_states = _DeviceTrajectories(self.fw_prev, self.likes, self.k0, final=fw_states_T._array,
+                                                 layout=self.layout)
         return fw_states_T, forward_states
 
     def tau_vals(self, fw_states_T):
@@ -567,7 +575,7 @@ class _HipBackend:
         collective), else left on the device until somebody looks at them."""
         if self.world > 1:
             return _LazyStates(self._gather_rows(psi_T.cpu().numpy()), self.likes)
-        return _LazyStates(None, self.likes, fetch=lambda: psi_T.cpu().numpy())
+        return _LazyStates(None, self.likes, fetch=lambda: psi_T.cpu().numpy(), layout=self.layout)
 
     def chi_host(self):
         """Normalised chi_k(T) and their norms of the last iteration, all objectives, on
@@ -720,10 +728,11 @@ class _HipBackend:
         opt_host = opt.cpu().numpy()
         self.__dict__.setdefault('_uploads', {})['pulses'] = (opt_host.copy(), opt)  # (the next iteration's guess, if unchanged)
         optimized = [opt_host[l].copy() for l in range(self.L)]
-        backward_states = _DeviceTrajectories(self.chi_store, self.likes, self.k0)
+        backward_states = _DeviceTrajectories(self.chi_store, self.likes, self.k0, layout=self.layout)
         forward_states = None
         if sigma is not None:
-            forward_states = _DeviceTrajectories(self.fw_next, self.likes, self.k0, final=fw_states_T._array)
+            forward_states = _DeviceTrajectories(self.fw_next, self.likes, self.k0, final=fw_states_T._array,
+                                                 layout=self.layout)
         return backward_states, optimized, fw_states_T, g_a.cpu().numpy(), forward_states
 
     def advance_second_order(self):
@@ -790,6 +799,10 @@ def optimize_pulses(
     device_path = _use_device_path(propagator, mu, overlap, sigma, storage, objectives)
     if process_group is not None and not device_path:
         raise ValueError("process_group requires the device path (propagator=krotov_amd.propagators.expm)")
+    if process_group is not None and layout_of(objectives, propagator).mixed:
+        # (host-only, the same verdict on every rank, before any collective)
+        raise ValueError("objectives of different dimension or kind run on one GPU: process_group= (sharding) is "
+                         "not supported for them")
     if mu is None:
         mu = derivative_wrt_pulse
     default_norm = norm is None
@@ -923,7 +936,7 @@ def optimize_pulses(
             chi_norms = [norm(chi) for chi in chi_states]
             chi_states = [chi / nrm for chi, nrm in zip(chi_states, chi_norms)]
             if device_path:
-                vecs = [state_to_vector(c, backend.N, backend.is_super) for c in chi_states]
+                vecs = [backend.state_vector(c, k) for k, c in enumerate(chi_states)]
                 if any(v is None for v in vecs):
                     raise ValueError("chi_constructor returned states that do not match the state dimension")
                 chi_T = np.array(vecs)
@@ -977,7 +990,7 @@ def optimize_pulses(
         if second_order:
             if chi_states is None:  # co-states formed on the device, in the caller's state type
                 chi_T, chi_norms = backend.chi_host()
-                chi_states = _LazyStates(chi_T, backend.likes)
+                chi_states = _LazyStates(chi_T, backend.likes, layout=backend.layout)
             sigma.refresh(
                 forward_states=forward_states, forward_states0=forward_states0, chi_states=chi_states,
                 chi_norms=chi_norms, optimized_pulses=optimized_pulses, guess_pulses=guess_pulses,
