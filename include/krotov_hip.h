@@ -144,7 +144,35 @@ int kh_engine_create_csr(const kh_problem_csr *problem, kh_engine **out);
  * KH_ERR_UNSUPPORTED.  KH_ERR_UNSUPPORTED for S > 2540 (the generic kernels' LDS) and more than 32 controls. */
 int kh_engine_create_mixed(const kh_problem *problem, const int32_t *dims, const int32_t *is_super, kh_engine **out);
 
-/* Which kernel family the engine selected: "tile64q2/512", "tile64/512", "tile64/256", "tile64/stream" (more objectives
+/* Density matrices under a d x d Hamiltonian and Lindblad operators -- the second way the reference writes an open
+ * system (Objective.H = [H0, [H1, eps], ...], Objective.c_ops = [C_1, ...]; docs/10_howto.rst, mu.py:106-117) -- in
+ * MATRIX form: d/dt rho = A rho + rho B + sum_j C_j rho C_j^+ with A = -i H(eps) - M/2, B = +i H(eps) - M/2,
+ * M = sum_j C_j^+ C_j; the d^2 x d^2 Liouvillian is never built (kh_engine_kernel: "lindblad/matrix").  The engine
+ * reports N = d*d and every entry point keeps its documented buffer shapes ([K][N], [K][nt][N], states column-stacked
+ * vec(rho)); results equal, to rounding, those of kh_engine_create on liouvillian(H, c_ops) with is_super = 1 (the
+ * reference ships no propagator that takes c_ops, and its default mu on such an objective is the bare H_l: the
+ * Liouvillian form is its own recommended equivalent, and what this engine reproduces -- update sums
+ * tr(chi^+ (H_l rho - rho H_l))).
+ *   ops      [K*(1+L)]        host array of dev pointers: d x d row-major Hamiltonian parts (drift, then per control;
+ *                             NULL: the control does not occur in the objective)
+ *   c_ops    [K*n_c]          host array of dev pointers: d x d row-major Lindblad operators (NULL: absent); may be
+ *                             NULL when n_c = 0
+ *   op_norms [K*(1+L+n_c)]    host: spectral-norm bounds of (H0, H_1..H_L, C_1..C_nc) per objective, or NULL (Frobenius)
+ * Limits: d <= 32, n_c <= 4, L <= 4 (KH_ERR_UNSUPPORTED beyond: build the Liouvillian and use kh_engine_create).
+ * First-order update in one launch on one GPU: kh_set_second_order (non-NULL arguments), kh_set_update_workgroups
+ * (> 0), kh_p2p_create_window and kh_update_begin / _step / _step_dev / _end answer KH_ERR_UNSUPPORTED.
+ * kh_last_stats counts one product per series term. */
+typedef struct kh_problem_lindblad {
+    int32_t K, d, L, nt, n_c, reserved;
+    const double *dt;                  /* host [nt-1] */
+    const kh_cdouble *const *ops;      /* host [K*(1+L)] */
+    const kh_cdouble *const *c_ops;    /* host [K*n_c] */
+    const double *op_norms;            /* host [K*(1+L+n_c)] or NULL */
+    double tol, theta_max;             /* as in kh_problem */
+} kh_problem_lindblad;
+int kh_engine_create_lindblad(const kh_problem_lindblad *problem, kh_engine **out);
+
+/* Which kernel family the engine selected: "lindblad/matrix" (kh_engine_create_lindblad), "tile64q2/512", "tile64/512", "tile64/256", "tile64/stream" (more objectives
  * than stay co-resident: one launch, the operators streamed; KH_NO_STREAM=1: "tile64/512 per interval"), "mini16/wave", "mini4/wave", "coop16/mfma", "tile128/512" (per-objective operators, 64 < N <= 128), "ell/csr"
  * (sparse operators with the matrix in registers), "generic", "generic/csr" or "generic/mixed" (kh_engine_create_mixed). */
 const char *kh_engine_kernel(const kh_engine *engine);

@@ -61,6 +61,23 @@ class kh_problem_csr(ctypes.Structure):
     ]
 
 
+class kh_problem_lindblad(ctypes.Structure):
+    _fields_ = [
+        ('K', ctypes.c_int32),
+        ('d', ctypes.c_int32),
+        ('L', ctypes.c_int32),
+        ('nt', ctypes.c_int32),
+        ('n_c', ctypes.c_int32),
+        ('reserved', ctypes.c_int32),
+        ('dt', ctypes.POINTER(ctypes.c_double)),
+        ('ops', ctypes.POINTER(ctypes.c_void_p)),
+        ('c_ops', ctypes.POINTER(ctypes.c_void_p)),
+        ('op_norms', ctypes.POINTER(ctypes.c_double)),
+        ('tol', ctypes.c_double),
+        ('theta_max', ctypes.c_double),
+    ]
+
+
 # every symbol include/krotov_hip.h declares: name -> (restype, argtypes)
 _P = ctypes.c_void_p
 SYMBOLS = {
@@ -70,6 +87,7 @@ SYMBOLS = {
     'kh_engine_create_csr': (ctypes.c_int, [ctypes.POINTER(kh_problem_csr), ctypes.POINTER(_P)]),
     'kh_engine_create_mixed': (ctypes.c_int, [ctypes.POINTER(kh_problem), ctypes.POINTER(ctypes.c_int32),
                                               ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_P)]),
+    'kh_engine_create_lindblad': (ctypes.c_int, [ctypes.POINTER(kh_problem_lindblad), ctypes.POINTER(_P)]),
     'kh_engine_destroy': (None, [_P]),
     'kh_engine_kernel': (ctypes.c_char_p, [_P]),
     'kh_forward_store': (ctypes.c_int, [_P, _P, _P, _P, _P, _P]),

@@ -25,6 +25,9 @@ __all__ = [
     'mixed_to_objectives',
     'spec_to_objectives',
     'liouvillian_dense',
+    'LindbladSpec',
+    'config_c4_lindblad',
+    'config_sparse_lindblad_form',
     'herm',
 ]
 
@@ -205,11 +208,54 @@ def config_c3(nt=2001):
 # --------------------------------------------------------------------------
 
 
-def config_c4(d=20, nt=1001, n_logical=4, gamma=1e-3):
+class LindbladSpec:
+    """A control problem in Lindblad form (plain arrays): ``H0``, ``H1`` (d, d) Hamiltonian parts shared by all
+    objectives, ``c_ops`` list of (d, d) Lindblad operators, ``init`` / ``target`` (K, d, d) density matrices, and
+    ``tlist``, ``controls``, ``update_shape``, ``lambda_a``, ``chi`` as in :class:`ProblemSpec`."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+        self.K, self.d, self.L = len(self.init), self.H0.shape[0], len(self.controls)
+
+    def objectives(self, krotov_module):
+        """``(objectives, pulse_options)`` with ``H = [H0, [H1, control]]`` and ``c_ops`` (shared objects)."""
+        H = [self.H0, [self.H1, self.controls[0]]]
+        objs = [krotov_module.Objective(initial_state=self.init[k], target=self.target[k], H=H, c_ops=list(self.c_ops))
+                for k in range(self.K)]
+        return objs, {self.controls[0]: dict(lambda_a=self.lambda_a, update_shape=self.update_shape)}
+
+
+def _unvec(v, d):
+    return np.asarray(v).reshape(d, d, order='F').copy()
+
+
+def _lindblad_form(spec, H0, H1, c_ops):
+    """The Lindblad-form twin of a Liouville-space spec built from the d x d operators ``H0``, ``H1``, ``c_ops``."""
+    d = H0.shape[0]
+    return LindbladSpec(
+        name=spec.name + '_lindblad_form', H0=H0, H1=H1, c_ops=list(c_ops),
+        init=np.array([_unvec(v, d) for v in spec.init]), target=np.array([_unvec(v, d) for v in spec.target]),
+        tlist=spec.tlist, controls=spec.controls, update_shape=spec.update_shape, lambda_a=spec.lambda_a, chi=spec.chi)
+
+
+def config_c4_lindblad(d=20, nt=1001, n_logical=4, gamma=1e-3):
+    """:func:`config_c4` in Lindblad form: the d x d transmon Hamiltonian parts and the decay operator the Liouvillians
+    of ``config_c4`` are built from (``liouvillian_dense(H0, c_ops)`` is its ``H0[0]`` bit for bit), d x d initial and
+    target density matrices."""
+    return config_c4(d, nt, n_logical, gamma, lindblad_form=True)
+
+
+def config_sparse_lindblad_form(d=12, nt=61, K=3, gamma=0.05):
+    """:func:`config_sparse_lindblad` in Lindblad form (see :func:`config_c4_lindblad`)."""
+    return config_sparse_lindblad(d, nt, K, gamma, lindblad_form=True)
+
+
+def config_c4(d=20, nt=1001, n_logical=4, gamma=1e-3, lindblad_form=False):
     """Transmon of tests/transmon_xgate_system_mod.py:18-27 (reference) with
     ``d`` charge states, one lowering-type decay operator in the eigenbasis,
     Liouvillian of dimension d^2, K = n_logical^2 density-matrix objectives
-    ('full' set, objectives.py:971-981) sharing one operator list."""
+    ('full' set, objectives.py:971-981) sharing one operator list.  ``lindblad_form``: the same problem as a
+    :class:`LindbladSpec` (:func:`config_c4_lindblad`)."""
     Ec, EjEc, ng, T = 0.386, 45, 0.0, 10.0
     Ej = EjEc * Ec
     n = np.arange(-(d // 2), d - d // 2)
@@ -240,13 +286,14 @@ def config_c4(d=20, nt=1001, n_logical=4, gamma=1e-3):
     init = np.array([_vec(np.outer(pi, pj.conj())) for pi in basis for pj in basis])
     target = np.array([_vec(np.outer(pi, pj.conj())) for pi in mapped for pj in mapped])
     K = n_logical * n_logical
-    return ProblemSpec(
+    spec = ProblemSpec(
         name='c4_transmon_liouville_d%d' % d,
         H0=[L0] * K, Hc=[[L1]] * K, is_super=True,
         init=init, target=target,
         tlist=np.linspace(0, T, nt), controls=[guess], update_shape=S,
         lambda_a=1.0, chi='re',
     )
+    return _lindblad_form(spec, H0, H1, [C]) if lindblad_form else spec
 
 
 def config_shared(K=20, N=96, nt=21, L=2, seed=3):
@@ -278,7 +325,7 @@ def config_shared(K=20, N=96, nt=21, L=2, seed=3):
     )
 
 
-def config_sparse_lindblad(d=12, nt=61, K=3, gamma=0.05):
+def config_sparse_lindblad(d=12, nt=61, K=3, gamma=0.05, lindblad_form=False):
     """A driven, damped d-level ladder in Liouville space: nearest-neighbour
     hopping + anharmonic levels, decay through the lowering operator, control on
     the level energies.  The Liouvillians (dimension d^2) have a handful of
@@ -303,10 +350,11 @@ def config_sparse_lindblad(d=12, nt=61, K=3, gamma=0.05):
     basis = np.eye(d, dtype=np.complex128)
     init = np.array([_vec(np.outer(basis[j], basis[j].conj())) for j in range(K)])
     target = np.array([_vec(np.outer(basis[(j + 1) % d], basis[(j + 1) % d].conj())) for j in range(K)])
-    return ProblemSpec(
+    spec = ProblemSpec(
         name='sparse_lindblad_d%d' % d, H0=[L0] * K, Hc=[[L1]] * K, is_super=True, init=init, target=target,
         tlist=np.linspace(0, T, nt), controls=[guess], update_shape=S, lambda_a=2.0, chi='re',
     )
+    return _lindblad_form(spec, H0, H1, [C.astype(np.complex128)]) if lindblad_form else spec
 
 
 def sparse_ops(spec):

@@ -25,6 +25,8 @@
 #include "kh_ens.h"
 #elif KH_TU == KH_TU_TILEN
 #include "kh_tilen.h"
+#elif KH_TU == KH_TU_LIND
+#include "kh_lind.h"
 #elif KH_TU == KH_TU_COOP_STORE || KH_TU == KH_TU_COOP_UPDATE_A || KH_TU == KH_TU_COOP_UPDATE_B
 #include "kh_coop.h"
 #elif KH_TU == KH_TU_ELL_STORE || KH_TU == KH_TU_ELL_UPDATE_A || KH_TU == KH_TU_ELL_UPDATE_B

@@ -38,6 +38,7 @@
 #include "kh_ell.h"
 #include "kh_tilen.h"
 #include "kh_ens.h"
+#include "kh_lind.h"
 // the parallel build (krotov_amd/build.py, -DKH_TU=KH_TU_MAIN): the sweep kernels are instantiated in the family units
 // (kh_tu.hip), here they are `extern template`; compiled by itself this file is the whole library in one unit
 #include "kh_instances.inc"
@@ -69,7 +70,7 @@ static int kh_fail(int code, const char *fmt, ...) {
                            __FILE__, __LINE__);                                               \
     } while (0)
 
-enum KernelKind { KIND_GENERIC = 0, KIND_TILE_RPT2 = 1, KIND_TILE_RPT1 = 2, KIND_TILE_Q2 = 3, KIND_COOP = 4, KIND_ELL = 5, KIND_TILEN = 6, KIND_TILEX = 7 /* plain sweeps only: kind_store */ };
+enum KernelKind { KIND_GENERIC = 0, KIND_TILE_RPT2 = 1, KIND_TILE_RPT1 = 2, KIND_TILE_Q2 = 3, KIND_COOP = 4, KIND_ELL = 5, KIND_TILEN = 6, KIND_TILEX = 7 /* plain sweeps only: kind_store */, KIND_LIND = 8 /* kh_engine_create_lindblad */ };
 
 // Switches, read from the environment ONCE, at creation (read_switches; not per launch, not per process: engines with
 // different settings coexist)
@@ -154,6 +155,7 @@ struct KhFacts {
     double imag_defect = -1.0;   // >= 0: bound on the Hermitian part of f A dt when the controls' f H_l are exactly
                                  // anti-Hermitian (|| . ||_F of the drift's part x max dt); < 0: not of that kind
     double theta_max;            // as given (<= 0: the families' own default)
+    bool lind = false;           // kh_engine_create_lindblad: d x d operators and Lindblad operators, matrix form (kh_lind.h)
 };
 
 // Which kernel families an engine runs, with every instantiation parameter (plan_families).  Two residency checks after
@@ -201,6 +203,9 @@ struct kh_engine {
     int K, N, L, nt, is_super;
     // kh_engine_create_mixed: objectives of their own dimension and kind; N is then the stride max N_k of every buffer
     bool mixed = false;
+    // kh_engine_create_lindblad: d x d Hamiltonians in d_ops_fw / d_ops_bw, the Lindblad operators and A0, B0 per direction
+    bool lind = false;
+    KhLindArgs lind_fw{}, lind_bw{};
     KhMixedArgs mixed_fw{}, mixed_bw{};  // device arrays: dims [K], f [K] per direction, mu [K] (both share dims, mu)
     double tol;
     int device, num_cus;
@@ -428,12 +433,13 @@ static int check_residency(const kh_engine *e, const void *func, int threads, si
     return KH_OK;
 }
 
-extern "C" const char *kh_version(void) { return "krotov_hip 0.6 (gfx950; tile64q2, tile64, tile64/stream, tile64x, ens64/mfma, mini16, mini4, coop16/mfma, ell/csr, ellstream/csr, tile128, generic, generic/csr, generic/mixed kernels)"; }
+extern "C" const char *kh_version(void) { return "krotov_hip 0.6 (gfx950; tile64q2, tile64, tile64/stream, tile64x, ens64/mfma, mini16, mini4, coop16/mfma, ell/csr, ellstream/csr, tile128, generic, generic/csr, generic/mixed, lindblad/matrix kernels)"; }
 
 extern "C" const char *kh_engine_kernel(const kh_engine *e) {
     if (e == nullptr) return "";
     if (e->mixed) return "generic/mixed";
     const KhPlan &p = e->plan;
+    if (p.kind == KIND_LIND) return "lindblad/matrix";
     if (p.ens) return "ens64/mfma";
     switch (p.kind) {
         case KIND_TILE_RPT2: return "tile64/256";
@@ -722,6 +728,12 @@ static KhPlan plan_families(const KhFacts &f, const KhSwitches &sw) {
     p.max_wgs = max_wgs;
     p.grid_update = K < max_wgs ? K : max_wgs;
     p.theta_max = theta_given ? f.theta_max : 1.0;
+    if (f.lind) {
+        // Lindblad form (kh_lind.h): one family for every sweep, one workgroup per objective, objectives in turns beyond
+        // the grid; Taylor tables, theta <= 1 per sub-step (a term costs no grid-wide round here)
+        p.kind = p.kind_store = KIND_LIND;
+        return p;
+    }
     p.ell_stream = f.ell_stream;
     p.ell_E = f.ell_E;
     const bool tile_shape = dense && N <= KH_TILE_N && L >= 1 && L <= 4;
@@ -1538,6 +1550,134 @@ extern "C" int kh_engine_create_mixed(const kh_problem *pr, const int32_t *dims,
     return KH_OK;
 }
 
+// ---- Lindblad-form engines (kh_engine_create_lindblad): d x d Hamiltonians and Lindblad operators, kh_lind.h
+static int lind_host_norm(const cplx *dev, int d, std::map<const void *, double> &cache, double *out) {
+    auto it = cache.find(dev);
+    if (it == cache.end()) {
+        std::vector<cplx> h((size_t)d * d);
+        KH_HIP(hipMemcpy(h.data(), dev, sizeof(cplx) * h.size(), hipMemcpyDeviceToHost));
+        double acc = 0.0;
+        for (const cplx &v : h) acc += v.x * v.x + v.y * v.y;
+        it = cache.emplace(dev, sqrt(acc)).first;
+    }
+    *out = it->second;
+    return KH_OK;
+}
+
+static int engine_build_lindblad(kh_engine *e, const kh_problem_lindblad *pl) {
+    KH_HIP(hipGetDevice(&e->device));
+    hipDeviceProp_t prop;
+    KH_HIP(hipGetDeviceProperties(&prop, e->device));
+    e->num_cus = prop.multiProcessorCount;
+    const int K = e->K, L = e->L, d = pl->d, n_c = pl->n_c, dd = d * d;
+    // W buffers: as many of the Lindblad operators at a time as LDS holds
+    int nw = n_c > 1 ? n_c : 1;
+    while (nw > 1 && kh_lind_lds_bytes(d, n_c, nw) > KH_LIND_LDS_MAX) --nw;
+    if (kh_lind_lds_bytes(d, n_c, nw) > KH_LIND_LDS_MAX)
+        return kh_fail(KH_ERR_UNSUPPORTED, "d=%d with %d Lindblad operators needs %zu bytes of LDS", d, n_c, kh_lind_lds_bytes(d, n_c, nw));
+    // bounds on || Lindbladian ||: n_0 = 2 ||H0|| + 2 sum_j ||C_j||^2, n_l = 2 ||H_l||
+    const size_t stride = (size_t)1 + L + n_c;
+    std::vector<double> norms((size_t)K * (1 + L), 0.0);
+    std::map<const void *, double> fro;
+    for (int k = 0; k < K; ++k) {
+        auto norm_of = [&](const kh_cdouble *op, size_t j, double *out) {
+            *out = 0.0;
+            if (op == nullptr) return (int)KH_OK;
+            if (pl->op_norms != nullptr) return *out = pl->op_norms[k * stride + j], (int)KH_OK;
+            return lind_host_norm((const cplx *)op, d, fro, out);
+        };
+        double v = 0.0;
+        for (int j = 0; j <= L; ++j) {
+            KH_TRY(norm_of(pl->ops[(size_t)k * (1 + L) + j], j, &v));
+            norms[(size_t)k * (1 + L) + j] = 2.0 * v;
+        }
+        for (int j = 0; j < n_c; ++j) {
+            KH_TRY(norm_of(pl->c_ops[(size_t)k * n_c + j], 1 + L + j, &v));
+            norms[(size_t)k * (1 + L)] += 2.0 * v * v;
+        }
+    }
+    kh_problem pr;
+    pr.K = K, pr.N = d, pr.L = L, pr.nt = e->nt, pr.is_super = 1, pr.reserved = 0;
+    pr.dt = pl->dt, pr.ops = pl->ops, pr.op_norms = norms.data(), pr.tol = pl->tol, pr.theta_max = pl->theta_max;
+    const std::vector<int32_t> dims(K, d);
+    std::vector<const cplx *> fw, bw;
+    KH_TRY(stage_operators(e, &pr, nullptr, nullptr, fw, bw, dims.data()));
+    // the Lindblad operators and their adjoints (one copy per distinct operator)
+    const size_t ncops = (size_t)K * n_c;
+    std::vector<const cplx *> cfw(ncops > 0 ? ncops : 1, nullptr), cbw(ncops > 0 ? ncops : 1, nullptr);
+    KhCopies adj;
+    for (size_t i = 0; i < ncops; ++i) {
+        const cplx *src = (const cplx *)pl->c_ops[i];
+        cfw[i] = src;
+        if (src == nullptr) continue;
+        KH_TRY(adj.get(e, src, nullptr, sizeof(cplx) * dd, [&](cplx *dst) {
+            kh_adjoint_kernel<<<dim3(1, 1), 256>>>(src, dst, d);
+            return KH_OK;
+        }, &cbw[i]));
+    }
+    KH_HIP(hipGetLastError());
+    const cplx **d_cfw = nullptr, **d_cbw = nullptr;
+    KH_TRY(dev_upload(e, &d_cfw, cfw.data(), sizeof(cplx *) * cfw.size()));
+    KH_TRY(dev_upload(e, &d_cbw, cbw.data(), sizeof(cplx *) * cbw.size()));
+    // A0 = -i H0 - M/2, B0 = +i H0 - M/2 per objective, and their adjoints for the backward sweep
+    cplx *pool[4] = {nullptr, nullptr, nullptr, nullptr};  // A0 fw, B0 fw, A0 bw, B0 bw
+    for (cplx *&q : pool) KH_TRY(dev_alloc(e, &q, sizeof(cplx) * (size_t)K * dd));
+    kh_lind_setup_kernel<<<K, 256>>>(e->d_ops_fw, d_cfw, pool[0], pool[1], 1 + L, n_c, d);
+    for (int k = 0; k < K; ++k) {
+        kh_adjoint_kernel<<<dim3(1, 1), 256>>>(pool[0] + (size_t)k * dd, pool[2] + (size_t)k * dd, d);
+        kh_adjoint_kernel<<<dim3(1, 1), 256>>>(pool[1] + (size_t)k * dd, pool[3] + (size_t)k * dd, d);
+    }
+    KH_HIP(hipGetLastError());
+    const cplx **tabs[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (int t = 0; t < 4; ++t) {
+        std::vector<const cplx *> ptrs(K);
+        for (int k = 0; k < K; ++k) ptrs[k] = pool[t] + (size_t)k * dd;
+        KH_TRY(dev_upload(e, &tabs[t], ptrs.data(), sizeof(cplx *) * K));
+    }
+    e->lind_fw = KhLindArgs{d, n_c, nw, -1.0, d_cfw, tabs[0], tabs[1]};
+    e->lind_bw = KhLindArgs{d, n_c, nw, +1.0, d_cbw, tabs[2], tabs[3]};
+
+    KhFacts f;
+    f.K = K, f.N = e->N, f.L = L, f.num_cus = e->num_cus;
+    f.csr = false, f.shared = false, f.has_h1 = f.all_h1 = false;
+    f.theta_max = pl->theta_max;
+    f.lind = true;
+    e->plan = plan_families(f, e->sw);
+    e->gen_adj_failed = true;  // (no adjoint-side store: the sums come from one pair of products per interval)
+    KH_TRY(stage_series(e));
+    return stage_workspaces(e);
+}
+
+extern "C" int kh_engine_create_lindblad(const kh_problem_lindblad *pl, kh_engine **out) {
+    if (pl == nullptr || out == nullptr) return kh_fail(KH_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (pl->d < 1 || pl->n_c < 0) return kh_fail(KH_ERR_INVALID, "bad sizes d=%d n_c=%d", pl->d, pl->n_c);
+    if (pl->n_c > 0 && pl->c_ops == nullptr) return kh_fail(KH_ERR_INVALID, "c_ops missing");
+    kh_problem pr;
+    pr.K = pl->K, pr.N = pl->d, pr.L = pl->L, pr.nt = pl->nt, pr.is_super = 1, pr.reserved = 0;
+    pr.dt = pl->dt, pr.ops = pl->ops, pr.op_norms = nullptr, pr.tol = pl->tol, pr.theta_max = pl->theta_max;
+    KH_TRY(validate_problem(&pr));
+    if (pl->d > KH_LIND_DMAX || pl->n_c > KH_LIND_MAX_NC || pl->L > KH_LIND_MAX_L)
+        return kh_fail(KH_ERR_UNSUPPORTED, "the Lindblad-form kernels take d <= %d, at most %d Lindblad operators and %d controls (d=%d n_c=%d L=%d)",
+                       KH_LIND_DMAX, KH_LIND_MAX_NC, KH_LIND_MAX_L, pl->d, pl->n_c, pl->L);
+    kh_engine *e = new kh_engine();
+    e->K = pl->K;
+    e->N = pl->d * pl->d;
+    e->L = pl->L;
+    e->nt = pl->nt;
+    e->is_super = 1;
+    e->lind = true;
+    e->tol = pl->tol > 0.0 ? pl->tol : ldexp(1.0, -53);
+    e->sw = read_switches();
+    const int rc = engine_build_lindblad(e, pl);
+    if (rc != KH_OK) {
+        kh_engine_destroy(e);
+        return rc;
+    }
+    *out = e;
+    return KH_OK;
+}
+
 // ---------------------------------------------------------------------------
 // launches
 // ---------------------------------------------------------------------------
@@ -1621,6 +1761,16 @@ static int with_ell(int N, int E, bool stream, F &&f) {
     if (N > 1024) return N <= 1536 ? f(KhInt<512>{}, KhInt<3>{}, KhInt<8>{}, F_{}) : f(KhInt<512>{}, KhInt<4>{}, KhInt<8>{}, F_{});
     if (E <= 8) return f(KhInt<1024>{}, KhInt<1>{}, KhInt<8>{}, F_{});
     return E <= 12 ? f(KhInt<512>{}, KhInt<2>{}, KhInt<12>{}, F_{}) : f(KhInt<512>{}, KhInt<2>{}, KhInt<16>{}, F_{});
+}
+
+// Lindblad-form kernels (kh_lind.h): rows per thread
+template <class F>
+static int with_lind(int d, F &&f) {
+    switch (kh_lind_rb(d)) {
+        case 1: return f(KhInt<1>{});
+        case 2: return f(KhInt<2>{});
+        default: return f(KhInt<4>{});
+    }
 }
 
 // cooperative kernels (kh_coop.h): operator-fragment slots per lane, objectives per workgroup
@@ -1805,6 +1955,15 @@ static int sweep_store(kh_engine *e, bool backward, const double *pulses, const 
             });
             break;
         }
+        case KIND_LIND: {
+            const KhLindArgs la = backward ? e->lind_bw : e->lind_fw;
+            rc = with_lind(la.d, [&](auto rb) {
+                return launch_plain_lds<kh_lind_sweep_store<decltype(rb)::value>>(e, dim3(grid_cus), dim3(KH_LIND_THREADS),
+                                                                                   kh_lind_lds_bytes(la.d, la.n_c, la.nw), st, p, la, pulses,
+                                                                                   in, store, out, direction);
+            });
+            break;
+        }
         case KIND_TILE_RPT2:
         case KIND_TILE_RPT1:
             rc = with_tile(pl.kind_store == KIND_TILE_RPT2, e->L, [&](auto rpt, auto lt) {
@@ -1867,7 +2026,7 @@ extern "C" int kh_backward_store(kh_engine *e, const kh_cdouble *chi_T_dev, cons
 
 // ---- the update sweep: one route per call (update_route), one small launcher per family
 
-enum KhRoute { ROUTE_ENS, ROUTE_ENS2, ROUTE_STREAM, ROUTE_QUAD, ROUTE_MINI, ROUTE_Q2, ROUTE_COOP, ROUTE_TILEN, ROUTE_ELL, ROUTE_TILE, ROUTE_TILEX, ROUTE_GENERIC };
+enum KhRoute { ROUTE_ENS, ROUTE_ENS2, ROUTE_STREAM, ROUTE_QUAD, ROUTE_MINI, ROUTE_Q2, ROUTE_COOP, ROUTE_TILEN, ROUTE_ELL, ROUTE_TILE, ROUTE_TILEX, ROUTE_GENERIC, ROUTE_LIND };
 
 // Which launcher runs an update call.  whole: the single launch over all intervals; stepwise: one interval per launch
 // (host- or device-indexed: the same route); so: second order; reduced_G: kh_set_update_workgroups; world: ranks of the
@@ -1876,6 +2035,7 @@ enum KhRoute { ROUTE_ENS, ROUTE_ENS2, ROUTE_STREAM, ROUTE_QUAD, ROUTE_MINI, ROUT
 template <class AdjStore>
 static KhRoute update_route(const KhPlan &p, int K, bool stepwise, bool whole, bool so, int reduced_G, int world,
                             bool have_sq, AdjStore &&adj_store) {
+    if (p.kind == KIND_LIND) return ROUTE_LIND;
     if (p.ens && whole) {
         // first order, four objectives per workgroup (512 < K <= 1024): the A^2 chain with the update sums on the adjoint
         // side (kh_ens2_forward_update; KH_ENS2=0: the term-by-term kernel, A/B switch and what second order and the other
@@ -2088,6 +2248,17 @@ static int update_tilex(kh_engine *e, const KhSweepArgs &p, const KhUpdateArgs &
     });
 }
 
+// Lindblad form (kh_lind.h): first order, the whole sweep in one launch
+static int update_lind(kh_engine *e, const KhSweepArgs &p, const KhUpdateArgs &u, const KhExchange &ex, hipStream_t st) {
+    if (u.sigma != nullptr || !u.internal_exchange)
+        return kh_fail(KH_ERR_UNSUPPORTED, "the Lindblad-form kernels run the first-order update sweep in one launch only");
+    const KhLindArgs la = e->lind_fw;
+    return with_lind(la.d, [&](auto rb) {
+        return launch_persistent_lds<kh_lind_forward_update<decltype(rb)::value>>(e, dim3(e->plan.grid_update), dim3(KH_LIND_THREADS),
+                                                                                  kh_lind_lds_bytes(la.d, la.n_c, la.nw), st, p, la, u, ex);
+    });
+}
+
 static int launch_update(kh_engine *e, const KhUpdateArgs &u, hipStream_t st) {
     const KhSweepArgs p = sweep_args(e, false);
     const KhExchange ex = exchange_args(e, u.internal_exchange != 0);
@@ -2119,6 +2290,7 @@ static int launch_update(kh_engine *e, const KhUpdateArgs &u, hipStream_t st) {
             break;
         case ROUTE_TILEX: rc = update_tilex(e, p, u, ex, st); break;
         case ROUTE_GENERIC: rc = update_generic(e, p, u, ex, st); break;
+        case ROUTE_LIND: rc = update_lind(e, p, u, ex, st); break;
     }
     if (rc != KH_OK) return rc;
     KH_HIP(hipGetLastError());
@@ -2222,6 +2394,7 @@ extern "C" int kh_set_update_workgroups(kh_engine *e, int32_t max_workgroups, in
         e->reduced_G = 0;
         return KH_OK;
     }
+    if (e->lind) return kh_fail(KH_ERR_UNSUPPORTED, "Lindblad-form engines (kh_engine_create_lindblad) have no form with fewer workgroups");
     if (e->p2p_ready) return kh_fail(KH_ERR_UNSUPPORTED, "sharded sweeps keep their grid (all ranks must agree on the form)");
     const KhPlan &p = e->plan;
     int G = 0;
@@ -2251,6 +2424,7 @@ extern "C" int kh_set_second_order(kh_engine *e, const kh_cdouble *fw_prev_dev, 
     const int given = (fw_prev_dev != nullptr) + (fw_store_dev != nullptr) + (sigma_dev != nullptr);
     if (given != 0 && given != 3)
         return kh_fail(KH_ERR_INVALID, "fw_prev, fw_store and sigma must be given together (or all NULL)");
+    if (e->lind && given != 0) return kh_fail(KH_ERR_UNSUPPORTED, "Lindblad-form engines (kh_engine_create_lindblad) run the first-order update only");
     if (fw_prev_dev != nullptr && (const void *)fw_prev_dev == (const void *)fw_store_dev)
         return kh_fail(KH_ERR_INVALID, "fw_store must not alias fw_prev");
     e->so_fw_prev = (const cplx *)fw_prev_dev;
@@ -2266,6 +2440,7 @@ extern "C" int kh_update_begin(kh_engine *e, const kh_cdouble *chi_store_dev, co
         guess_dev == nullptr || opt_dev == nullptr || g_a_dev == nullptr || partial_dev == nullptr)
         return kh_fail(KH_ERR_INVALID, "null argument");
     if (e->L < 1) return kh_fail(KH_ERR_INVALID, "no controls to update");
+    if (e->lind) return kh_fail(KH_ERR_UNSUPPORTED, "Lindblad-form engines (kh_engine_create_lindblad) have no per-interval update sweep");
     hipStream_t st = (hipStream_t)stream;
     e->guess_dev = guess_dev;
     KH_HIP(hipMemsetAsync(e->d_stats, 0, sizeof(double) * 4, st));
@@ -2284,6 +2459,7 @@ extern "C" int kh_update_step(kh_engine *e, int32_t n, const double *D_dev, cons
         shape_dev == nullptr || lambda_dev == nullptr || opt_dev == nullptr || g_a_dev == nullptr ||
         partial_dev == nullptr)
         return kh_fail(KH_ERR_INVALID, "null argument");
+    if (e->lind) return kh_fail(KH_ERR_UNSUPPORTED, "Lindblad-form engines (kh_engine_create_lindblad) have no per-interval update sweep");
     if (e->guess_dev == nullptr) return kh_fail(KH_ERR_INVALID, "kh_update_begin was not called");
     if (n < 0 || n >= e->nt - 1) return kh_fail(KH_ERR_INVALID, "interval %d out of range", n);
     const KhUpdateArgs u = update_args(e, chi_store_dev, chi_norms_dev, e->guess_dev, shape_dev, lambda_dev, opt_dev, g_a_dev);
@@ -2298,6 +2474,7 @@ extern "C" int kh_update_step_dev(kh_engine *e, int32_t *n_dev, const double *D_
         chi_norms_dev == nullptr || shape_dev == nullptr || lambda_dev == nullptr || opt_dev == nullptr ||
         g_a_dev == nullptr || partial_dev == nullptr)
         return kh_fail(KH_ERR_INVALID, "null argument");
+    if (e->lind) return kh_fail(KH_ERR_UNSUPPORTED, "Lindblad-form engines (kh_engine_create_lindblad) have no per-interval update sweep");
     if (e->guess_dev == nullptr) return kh_fail(KH_ERR_INVALID, "kh_update_begin was not called");
     const KhUpdateArgs u = update_args(e, chi_store_dev, chi_norms_dev, e->guess_dev, shape_dev, lambda_dev, opt_dev, g_a_dev);
     return update_interval(e, u, D_dev, 0, 1, n_dev, partial_dev, true, (hipStream_t)stream);  // (n_begin: overridden on the device)
@@ -2305,6 +2482,7 @@ extern "C" int kh_update_step_dev(kh_engine *e, int32_t *n_dev, const double *D_
 
 extern "C" int kh_update_end(kh_engine *e, kh_cdouble *psi_T_dev, void *stream) {
     if (e == nullptr || psi_T_dev == nullptr) return kh_fail(KH_ERR_INVALID, "null argument");
+    if (e->lind) return kh_fail(KH_ERR_UNSUPPORTED, "Lindblad-form engines (kh_engine_create_lindblad) have no per-interval update sweep");
     KH_HIP(hipMemcpyAsync(psi_T_dev, e->d_phi, sizeof(cplx) * (size_t)e->K * e->N, hipMemcpyDeviceToDevice,
                           (hipStream_t)stream));
     e->guess_dev = nullptr;
@@ -2347,6 +2525,7 @@ extern "C" int kh_p2p_create_window(kh_engine *e, int32_t world, int32_t rank, u
     if (e == nullptr || ipc_handle_out == nullptr) return kh_fail(KH_ERR_INVALID, "null argument");
     if (world < 1 || rank < 0 || rank >= world) return kh_fail(KH_ERR_INVALID, "bad world/rank %d/%d", rank, world);
     if (e->mixed) return kh_fail(KH_ERR_UNSUPPORTED, "mixed engines (kh_engine_create_mixed) are not sharded");
+    if (e->lind) return kh_fail(KH_ERR_UNSUPPORTED, "Lindblad-form engines (kh_engine_create_lindblad) are not sharded");
     const int Lx = e->L > 0 ? e->L : 1;
     if (world * Lx * 2 > 64 || Lx > KH_MAX_L)
         return kh_fail(KH_ERR_UNSUPPORTED, "world * L = %d exceeds the 32 exchange lanes (or more than %d controls)", world * Lx, KH_MAX_L);

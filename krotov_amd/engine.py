@@ -60,9 +60,16 @@ class HipKrotovEngine:
         op_norms: optional (K, 1+L) spectral-norm bounds; computed on the host
             with ``numpy.linalg.norm(., 2)`` per distinct operator when omitted.
         device: torch device (default: current CUDA/HIP device).
+        c_ops: Lindblad form (``kh_engine_create_lindblad``, kernel family ``"lindblad/matrix"``): list (K) of lists of
+            (d, d) Lindblad operators (``None`` / shorter lists where an objective has fewer; ``[]`` for none).  ``ops``
+            then holds d x d Hamiltonian parts, the states are density matrices column-stacked to N = d*d as for
+            ``is_super`` (which is implied), and every sweep equals -- to rounding -- the one of an ``is_super`` engine on
+            ``liouvillian(H, c_ops)``, whose d^2 x d^2 operators are never built.  d <= 32, at most 4 Lindblad operators
+            and 4 controls (``KrotovHipError`` with ``KH_ERR_UNSUPPORTED`` beyond); first-order update on one GPU only.
+            ``op_norms``: (K, 1+L+n_c) bounds for (H0, H_l, C_j).
     """
 
-    def __init__(self, ops, dt, is_super=False, op_norms=None, device=None, tol=0.0, theta_max=0.0):
+    def __init__(self, ops, dt, is_super=False, op_norms=None, device=None, tol=0.0, theta_max=0.0, c_ops=None):
         _require_gpu()
         self._lib = _lib.load()
         self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
@@ -80,6 +87,15 @@ class HipKrotovEngine:
             if len(row) != 1 + self.L:
                 raise ValueError("objective %d has %d operators, expected %d" % (k, len(row), 1 + self.L))
         dims = self._dims_of(ops)
+        self.lindblad = c_ops is not None
+        if self.lindblad:
+            if len(set(dims)) > 1 or len(c_ops) != self.K:
+                raise ValueError("Lindblad form: one dimension d for all objectives and one c_ops list per objective")
+            if any(_is_sparse(op) for row in list(ops) + [list(r or []) for r in c_ops] for op in row):
+                raise ValueError("Lindblad form: dense d x d operators only")
+            self.d = dims[0]
+            dims = [self.d * self.d] * self.K
+            kinds = [True] * self.K
         self.mixed = len(set(dims)) > 1 or len(set(kinds)) > 1
         self.dims = dims
         self.kinds = kinds
@@ -90,11 +106,13 @@ class HipKrotovEngine:
             raise ValueError("objectives of different dimension or kind need dense operators: "
                              "sparse (CSR) operators take one dimension and one kind for all objectives")
         with torch.cuda.device(self.device):
-            if sparse:
+            if self.lindblad:
+                norms = self._create_lindblad(ops, c_ops, dt, op_norms, tol, theta_max)
+            elif sparse:
                 norms = self._create_sparse(ops, dt, op_norms, tol, theta_max)
             else:
                 norms = self._create_dense(ops, dt, op_norms, tol, theta_max)
-        self.op_norms = norms.reshape(self.K, 1 + self.L)
+        self.op_norms = norms.reshape(self.K, -1)
         self.kernel = self._lib.kh_engine_kernel(self._handle).decode()
         # optional per-launch timing with HIP events on the launch stream
         self.profile = os.environ.get('KH_PROFILE', '0') == '1'
@@ -171,6 +189,55 @@ class HipKrotovEngine:
             _lib.check(self._lib.kh_engine_create_mixed(ctypes.byref(pr), dims, kinds, ctypes.byref(self._handle)))
         else:
             _lib.check(self._lib.kh_engine_create(ctypes.byref(pr), ctypes.byref(self._handle)))
+        return norms
+
+    def _create_lindblad(self, ops, c_ops, dt, op_norms, tol, theta_max):
+        """d x d Hamiltonian parts and Lindblad operators, each distinct object uploaded once.  Norm bounds: the 2-norm;
+        for a Hermitian Hamiltonian part half the spread of its spectrum (the commutator does not see H -> H - c)."""
+        rows = [list(r) if r is not None else [] for r in c_ops]
+        self.n_c = n_c = max([len(r) for r in rows] + [0])
+        stride = 1 + self.L + n_c
+        n_ops, n_cops = self.K * (1 + self.L), self.K * n_c
+        ptrs = (ctypes.c_void_p * n_ops)()
+        cptrs = (ctypes.c_void_p * max(n_cops, 1))()
+        norms = np.zeros(self.K * stride, dtype=np.float64)
+        norms_cache = {}
+
+        def upload(op, hamiltonian):
+            key = id(op)
+            if key not in self._op_tensors:
+                host = op.detach().cpu().numpy() if isinstance(op, torch.Tensor) else np.asarray(op)
+                host = np.ascontiguousarray(host, dtype=np.complex128)
+                if host.shape != (self.d, self.d):
+                    raise ValueError("Lindblad form: every operator must be %d x %d" % (self.d, self.d))
+                self._op_tensors[key] = (torch.from_numpy(host).to(self.device), op)
+                if hamiltonian and np.array_equal(host, host.conj().T):
+                    ev = np.linalg.eigvalsh(host)
+                    norms_cache[key] = 0.5 * float(ev[-1] - ev[0])
+                else:
+                    norms_cache[key] = float(np.linalg.norm(host, 2))
+            return self._op_tensors[key][0].data_ptr(), norms_cache[key]
+
+        for k in range(self.K):
+            for j, op in enumerate(ops[k]):
+                if op is not None:
+                    ptrs[k * (1 + self.L) + j], norms[k * stride + j] = upload(op, True)
+            for j, op in enumerate(rows[k]):
+                if op is not None:
+                    cptrs[k * n_c + j], norms[k * stride + 1 + self.L + j] = upload(op, False)
+        if op_norms is not None:
+            norms = np.ascontiguousarray(np.asarray(op_norms, dtype=np.float64).reshape(-1))
+            if norms.size != self.K * stride:
+                raise ValueError("op_norms must have K*(1+L+n_c) entries")
+        pr = _lib.kh_problem_lindblad()
+        pr.K, pr.d, pr.L, pr.nt, pr.n_c = self.K, self.d, self.L, self.nt, n_c
+        pr.dt = dt.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+        pr.ops = ctypes.cast(ptrs, ctypes.POINTER(ctypes.c_void_p))
+        pr.c_ops = ctypes.cast(cptrs, ctypes.POINTER(ctypes.c_void_p))
+        pr.op_norms = norms.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+        pr.tol = float(tol)
+        pr.theta_max = float(theta_max)
+        _lib.check(self._lib.kh_engine_create_lindblad(ctypes.byref(pr), ctypes.byref(self._handle)))
         return norms
 
     def _create_sparse(self, ops, dt, op_norms, tol, theta_max):

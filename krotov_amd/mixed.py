@@ -11,7 +11,7 @@ import numpy as np
 
 from ._ingest import obj_type, state_array, state_to_vector, to_dense, vector_to_state
 
-__all__ = ['Layout', 'layout_of', 'objective_kind']
+__all__ = ['Layout', 'layout_of', 'objective_kind', 'LindbladLayout', 'lindblad_layout_of']
 
 
 class Layout:
@@ -91,3 +91,73 @@ def layout_of(objectives, propagator=None):
         dims.append(n)
         kinds.append(objective_kind(obj, op, n, prop))
     return Layout(dims, kinds)
+
+
+# the limits of the Lindblad-form kernels (krotov_amd/csrc/kh_lind.h: KH_LIND_DMAX, KH_LIND_MAX_NC, KH_LIND_MAX_L)
+LIND_DMAX, LIND_MAX_NC, LIND_MAX_L = 32, 4, 4
+
+
+class LindbladLayout:
+    """How an objective list with ``c_ops`` runs on the device (:func:`lindblad_layout_of`).  ``decision``:
+    ``'matrix'`` -- the Lindblad-form engine (``"lindblad/matrix"``): every objective a d x d density matrix under a
+    d x d Hamiltonian, ``d`` common, ``n_c`` the largest number of Lindblad operators; or ``'liouvillian'`` -- the
+    Liouvillian fallback: ``liouvillian(H, c_ops)`` is built on the host for every objective with ``c_ops`` and today's
+    uniform / mixed engine runs, for the ``reason`` given."""
+
+    def __init__(self, decision, reason=None, d=None, n_c=0):
+        self.decision, self.reason, self.d, self.n_c = decision, reason, d, n_c
+
+    @property
+    def matrix(self):
+        return self.decision == 'matrix'
+
+    @staticmethod
+    def liouvillian_objectives(objectives):
+        """The same list with every Lindblad-form objective rewritten as ``H = liouvillian(H, c_ops)``, ``c_ops = []``
+        (the nested-list positions of the controls do not change)."""
+        from .objectives import Objective, liouvillian
+
+        out = []
+        for obj in objectives:
+            if len(obj.c_ops) == 0:
+                out.append(obj)
+                continue
+            new = Objective(initial_state=obj.initial_state, H=liouvillian(obj.H, obj.c_ops), target=obj.target, c_ops=[])
+            if getattr(obj, 'weight', None) is not None:
+                new.weight = obj.weight
+            out.append(new)
+        return out
+
+
+def lindblad_layout_of(objectives, propagator=None, n_controls=None, second_order=False):
+    """Decide, on the host, how a list in which some objective carries ``c_ops`` runs (see :class:`LindbladLayout`).
+    A control inside ``c_ops`` raises ``NotImplementedError`` (as the reference's ``mu`` does, mu.py:135-139).  Objectives
+    without ``c_ops`` are fine in a matrix-form list when they, too, are d x d density matrices under a d x d
+    Hamiltonian."""
+    for obj in objectives:
+        if any(isinstance(c, list) for c in obj.c_ops):
+            raise NotImplementedError("Time-dependent collapse operators not implemented")
+    if second_order:
+        return LindbladLayout('liouvillian', "second-order update (sigma=)")
+    ds, n_c = set(), 0
+    for k, obj in enumerate(objectives):
+        op = _drift(obj, k)
+        d = _dim(op)
+        s0 = state_array(obj.initial_state)
+        if obj_type(op) == 'super' or not (s0.ndim == 2 and s0.shape == (d, d) and d > 1):
+            return LindbladLayout('liouvillian', "objective %d is not a d x d density matrix under a d x d Hamiltonian "
+                                  "(kets and Lindblad-form objectives mixed)" % k)
+        if any(_dim(c) != d for c in obj.c_ops):
+            raise ValueError("objective %d: c_ops must have the dimension of H" % k)
+        ds.add(d)
+        n_c = max(n_c, len(obj.c_ops))
+    if len(ds) > 1:
+        return LindbladLayout('liouvillian', "objectives of different dimension %s" % sorted(ds))
+    d = ds.pop()
+    if d > LIND_DMAX:
+        return LindbladLayout('liouvillian', "d = %d > %d" % (d, LIND_DMAX), d=d, n_c=n_c)
+    if n_c > LIND_MAX_NC:
+        return LindbladLayout('liouvillian', "%d Lindblad operators > %d" % (n_c, LIND_MAX_NC), d=d, n_c=n_c)
+    if n_controls is not None and n_controls > LIND_MAX_L:
+        return LindbladLayout('liouvillian', "%d controls > %d" % (n_controls, LIND_MAX_L), d=d, n_c=n_c)
+    return LindbladLayout('matrix', d=d, n_c=n_c)

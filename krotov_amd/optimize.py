@@ -51,10 +51,10 @@ from ._lib import KH_ERR_TIMEOUT as _KH_ERR_TIMEOUT, KH_ERR_UNSUPPORTED as _KH_E
 _KH_MAX_CONTROLS = 32  # KH_GEN_MAX_L of krotov_amd/csrc/kh_common.h (the register-resident kernel families: 8)
 _FULL_GRID_PROBE_EVERY = 16  # update sweeps in a row on a reduced grid before the full one is tried again
 from .info_hooks import chain
-from .mixed import layout_of
+from .mixed import Layout, LindbladLayout, layout_of, lindblad_layout_of
 from .mu import derivative_wrt_pulse
 from .parallelization import serial_map
-from .propagators import HipExpm, Propagator, expm
+from .propagators import HipExpm, LindbladExpm, Propagator, expm
 from .result import Result
 from .second_order import _overlap
 from .shapes import one_shape, zero_shape
@@ -410,7 +410,11 @@ def _use_device_path(propagator, mu, overlap, sigma, storage, objectives):
         return False
     if storage != 'array':
         return False
-    return all(len(obj.c_ops) == 0 for obj in objectives)
+    if all(len(obj.c_ops) == 0 for obj in objectives):
+        return True
+    # objectives in Lindblad form (H + c_ops): only with the propagator that opts in
+    props = propagator if isinstance(propagator, list) else [propagator]
+    return all(isinstance(p, LindbladExpm) for p in props)
 
 
 class _HipBackend:
@@ -418,7 +422,8 @@ class _HipBackend:
 
     device = True
 
-    def __init__(self, objectives, pulses_mapping, tlist, n_controls, propagator, process_group=None):
+    def __init__(self, objectives, pulses_mapping, tlist, n_controls, propagator, process_group=None,
+                 second_order=False):
         import torch
 
         from .engine import HipKrotovEngine
@@ -442,7 +447,26 @@ class _HipBackend:
             raise ValueError("%d objectives cannot be sharded over %d ranks" % (K_total, self.world))
         # every objective's dimension and kind (Hilbert / Liouville), decided per objective over the whole list (the
         # same on every rank)
-        layout = layout_of(objectives, propagator)
+        # objectives in Lindblad form (H + c_ops): the matrix-form engine, or -- outside its limits -- the Liouvillian
+        # built on the host and today's engines (host-only decision)
+        self.lindblad = None
+        if any(len(obj.c_ops) > 0 for obj in objectives):
+            lind = lindblad_layout_of(objectives, propagator, n_controls, second_order)
+            if lind.matrix:
+                if process_group is not None:
+                    raise ValueError("objectives in Lindblad form run on one GPU: process_group= (sharding) is not "
+                                     "supported for the matrix-form engine")
+                self.lindblad = lind
+                logging.getLogger('krotov').info(
+                    "Lindblad-form objectives: matrix-form engine (d = %d, up to %d Lindblad operators)", lind.d, lind.n_c)
+            else:
+                logging.getLogger('krotov').info("Lindblad-form objectives: Liouvillian fallback (%s)", lind.reason)
+                objectives = LindbladLayout.liouvillian_objectives(objectives)
+                self.objectives = objectives
+        if self.lindblad is not None:
+            layout = Layout([self.lindblad.d ** 2] * K_total, [True] * K_total)
+        else:
+            layout = layout_of(objectives, propagator)
         self.layout = layout if layout.mixed else None
         self.K_total = K_total
         L = n_controls
@@ -474,7 +498,7 @@ class _HipBackend:
                 sums[key] = (total, terms)
             return sums[key][0]
 
-        ops = []
+        ops, c_rows = [], []
         for k in range(self.k0, self.k1):
             obj = objectives[k]
             H = obj.H if isinstance(obj.H, list) else [obj.H]
@@ -484,11 +508,15 @@ class _HipBackend:
                 where = pulses_mapping[k][0][l]
                 row.append(summed([H[i][0] for i in where]) if len(where) else None)
             ops.append(row)
+            c_rows.append([dense_of(c) for c in obj.c_ops])
         N = layout.stride
         self.is_super = layout.kinds[self.k0:self.k1] if layout.mixed else layout.kinds[self.k0]
         self.N, self.L = N, L
         tlist = np.asarray(tlist, dtype=np.float64)
-        self.engine = HipKrotovEngine(ops, np.diff(tlist), is_super=self.is_super)
+        if self.lindblad is not None:
+            self.engine = HipKrotovEngine(ops, np.diff(tlist), c_ops=c_rows)
+        else:
+            self.engine = HipKrotovEngine(ops, np.diff(tlist), is_super=self.is_super)
         self.nt = len(tlist)
         self.tlist_host = tlist
         self.likes = [obj.initial_state for obj in objectives]
@@ -799,7 +827,13 @@ def optimize_pulses(
     device_path = _use_device_path(propagator, mu, overlap, sigma, storage, objectives)
     if process_group is not None and not device_path:
         raise ValueError("process_group requires the device path (propagator=krotov_amd.propagators.expm)")
-    if process_group is not None and layout_of(objectives, propagator).mixed:
+    if device_path and any(len(obj.c_ops) > 0 for obj in objectives):
+        # (host-only, before any GPU work and any collective: a control inside c_ops raises here; the same verdict on
+        # every rank)
+        if lindblad_layout_of(objectives, propagator, None, second_order).matrix and process_group is not None:
+            raise ValueError("objectives in Lindblad form run on one GPU: process_group= (sharding) is not supported "
+                             "for the matrix-form engine")
+    elif process_group is not None and layout_of(objectives, propagator).mixed:
         # (host-only, the same verdict on every rank, before any collective)
         raise ValueError("objectives of different dimension or kind run on one GPU: process_group= (sharding) is "
                          "not supported for them")
@@ -852,7 +886,8 @@ def optimize_pulses(
         result = copy.deepcopy(continue_from)
 
     if device_path:
-        backend = _HipBackend(objectives, pulses_mapping, tlist, len(guess_pulses), propagator, process_group)
+        backend = _HipBackend(objectives, pulses_mapping, tlist, len(guess_pulses), propagator, process_group,
+                              second_order=second_order)
     else:
         backend = _PluginBackend(
             objectives, adjoint_objectives, pulses_mapping, tlist, propagators, storage, parallel_map, mu, overlap

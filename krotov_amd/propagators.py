@@ -21,7 +21,7 @@ import numpy as np
 
 from ._ingest import obj_type, state_to_vector, to_dense, vector_to_state
 
-__all__ = ['expm', 'Propagator', 'HipExpm', 'DensityMatrixODEPropagator']
+__all__ = ['expm', 'Propagator', 'HipExpm', 'LindbladExpm', 'DensityMatrixODEPropagator']
 
 
 class Propagator(ABC):
@@ -115,6 +115,57 @@ class HipExpm(Propagator):
 
     def __call__(self, H, state, dt, c_ops=None, backwards=False, initialize=False):
         return _single_step(H, state, dt, c_ops, backwards, self.liouville)
+
+
+class LindbladExpm(HipExpm):
+    """The opt-in for objectives in Lindblad form -- ``Objective.H`` the d x d Hamiltonian ``[H0, [H1, eps], ...]``,
+    ``Objective.c_ops`` the Lindblad operators (reference docs/10_howto.rst, "How to optimize in a dissipative system").
+    One interval of ``d/dt rho = -i (H rho - rho H) + sum_j (C_j rho C_j^+ - {C_j^+ C_j, rho} / 2)`` on the GPU in matrix
+    form (kernel family ``"lindblad/matrix"``); the result equals, to rounding, :class:`HipExpm` on
+    ``liouvillian(H, c_ops)``, which is never built.  Without ``c_ops`` it is :class:`HipExpm`.
+
+    ``backwards=True`` takes the operators of the *adjoint* objective (``Objective.adjoint()``: H^+ and the C_j^+) and
+    applies the adjoint generator, ``A^+ chi + chi B^+ + sum_j C_j^+ chi C_j``.
+
+    The reference has no propagator that accepts ``c_ops`` (its ``expm`` raises, as :func:`expm` and :class:`HipExpm`
+    here still do), so this class has no counterpart there: the Liouvillian form is the reference's own equivalent.
+    Passed to ``optimize_pulses`` it selects the device path for objectives with ``c_ops``; time-dependent ``c_ops``
+    raise ``NotImplementedError`` (as the reference's ``mu`` does, mu.py:135-139).  Beyond the kernels' limits (d > 32,
+    more than 4 Lindblad operators) the Liouvillian is built on the host and the uniform engine runs."""
+
+    def __call__(self, H, state, dt, c_ops=None, backwards=False, initialize=False):
+        if c_ops is None or len(c_ops) == 0:
+            return super().__call__(H, state, dt, c_ops, backwards, initialize)
+        from .configs import liouvillian_dense
+        from .engine import HipKrotovEngine  # needs a GPU; raises otherwise
+        from .mixed import LIND_DMAX, LIND_MAX_NC
+
+        if any(isinstance(c, list) for c in c_ops):
+            raise NotImplementedError("Time-dependent collapse operators not implemented")
+        A, _ = _fold(H)
+        cs = [to_dense(c) for c in c_ops]
+        if backwards:  # the adjoint objective's operators -> the objective's own
+            A, cs = A.conj().T, [c.conj().T for c in cs]
+        d = A.shape[0]
+        rho = np.asarray(state.full() if hasattr(state, 'full') else state, dtype=np.complex128)
+        if rho.shape != (d, d) or any(c.shape != (d, d) for c in cs):
+            raise NotImplementedError("Lindblad form: state and c_ops must be %d x %d matrices" % (d, d))
+        vec = rho.ravel(order='F')[None, :]
+        none = np.zeros((0, 1))
+        if d <= LIND_DMAX and len(cs) <= LIND_MAX_NC:
+            eng = HipKrotovEngine([[A]], [float(dt)], c_ops=[cs])
+            try:
+                res = (eng.backward(vec, none)[0, 0] if backwards else eng.forward(none, vec)[0]).cpu().numpy()
+            finally:
+                eng.close()
+        else:
+            Lv = liouvillian_dense(A, cs)
+            eng = HipKrotovEngine([[Lv.conj().T if backwards else Lv]], [float(dt)], is_super=True)
+            try:
+                res = eng.forward(none, vec)[0].cpu().numpy()
+            finally:
+                eng.close()
+        return vector_to_state(res, state)
 
 
 class DensityMatrixODEPropagator(HipExpm):
