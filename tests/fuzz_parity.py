@@ -6,11 +6,13 @@ scaled and per-objective operators; objectives without one of their controls; Hi
 
 Test infrastructure (it imports ``oracle/``): run on a GPU box,
 
-    python tests/fuzz_parity.py [--seconds 300] [--seed 1] [--cases 0] [--level sweeps|optimize]
+    python tests/fuzz_parity.py [--seconds 300] [--seed 1] [--cases 0] [--level sweeps|optimize] [--regimes]
 
 prints one line per case (kernel, shape, largest deviation) and a summary; exit code 1 if any case is off by more than
 the tolerance of tests/test_hip_parity.py (1e-12, 1e-11 in Liouville space).  ``tests/test_hip_parity.py::
-test_fuzz_parity_fixed_seed`` runs a fixed-seed slice of it in the suite.
+test_fuzz_parity_fixed_seed`` runs a fixed-seed slice of it in the suite.  ``--regimes`` (sweeps level) puts every drawn
+problem into a randomly chosen regime of the per-interval series (``ramp``, ``pulse_ramp``, ``tiny``: tests/helpers.py) and adds
+Lindblad-form and mixed-dimension problems; it draws from a generator of its own, so the default stream stays what it is.
 """
 import argparse
 import os
@@ -26,6 +28,7 @@ sys.path.insert(0, HERE)
 from krotov_amd import configs  # noqa: E402
 from oracle import krotov_oracle as ko  # noqa: E402
 
+import helpers as hp  # noqa: E402
 from helpers import oracle_controls, spec_to_oracle  # noqa: E402
 
 N_CHOICES = [2, 3, 4, 5, 7, 8, 15, 16, 17, 24, 31, 32, 33, 48, 63, 64, 65, 72, 80, 81, 95, 96, 97, 112, 127, 128, 129, 144]
@@ -74,6 +77,74 @@ def draw(rng, drop_controls=True):
             spec.Hc[k] = spec.Hc[0]
         tag += ' shared'
     return spec, tag, None
+
+
+def draw_regime(rng, spec, tag, fmt):
+    """``--regimes``: sometimes another kind of problem (Lindblad form, mixed dimensions), then a random regime; ``rng`` is
+    NOT the generator of :func:`draw`.  Returns the regime problem, its tag and the theta_max it was built for."""
+    kind = rng.choice(['drawn', 'drawn', 'drawn', 'drawn', 'lindblad', 'mixed'])
+    if kind == 'lindblad':
+        import test_lindblad_form as tlf
+
+        d, n_c, L = int(rng.choice([3, 5, 8, 12, 17, 23])), int(rng.integers(0, 3)), int(rng.integers(1, 3))
+        spec = tlf._random(d, int(rng.integers(1, 4)), L, n_c, int(rng.integers(12, 16)), int(rng.integers(0, 1000)),
+                           per_objective=bool(rng.integers(0, 2)))
+        spec.pulses = tlf._pulses(spec)
+        spec.shapes = [np.linspace(0.2, 1.0, len(spec.dt)) for _ in range(L)]
+        spec.lambdas = [0.7 + 0.3 * l for l in range(L)]
+        tag, fmt = 'lindblad(d=%d, K=%d, L=%d, n_c=%d)' % (d, spec.K, L, n_c), 'lindblad'
+    elif kind == 'mixed':
+        case = str(rng.choice(['dims', 'same_n', 'wide']))
+        spec = configs.config_mixed(case, nt=int(rng.integers(12, 24)))
+        tag, fmt = 'mixed(%s)' % case, 'mixed'
+    regime = str(rng.choice(['tiny', 'ramp', 'ramp', 'long'] + (['pulse_ramp'] if fmt in (None, 'csr') else [])))
+    if regime == 'long' and not (fmt in (None, 'csr') and spec.K * spec.N ** 2 <= 2e4):
+        regime = 'ramp'  # (140 intervals: where the oracle finishes in seconds)
+    # theta_max is given to the engine explicitly: the value of most families or that of the cooperative / padded-row kernels
+    theta_max = float(rng.choice([1.0, 1.0, 4.0]))
+    wanted = {'long': 140, 'tiny': 0}.get(regime, int(rng.integers(hp.RAMP_MIN_INTERVALS, 17)))
+    if fmt != 'lindblad' and len(spec.tlist) - 1 < wanted:
+        # (the drawn grids have 2 ... 23 intervals and a ramp needs 11: the same time span on a finer grid; the regime sets
+        # the step lengths anyway)
+        spec.tlist = np.linspace(spec.tlist[0], spec.tlist[-1], wanted + 1)
+    obj = hp.explicit(spec, 'dense' if fmt is None else fmt)
+    try:
+        out = hp.REGIMES[regime](obj, theta_max)
+    except ValueError:  # (a pulse ramp needs the drift alone below theta_max: the stiff Liouvillians are beyond it)
+        regime = 'ramp'
+        out = hp.REGIMES[regime](obj, theta_max)
+    return out, '%s %s theta_max=%g' % (tag, regime, theta_max), theta_max
+
+
+def run_regime_case(obj, theta_max):
+    """:func:`run_case` for a regime problem (explicit interval values, any operator form)."""
+    prob = hp.regime_oracle(obj)
+    pulses, Sa, lama = np.array(obj.pulses), np.array(obj.shapes), np.array(obj.lambdas)
+    chi_T = prob.target / np.linalg.norm(prob.target, axis=1)[:, None]
+    norms = np.full(obj.K, 0.3 * min(1.0, 8.0 / obj.K) * min(1.0, 4.0 / obj.L))
+    if obj.fmt == 'dense' and obj.is_super:
+        norms *= 0.02
+    with hp.MemoExpm():
+        ref_T, ref_states = ko.forward_propagation(prob, obj.pulses, store=True)
+        ref_chi = ko.backward_sweep(prob, chi_T, obj.pulses)
+        ref_opt, ref_psi, ref_ga = ko.forward_update_sweep(prob, ref_chi, norms, obj.pulses, obj.shapes, obj.lambdas)
+    eng = hp.regime_engine(obj, theta_max)
+    try:
+        fw_T, states = eng.forward(pulses, prob.init, store=True)
+        chi = eng.backward(chi_T, pulses)
+        opt, psi_T, g_a = eng.forward_update(chi, norms, prob.init, pulses, Sa, lama)
+        eng.check()
+        scale = max(1.0, np.abs(np.array(ref_opt)).max())
+        dev = {
+            'states': np.abs(states.cpu().numpy() - ref_states).max(),
+            'chi': np.abs(chi.cpu().numpy() - ref_chi).max(),
+            'opt': np.abs(opt.cpu().numpy() - np.array(ref_opt)).max() / scale,
+            'psi_T': np.abs(psi_T.cpu().numpy() - ref_psi).max(),
+            'g_a': np.abs(g_a.cpu().numpy() - ref_ga).max() / max(1.0, np.abs(ref_ga).max()),
+        }
+        return eng.kernel, dev
+    finally:
+        eng.close()
 
 
 def run_case(spec, fmt):
@@ -152,9 +223,10 @@ def run_optimize_case(spec, fmt, rng):
     return '%s chis_%s%s' % (engine_mod.LAST_ENGINE().kernel, spec.chi, ' 2nd' if second else ''), dev
 
 
-def fuzz(seed, seconds=None, cases=None, verbose=True, level='sweeps'):
+def fuzz(seed, seconds=None, cases=None, verbose=True, level='sweeps', regimes=False):
     """Run random cases until `seconds` have passed or `cases` are done; returns (number run, list of failures)."""
     rng = np.random.default_rng(seed)
+    rng_regimes = np.random.default_rng([int(seed), 0x7e91]) if regimes else None  # (the default stream stays untouched)
     t0 = time.time()
     done, failures, by_kernel = 0, [], {}
     while True:
@@ -171,7 +243,12 @@ def fuzz(seed, seconds=None, cases=None, verbose=True, level='sweeps'):
         tol = (1e-10 if spec.is_super else 1e-11) if level == 'optimize' else (1e-11 if spec.is_super else 1e-12)
         tol2 = 1e-9  # second order (the kernel tag ends in '2nd'): sigma's A is a ratio of small differences (1e-9)
         try:
-            if level == 'optimize':
+            if rng_regimes is not None and level == 'sweeps':
+                obj, tag, theta_max = draw_regime(rng_regimes, spec, tag, fmt)
+                liouville = obj.fmt == 'lindblad' or bool(np.any(obj.is_super))
+                tol = 1e-11 if liouville or ' ramp ' in tag else 1e-12  # (as tests/test_series_regimes.py)
+                kernel, dev = run_regime_case(obj, theta_max)
+            elif level == 'optimize':
                 kernel, dev = run_optimize_case(spec, fmt, rng)
             else:
                 kernel, dev = run_case(spec, fmt)
@@ -200,6 +277,9 @@ if __name__ == '__main__':
     ap.add_argument('--cases', type=int, default=0)
     ap.add_argument('--level', choices=['sweeps', 'optimize'], default='sweeps',
                     help="'optimize': two iterations of optimize_pulses (random chi constructor, first / second order) against oracle.optimize")
+    ap.add_argument('--regimes', action='store_true',
+                    help="put every drawn problem into a random regime of the series (ramp, pulse_ramp, tiny) and add Lindblad-form "
+                         "and mixed-dimension problems; drawn from a separate generator")
     a = ap.parse_args()
-    n, bad = fuzz(a.seed, seconds=None if a.cases else a.seconds, cases=a.cases or None, level=a.level)
+    n, bad = fuzz(a.seed, seconds=None if a.cases else a.seconds, cases=a.cases or None, level=a.level, regimes=a.regimes)
     sys.exit(1 if bad else 0)

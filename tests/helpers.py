@@ -169,3 +169,318 @@ def check_infohook_chaining(**optimize_kwargs):
     assert 'Iteration 1: \tF = 0.001978' in out
     assert 'msg: λₐ: 0.5 → 0.25' in out
     return res
+
+
+# ---------------------------------------------------------------------------
+# Regimes of the per-interval series (tests/test_series_regimes.py, tests/fuzz_parity.py --regimes)
+# ---------------------------------------------------------------------------
+# Pure NumPy.  A *regime problem* is a ProblemSpec (uniform or ``config_mixed``) or a Lindblad ``Case`` (anything with
+# ``H`` / ``C`` / ``dt``) that carries its interval values explicitly -- ``pulses`` (L arrays of nt - 1 values), ``shapes``,
+# ``lambdas`` -- because a non-uniform grid and pulse values of exactly 0.0 cannot be expressed through the
+# callable -> mid-point -> interval conversion of ``oracle_controls``.  ``fmt``: 'dense' | 'csr' | 'mixed' | 'lindblad'.
+
+# theta_n / theta_max along a ramp (log-linear between these levels): up through one, two and three sub-steps and down
+# again through other values than on the way up, from <= 1e-3 to 2.9 and back
+RAMP_LEVELS = (7e-4, 6e-2, 0.2, 1.5, 2.9, 2.6, 1.8, 0.5, 0.06, 2e-3, 5e-5)
+RAMP_MIN_INTERVALS = len(RAMP_LEVELS)
+PULSE_RAMP_DT = 0.02   # uniform grid of the pulse ramps: dt x this, so that the drift alone is at degree ~6
+PULSE_RAMP_FLOOR = 1e-4  # smallest pulse amplitude of a pulse ramp relative to its largest (where the drift alone exceeds the level)
+
+
+def _is_lindblad(obj):
+    return hasattr(obj, 'C') and hasattr(obj, 'H')
+
+
+def ramp_profile(M, periods=1):
+    """theta_n / theta_max on M intervals: every level of RAMP_LEVELS (``periods`` times over) on an interval of its own,
+    interpolated in the logarithm in between."""
+    levels = np.log(np.array(RAMP_LEVELS * periods))
+    at = np.round(np.arange(len(levels)) * (M - 1.0) / (len(levels) - 1.0))
+    return np.exp(np.interp(np.arange(M), at, levels))
+
+
+def explicit(obj, fmt=None):
+    """A shallow copy of ``obj`` with explicit ``pulses`` / ``shapes`` / ``lambdas`` (those of ``oracle_controls`` unless
+    it has them already) and ``fmt``."""
+    import copy
+
+    new = copy.copy(obj)
+    if getattr(new, 'pulses', None) is None:
+        gp, S, lam = oracle_controls(obj)
+        new.pulses, new.shapes, new.lambdas = [np.array(p) for p in gp], [np.array(s) for s in S], list(lam)
+    if fmt is not None or not hasattr(new, 'fmt'):
+        new.fmt = fmt or ('lindblad' if _is_lindblad(obj) else 'mixed' if hasattr(obj, 'kinds') else 'dense')
+    return new
+
+
+def regime_dt(obj):
+    return np.asarray(obj.dt, dtype=np.float64) if _is_lindblad(obj) else np.diff(obj.tlist)
+
+
+def _set_dt(obj, dt):
+    obj.tlist = np.concatenate([[0.0], np.cumsum(dt)])
+    if _is_lindblad(obj):
+        obj.dt = np.asarray(dt, dtype=np.float64)
+
+
+def series_bounds(obj):
+    """(K, 1 + L) norm bounds (n_0, n_l) with theta_n = dt_n (n_0 + sum_l |eps_l[n]| n_l): the formulas of
+    ``HipKrotovEngine._create_dense`` (2-norm), ``_create_sparse`` (sqrt(||A||_1 ||A||_inf)) and ``_create_lindblad`` +
+    ``kh_engine_create_lindblad`` (Hermitian Hamiltonian part: half the spread of its spectrum; n_0 = 2 ||H0|| +
+    2 sum_j ||C_j||^2, n_l = 2 ||H_l||), restated."""
+    cache = {}
+
+    def two(op):
+        return float(np.linalg.norm(np.asarray(op), 2))
+
+    def csr(op):
+        a = np.abs(np.asarray(op))
+        return float(np.sqrt(a.sum(axis=0).max() * a.sum(axis=1).max()))
+
+    def ham(op):
+        op = np.asarray(op)
+        if np.array_equal(op, op.conj().T):
+            ev = np.linalg.eigvalsh(op)
+            return 0.5 * float(ev[-1] - ev[0])
+        return two(op)
+
+    def bound(op, fn):
+        if op is None:
+            return 0.0
+        if id(op) not in cache:
+            cache[id(op)] = (fn(op), op)
+        return cache[id(op)][0]
+
+    if _is_lindblad(obj):
+        out = np.zeros((obj.K, 1 + obj.L))
+        for k in range(obj.K):
+            out[k] = [2.0 * bound(h, ham) for h in obj.H[k]]
+            out[k, 0] += 2.0 * sum(bound(c, two) ** 2 for c in obj.C[k] if c is not None)
+        return out
+    fn = csr if obj.fmt == 'csr' else two
+    return np.array([[bound(obj.H0[k], fn)] + [bound(obj.Hc[k][l], fn) for l in range(obj.L)] for k in range(obj.K)])
+
+
+def theta_sequence(obj, pulses=None):
+    """theta[k, n] of a regime problem under ``pulses`` (default: its own guess)."""
+    b = series_bounds(obj)
+    eps = np.abs(np.array(obj.pulses if pulses is None else pulses, dtype=np.float64)).reshape(obj.L, -1)
+    return regime_dt(obj)[None, :] * (b[:, :1] + b[:, 1:] @ eps)
+
+
+def _scale_operators(obj, factor):
+    """Every generator x ``factor``; objects shared between objectives stay shared (one scaled copy per distinct array)."""
+    made = {}
+
+    def s(op, f=factor):
+        if op is None:
+            return None
+        if (id(op), f) not in made:
+            made[id(op), f] = (f * op, op)
+        return made[id(op), f][0]
+
+    if _is_lindblad(obj):  # (the dissipator is quadratic in C)
+        obj.H = [[s(h) for h in row] for row in obj.H]
+        obj.C = [[s(c, np.sqrt(factor)) for c in row] for row in obj.C]
+    else:
+        obj.H0 = [s(h) for h in obj.H0]
+        obj.Hc = [[s(h) for h in row] for row in obj.Hc]
+
+
+def _largest(obj):
+    """The objective with the largest theta under the guess pulses, and theta_n / dt_n of it."""
+    rate = theta_sequence(obj) / regime_dt(obj)[None, :]
+    k = int(np.argmax(rate.max(axis=1)))
+    return k, rate[k]
+
+
+def regime_ramp(obj, theta_max):
+    """Non-uniform grid: dt_n such that theta_n of the objective with the largest norms follows ``ramp_profile`` under the
+    guess pulses -- from <= 1e-3 theta_max up to 2.9 theta_max (three sub-steps) and back; the pulses keep their interval
+    values."""
+    new = explicit(obj)
+    M = len(regime_dt(new))
+    if M < RAMP_MIN_INTERVALS:
+        raise ValueError("a ramp needs at least %d intervals" % RAMP_MIN_INTERVALS)
+    _set_dt(new, theta_max * ramp_profile(M) / _largest(new)[1])
+    return new
+
+
+def regime_pulse_ramp(obj, theta_max, periods=1, zeros=True):
+    """Uniform grid (dt x PULSE_RAMP_DT: the drift alone sits at a low degree); every guess pulse is replaced by
+    a_n (0.3 + |guess|) with a_n such that theta_n follows ``ramp_profile`` (a_n >= PULSE_RAMP_FLOOR max a where the drift
+    alone is beyond the level), and is exactly 0.0 on the first and the last interval and on the first interval of the way
+    down that needs no sub-steps."""
+    new = explicit(obj)
+    dt = regime_dt(new)
+    M = len(dt)
+    if M < RAMP_MIN_INTERVALS * periods:
+        raise ValueError("a ramp needs at least %d intervals" % (RAMP_MIN_INTERVALS * periods))
+    _set_dt(new, dt * PULSE_RAMP_DT)
+    new.pulses = [0.3 + np.abs(p) for p in new.pulses]
+    k, rate = _largest(new)
+    drift = series_bounds(new)[k, 0]
+    if drift * regime_dt(new).max() >= theta_max:
+        raise ValueError("the drift alone is beyond theta_max")
+    profile = ramp_profile(M, periods)
+    a = (theta_max * profile / regime_dt(new) - drift) / (rate - drift)
+    a = np.maximum(a, PULSE_RAMP_FLOOR * a.max())
+    new.pulses = [a * p for p in new.pulses]
+    if zeros:
+        falling = [n for n in range(1, M) if profile[n] < 1.0 <= profile[n - 1]]  # (one per period)
+        for n in [0, M - 1] + falling:
+            for p in new.pulses:
+                p[n] = 0.0
+    return new
+
+
+def regime_tiny(obj, factor=1e-7):
+    """Every operator x 1e-7 (degree 2: one product per interval); lambda_a shrinks with it so that the update moves the
+    pulses as much as in the base case."""
+    new = explicit(obj)
+    _scale_operators(new, factor)
+    new.lambdas = [lam * factor for lam in new.lambdas]
+    return new
+
+
+def regime_long(obj, theta_max):
+    """>= 130 intervals (two restarts of an advanced generator, one of them inside the grid) under a pulse ramp with two
+    periods: |eps| spans the envelope's decades inside every 64-interval window."""
+    if len(regime_dt(explicit(obj))) < 130:
+        raise ValueError("the long regime needs at least 130 intervals")
+    return regime_pulse_ramp(obj, theta_max, periods=2)
+
+
+REGIMES = {'ramp': regime_ramp, 'pulse_ramp': regime_pulse_ramp, 'tiny': lambda obj, theta_max: regime_tiny(obj),
+           'long': regime_long}
+
+
+def series_degree_tables(theta_cap=2.0, defect=3e-3):
+    """{'taylor' | 'real' | 'defect': theta thresholds per degree} from the library's exported host code (no GPU)."""
+    import ctypes
+
+    from krotov_amd import _lib
+
+    lib = _lib.load()
+    out = {}
+    for name, call in (('taylor', lambda th, ra: lib.kh_series_tables(0, 0.0, th, ra)),
+                       ('real', lambda th, ra: lib.kh_series_tables(1, 0.0, th, ra)),
+                       ('defect', lambda th, ra: lib.kh_series_tables_defect(0.0, theta_cap, defect, th, ra))):
+        th, ra = (ctypes.c_double * 65)(), (ctypes.c_double * (65 * 65))()
+        assert call(th, ra) == 0
+        out[name] = np.array(th)
+    return out
+
+
+def series_plan(theta, theta_max, tab):
+    """(nsub_n, degree_n) of a sequence theta_n: ``kh_degree_lookup`` restated (sub-steps beyond theta_max; the smallest
+    degree m >= 1 whose threshold tab[m] serves theta_n / nsub_n)."""
+    theta = np.asarray(theta, dtype=np.float64)
+    nsub = np.where(theta > theta_max, np.ceil(theta / theta_max), 1.0).astype(int)
+    th = theta / nsub
+    deg = np.array([next((m for m in range(1, 64) if t <= tab[m]), 64) for t in th])
+    return nsub, deg
+
+
+def _changes(seq):
+    return int(np.count_nonzero(np.diff(np.asarray(seq))))
+
+
+def regime_witness(obj, regime, theta_max, pulses, tables):
+    """Assert that ``obj`` under ``pulses`` (L, nt - 1) really is in ``regime`` (host only).  Evaluated for the objective
+    with the largest theta; returns its (theta, nsub, {table: degrees}) for reports."""
+    theta_all = theta_sequence(obj, pulses)
+    k = int(np.argmax(theta_all.max(axis=1)))
+    theta = theta_all[k]
+    plans = {name: series_plan(theta, theta_max, tab) for name, tab in tables.items()}
+    nsub = plans['taylor'][0]
+    M = len(theta)
+    if regime in ('ramp', 'pulse_ramp', 'long'):
+        assert nsub.max() >= 3, "no interval with three sub-steps"
+        assert np.all(theta_all.min(axis=1) <= theta_max), "no interval without sub-steps"
+        assert theta.max() >= 2.5 * theta_max
+        assert _changes(nsub) >= 4, "sub-step counts change %d times" % _changes(nsub)
+        for name, (_, deg) in plans.items():
+            steps = np.diff(deg)
+            assert len(set(deg.tolist())) >= 4, "%s: degrees %s" % (name, sorted(set(deg.tolist())))
+            assert steps.max() > 0 and steps.min() < 0, "%s: degrees do not rise and fall" % name
+    if regime == 'ramp':
+        assert theta.min() <= 1e-3 * theta_max
+        assert np.ptp(regime_dt(obj)) > 0
+    if regime in ('pulse_ramp', 'long'):
+        eps = np.abs(np.asarray(pulses, dtype=np.float64)).reshape(obj.L, -1)
+        assert np.ptp(regime_dt(obj)) < 1e-12 * regime_dt(obj).max()  # uniform grid
+        guess = np.array(obj.pulses)
+        assert np.all(guess[:, 0] == 0.0) and np.all(guess[:, -1] == 0.0) and np.count_nonzero(guess[0] == 0.0) >= 3
+    if regime == 'tiny':
+        for name, (ns, deg) in plans.items():
+            assert ns.max() == 1 and deg.max() <= 4, "%s: degree %d" % (name, deg.max())
+    if regime == 'long':
+        assert M >= 130 and M % 64 != 0  # restarts at intervals 64 and 128, both inside the grid
+        spans = []
+        for start in range(0, M, 64):
+            w = eps[0, start:start + 64]
+            w = w[w > 0]
+            spans.append(np.log10(w.max() / w.min()))
+        assert max(spans) >= 2.5, "pulse spans %.1f decades inside a restart window" % max(spans)
+    return theta, nsub, {name: p[1] for name, p in plans.items()}
+
+
+def regime_oracle(obj):
+    """The oracle problem of a regime problem: Liouvillian form of a Lindblad case, padded Hilbert form of a mixed one."""
+    if obj.fmt == 'lindblad':
+        return obj.oracle()
+    if obj.fmt == 'mixed':  # zero-padded to the stride, Liouvillians L as i L (Hilbert form)
+        S = obj.N
+
+        def pad(a, shape):
+            out = np.zeros(shape, dtype=np.complex128)
+            out[tuple(slice(0, n) for n in a.shape)] = a
+            return out
+
+        def vec(state):
+            arr = np.asarray(state, dtype=np.complex128)
+            return arr.ravel(order='F') if arr.ndim == 2 and arr.shape[0] == arr.shape[1] and arr.shape[0] > 1 else arr.ravel()
+
+        ops = [[pad((1j if obj.kinds[k] else 1.0) * op, (S, S)) for op in [obj.H0[k]] + list(obj.Hc[k])] for k in range(obj.K)]
+        return ko.OracleProblem(ops, np.array([pad(vec(s), (S,)) for s in obj.init]),
+                                np.array([pad(vec(s), (S,)) for s in obj.target]), obj.tlist, is_super=False)
+    return spec_to_oracle(obj)
+
+
+def regime_engine(obj, theta_max=0.0):
+    """The engine of a regime problem (dense, CSR, mixed or Lindblad form)."""
+    from krotov_amd import configs
+    from krotov_amd.engine import HipKrotovEngine
+
+    if obj.fmt == 'lindblad':
+        return HipKrotovEngine(obj.H, obj.dt, c_ops=obj.C, theta_max=theta_max)
+    if obj.fmt == 'csr':
+        ops = configs.sparse_ops(obj)
+    else:
+        ops = [[obj.H0[k]] + [obj.Hc[k][l] for l in range(obj.L)] for k in range(obj.K)]
+    return HipKrotovEngine(ops, regime_dt(obj), is_super=obj.is_super, theta_max=theta_max)
+
+
+class MemoExpm:
+    """Context manager: ``ko.expm_dense`` with a memo on its argument's bytes -- objectives sharing one operator list ask
+    for the same exponential K times per interval.  The values are the oracle's own, bit for bit."""
+
+    def __enter__(self):
+        self._orig, memo = ko.expm_dense, {}
+
+        def expm_dense(A, use_scipy=False):
+            key = (A.shape, bool(use_scipy), hash(A.tobytes()))
+            hit = memo.get(key)
+            if hit is None or not np.array_equal(hit[0], A):
+                if len(memo) >= 512:  # (per-objective operators never hit: keep the memo small)
+                    memo.clear()
+                hit = memo[key] = (np.array(A), self._orig(A, use_scipy))
+            return hit[1]
+
+        ko.expm_dense = expm_dense
+        return self
+
+    def __exit__(self, *exc):
+        ko.expm_dense = self._orig
+        return False
