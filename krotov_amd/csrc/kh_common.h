@@ -425,6 +425,28 @@ __device__ __forceinline__ void kh_publish(const KhExchange &ex, int parity, int
     }
 }
 
+// What a polling wave does after a round that found a stale tag: nap, and every 256th round test the timeout and the
+// abort flag (agent scope, whatever the scope of the polled slots).  Called by the whole wave; t0 and spins are the
+// loop's own, both 0 before the first round.  Returns true when the wave gave up: lane 0 has then raised the abort
+// flag, which ends every other polling wave of the GPU at its next test.
+// (t0 is taken when the first poll fails: s_memrealtime is an SMEM read that the next lgkmcnt wait -- the LDS write of
+// the result -- would sit behind in every interval)
+__device__ __forceinline__ bool kh_poll_gave_up(const KhExchange &ex, int lane, long long &t0, unsigned int &spins) {
+    bool wave_gave_up = false;  // (one return: with a second one inside the test the callers' register counts move)
+    __builtin_amdgcn_s_sleep(1);
+    if (spins == 0) t0 = wall_clock64();
+    if ((++spins & 255u) == 0) {  // wave-uniform
+        const bool gave_up =
+            (wall_clock64() - t0 > ex.timeout_ticks) ||
+            (__hip_atomic_load(ex.abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u);
+        if (__any(gave_up)) {
+            if (lane == 0) __hip_atomic_store(ex.abort_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            wave_gave_up = true;
+        }
+    }
+    return wave_gave_up;
+}
+
 #define KH_GATHER_CHUNKS 4  // workgroups per lane (default): the exchange handles up to 256 workgroups
 #define KH_GATHER_CHUNKS_WIDE 8  // two 256-thread workgroups per CU: up to 512
 
@@ -451,8 +473,7 @@ __device__ __forceinline__ bool kh_gather_range(const KhExchange &ex, int parity
     L -= l0;  // (controls left from l0 on; the slot stride below keeps the full count)
     const int Lfull = L + l0;
     kh_u64 a[MAXL][CH], b[MAXL][CH];
-    long long t0 = 0;  // (taken when the first poll fails: s_memrealtime is an SMEM read that the next lgkmcnt wait -- the
-                       // LDS write of the result -- would sit behind in every interval)
+    long long t0 = 0;
     unsigned int spins = 0;
     // a poll issued before the slowest producer's store has reached the memory
     // side costs a whole extra round trip: give the stores a head start
@@ -479,17 +500,7 @@ __device__ __forceinline__ bool kh_gather_range(const KhExchange &ex, int parity
             for (int c = 0; c < CH; ++c)
                 ok = ok && ((unsigned int)(a[l][c] >> 32) == epoch) && ((unsigned int)(b[l][c] >> 32) == epoch);
         if (__all(ok)) break;
-        __builtin_amdgcn_s_sleep(1);
-        if (spins == 0) t0 = wall_clock64();
-        if ((++spins & 255u) == 0) {  // wave-uniform
-            const bool gave_up =
-                (wall_clock64() - t0 > ex.timeout_ticks) ||
-                (__hip_atomic_load(ex.abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u);
-            if (__any(gave_up)) {
-                if (lane == 0) __hip_atomic_store(ex.abort_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                return false;
-            }
-        }
+        if (kh_poll_gave_up(ex, lane, t0, spins)) return false;
     }
 #ifdef KH_TIMING
     if (lane == 0 && blockIdx.x == 0 && blockIdx.y == 0) ex.abort_flag[1] += spins + 1u;  // polling rounds (workgroup 0)
@@ -535,17 +546,7 @@ __device__ __forceinline__ bool kh_gather_one(const KhExchange &ex, int parity, 
         for (int c = 0; c < CH; ++c)
             ok = ok && ((unsigned int)(a[c] >> 32) == epoch) && ((unsigned int)(b[c] >> 32) == epoch);
         if (__all(ok)) break;
-        __builtin_amdgcn_s_sleep(1);
-        if (spins == 0) t0 = wall_clock64();
-        if ((++spins & 255u) == 0) {  // wave-uniform
-            const bool gave_up =
-                (wall_clock64() - t0 > ex.timeout_ticks) ||
-                (__hip_atomic_load(ex.abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u);
-            if (__any(gave_up)) {
-                if (lane == 0) __hip_atomic_store(ex.abort_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                return false;
-            }
-        }
+        if (kh_poll_gave_up(ex, lane, t0, spins)) return false;
     }
     double acc = 0.0;
 #pragma unroll
@@ -589,7 +590,7 @@ __device__ __forceinline__ bool kh_p2p_gather(const KhExchange &ex, int parity, 
     const bool active = lane < pairs;
     const kh_u64 *g = ex.my_window + ((size_t)parity * ex.world * L + (active ? lane : 0)) * 2;
     kh_u64 a = 0, b = 0;
-    long long t0 = 0;  // (taken when the first poll fails, see kh_gather)
+    long long t0 = 0;
     unsigned int spins = 0;
     for (;;) {
         if (active) {
@@ -598,17 +599,7 @@ __device__ __forceinline__ bool kh_p2p_gather(const KhExchange &ex, int parity, 
         }
         const bool ok = !active || (((unsigned int)(a >> 32) == epoch) && ((unsigned int)(b >> 32) == epoch));
         if (__all(ok)) break;
-        __builtin_amdgcn_s_sleep(1);
-        if (spins == 0) t0 = wall_clock64();
-        if ((++spins & 255u) == 0) {
-            const bool gave_up =
-                (wall_clock64() - t0 > ex.timeout_ticks) ||
-                (__hip_atomic_load(ex.abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u);
-            if (__any(gave_up)) {
-                if (lane == 0) __hip_atomic_store(ex.abort_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                return false;
-            }
-        }
+        if (kh_poll_gave_up(ex, lane, t0, spins)) return false;
     }
     const kh_u64 bits = ((a & 0xffffffffull) << 32) | (b & 0xffffffffull);
     const double v = active ? __longlong_as_double((long long)bits) : 0.0;
@@ -667,4 +658,62 @@ __device__ __forceinline__ bool kh_exchange(const KhExchange &ex, int n, int wg,
                                             const double *part, double (&out)[MAXL]) {
     kh_exchange_publish(ex, n, wg, L, lane, part);
     return kh_exchange_collect<MAXL, CH, P2P>(ex, n, wg, L, lane, part, out);
+}
+
+// The same exchange with one wave per control (kh_tilen.h, kh_ell.h, kh_tile64x.h: workgroups of more than KH_MAX_L
+// waves): wave 0 publishes, waves 0 .. L - 1 gather one control each side by side (kh_gather_one), and the results meet
+// in LDS -- D[l] the sum of control l, ok[l] != 0.0: it arrived.  Before the caller's __syncthreads() (its own, so that a
+// kernel keeps what it has in flight across it): kh_exchange_waves_publish, called by wave 0 from the block that holds
+// its `part` (KH_MAX_L values, zero from L on; declared any wider, the array stays in registers through the interval),
+// then kh_exchange_waves_gather, called by every wave.  After it: kh_exchange_waves_finish, every wave.
+__device__ __forceinline__ void kh_exchange_waves_publish(const KhExchange &ex, int n, int wg, int L, int lane,
+                                                          const double *part, double *D, double *ok) {
+    if (ex.G == 1) {
+        if (lane == 0)
+            for (int l = 0; l < L; ++l) {
+                D[l] = part[l];
+                ok[l] = 1.0;
+            }
+    }
+    if (ex.G > 1) kh_publish(ex, n & 1, wg, L, lane, part, (unsigned)(n + 1));
+}
+__device__ __forceinline__ void kh_exchange_waves_gather(const KhExchange &ex, int n, int L, int wave, int lane, double *D,
+                                                         double *ok) {
+    if (ex.G > 1 && wave < L) {
+        double Dl = 0.0;
+        const bool arrived = kh_gather_one<KH_GATHER_CHUNKS>(ex, n & 1, L, wave, (unsigned)(n + 1), lane, Dl);
+        if (lane == 0) {
+            D[wave] = Dl;
+            ok[wave] = arrived ? 1.0 : 0.0;
+        }
+    }
+}
+// After the barrier: the GPUs' sums through the peer windows (wave 0; objectives sharded over GPUs), one more barrier
+// in that case, and the verdict -- false: a gather gave up, the kernel returns.
+__device__ __forceinline__ bool kh_exchange_waves_finish(const KhExchange &ex, int n, int wg, int L, int wave, int lane,
+                                                         double *D_sh, double *ok_sh) {
+    if (ex.world > 1) {
+        if (wave == 0) {
+            double D[KH_MAX_L];
+            bool ok = true;
+            for (int l = 0; l < KH_MAX_L; ++l) {
+                D[l] = l < L ? D_sh[l] : 0.0;
+                ok = ok && (l >= L || ok_sh[l] != 0.0);
+            }
+            const unsigned int epoch = ex.epoch_base + (unsigned)(n + 1);
+            if (ok) {
+                if (wg == 0 && n != ex.fail_at) kh_p2p_publish(ex, n & 1, L, lane, D, epoch);
+                ok = kh_p2p_gather<KH_MAX_L>(ex, n & 1, L, epoch, lane, D);
+            }
+            if (lane == 0)
+                for (int l = 0; l < L; ++l) {
+                    D_sh[l] = D[l];
+                    ok_sh[l] = ok ? 1.0 : 0.0;
+                }
+        }
+        __syncthreads();
+    }
+    bool all_ok = true;
+    for (int l = 0; l < L; ++l) all_ok = all_ok && ok_sh[l] != 0.0;
+    return all_ok;
 }

@@ -501,64 +501,14 @@ kh_ell_forward_update(KhSweepArgs p, const KhEll *__restrict__ ells, const int *
                     for (int w = 0; w < T / 64; ++w) acc += s.red[w * KH_MAX_L + l];
                 part[l] = chi_norm * acc;
             }
-            if (ex.G == 1) {
-                if (lane == 0)
-                    for (int l = 0; l < L; ++l) {
-                        s.D[l] = part[l];
-                        s.ok[l] = 1.0;
-                    }
-            }
-            if (ex.G > 1) kh_publish(ex, n & 1, k, L, lane, part, (unsigned)(n + 1));
+            kh_exchange_waves_publish(ex, n, k, L, lane, part, s.D, s.ok);
         }
-        if (ex.G > 1 && wave < L) {
-            double Dl = 0.0;
-            const bool ok = kh_gather_one<KH_GATHER_CHUNKS>(ex, n & 1, L, wave, (unsigned)(n + 1), lane, Dl);
-            if (lane == 0) {
-                s.D[wave] = Dl;
-                s.ok[wave] = ok ? 1.0 : 0.0;
-            }
-        }
+        kh_exchange_waves_gather(ex, n, L, wave, lane, s.D, s.ok);
         __syncthreads();
-        if (ex.world > 1) {  // objectives sharded over GPUs: the GPUs' sums through the peer windows
-            if (wave == 0) {
-                double D[KH_MAX_L];
-                bool ok = true;
-                for (int l = 0; l < KH_MAX_L; ++l) {
-                    D[l] = l < L ? s.D[l] : 0.0;
-                    ok = ok && (l >= L || s.ok[l] != 0.0);
-                }
-                const unsigned int epoch = ex.epoch_base + (unsigned)(n + 1);
-                if (ok) {
-                    if (k == 0 && n != ex.fail_at) kh_p2p_publish(ex, n & 1, L, lane, D, epoch);
-                    ok = kh_p2p_gather<KH_MAX_L>(ex, n & 1, L, epoch, lane, D);
-                }
-                if (lane == 0)
-                    for (int l = 0; l < L; ++l) {
-                        s.D[l] = D[l];
-                        s.ok[l] = ok ? 1.0 : 0.0;
-                    }
-            }
-            __syncthreads();
-        }
-        {
-            bool all_ok = true;
-            for (int l = 0; l < L; ++l) all_ok = all_ok && s.ok[l] != 0.0;
-            if (!all_ok) return;
-        }
+        if (!kh_exchange_waves_finish(ex, n, k, L, wave, lane, s.D, s.ok)) return;
         // ---- pulse update (optimize.py:471-477) ----
         const double dt = p.dt[n];
-        double theta = norms_k[0];
-        for (int l = 0; l < L; ++l) {
-            const double stepw = u.shape[(size_t)l * (nt - 1) + n] / u.lambda[l];
-            const double d1 = s.D[l];
-            const double eps = u.guess[(size_t)l * (nt - 1) + n] + stepw * d1;
-            if (tid == l) {
-                s.eps[l] = eps;
-                s.g_a[l] += stepw * (d1 * d1) * dt;
-                if (k == 0) u.opt[(size_t)l * (nt - 1) + n] = eps;
-            }
-            theta += fabs(eps) * norms_k[1 + l];
-        }
+        const double theta = kh_pulse_update(u, norms_k, s.D, n, nt, L, k, tid, dt, s.eps, s.g_a);
         __syncthreads();
         // ---- propagate over interval n with the updated pulses (optimize.py:479-491) ----
         if constexpr (STREAM)

@@ -388,6 +388,27 @@ struct KhUpdateArgs {
                                 // [L][K][nt][N] H_lk^+ chi_k(t_n) (kh_gen_adjoint_side); or NULL
 };
 
+// The pulse update of interval n (optimize.py:471-477) as kh_tilen.h and kh_ell.h do it, called by every thread after the
+// exchange (kh_exchange_waves_finish): thread l writes control l's new value to eps_sh[l], adds its share to g_a_sh[l]
+// and, in workgroup 0, stores the value to u.opt.  Returns theta = ||H0|| + sum_l |eps_l| ||H_l|| of objective k.
+__device__ __forceinline__ double kh_pulse_update(const KhUpdateArgs &u, const double *norms_k, const double *D_sh, int n,
+                                                  int nt, int L, int k, int tid, double dt, double *eps_sh,
+                                                  double *g_a_sh) {
+    double theta = norms_k[0];
+    for (int l = 0; l < L; ++l) {
+        const double stepw = u.shape[(size_t)l * (nt - 1) + n] / u.lambda[l];
+        const double d1 = D_sh[l];
+        const double eps = u.guess[(size_t)l * (nt - 1) + n] + stepw * d1;
+        if (tid == l) {
+            eps_sh[l] = eps;
+            g_a_sh[l] += stepw * (d1 * d1) * dt;
+            if (k == 0) u.opt[(size_t)l * (nt - 1) + n] = eps;
+        }
+        theta += fabs(eps) * norms_k[1 + l];
+    }
+    return theta;
+}
+
 // ---------------------------------------------------------------------------
 // Update sums on the adjoint side (first order, dense operators; round 6)
 // ---------------------------------------------------------------------------

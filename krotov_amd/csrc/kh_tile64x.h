@@ -311,7 +311,6 @@ kh_tx_forward_update(KhSweepArgs p, const cplx *const *__restrict__ tabs, KhUpda
     const double my_lambda = tid < LT ? u.lambda[tid] : 1.0;
 
     for (int n = u.n_begin; n < u.n_end; ++n) {
-        const int par = n & 1;
         cplx ts0[8], ts1[8];
         kh_tx_prefetch<LT, KH_TX_UPDATE_PRE>(tab_k, tid, N, ts0, ts1);
         double my_guess = 0.0, my_stepw = 0.0;  // (in flight while the sums are exchanged)
@@ -325,52 +324,12 @@ kh_tx_forward_update(KhSweepArgs p, const cplx *const *__restrict__ tabs, KhUpda
             double part[KH_MAX_L];
 #pragma unroll
             for (int l = 0; l < KH_MAX_L; ++l) part[l] = l < L ? red[l] : 0.0;
-            if (ex.G == 1) {
-                if (lane == 0)
-                    for (int l = 0; l < L; ++l) {
-                        D_sh[l] = part[l];
-                        ok_sh[l] = 1.0;
-                    }
-            }
-            if (ex.G > 1) kh_publish(ex, par, k, L, lane, part, (unsigned)(n + 1));
+            kh_exchange_waves_publish(ex, n, k, L, lane, part, D_sh, ok_sh);
         }
-        if (ex.G > 1 && wave < L) {
-            double Dl = 0.0;
-            const bool ok = kh_gather_one<KH_GATHER_CHUNKS>(ex, par, L, wave, (unsigned)(n + 1), lane, Dl);
-            if (lane == 0) {
-                D_sh[wave] = Dl;
-                ok_sh[wave] = ok ? 1.0 : 0.0;
-            }
-        }
+        kh_exchange_waves_gather(ex, n, L, wave, lane, D_sh, ok_sh);
         const double dt = kh_uniform(p.dt[n]);
         __syncthreads();
-        if (ex.world > 1) {  // objectives sharded over GPUs: the GPUs' sums through the peer windows
-            if (wave == 0) {
-                double D[KH_MAX_L];
-                bool ok = true;
-#pragma unroll
-                for (int l = 0; l < KH_MAX_L; ++l) {
-                    D[l] = l < L ? D_sh[l] : 0.0;
-                    ok = ok && (l >= L || ok_sh[l] != 0.0);
-                }
-                const unsigned int epoch = ex.epoch_base + (unsigned)(n + 1);
-                if (ok) {
-                    if (k == 0 && n != ex.fail_at) kh_p2p_publish(ex, par, L, lane, D, epoch);
-                    ok = kh_p2p_gather<KH_MAX_L>(ex, par, L, epoch, lane, D);
-                }
-                if (lane == 0)
-                    for (int l = 0; l < L; ++l) {
-                        D_sh[l] = D[l];
-                        ok_sh[l] = ok ? 1.0 : 0.0;
-                    }
-            }
-            __syncthreads();
-        }
-        {
-            bool all_ok = true;
-            for (int l = 0; l < L; ++l) all_ok = all_ok && ok_sh[l] != 0.0;
-            if (!all_ok) return;
-        }
+        if (!kh_exchange_waves_finish(ex, n, k, L, wave, lane, D_sh, ok_sh)) return;
         // ---- pulse update (optimize.py:471-477): thread l = control l, its guess and step width fetched before the exchange ----
         if (tid < LT) {
             const double d1 = D_sh[tid];
