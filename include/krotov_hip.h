@@ -374,10 +374,15 @@ int kh_series_tables_defect(double tol, double theta_cap, double defect, double 
  * hold.  KH_ERR_UNSUPPORTED when N > 2048 or a row is wider than 32 entries (16 for N > 512, 8 for N > 1024): such
  * engines run the STREAMED form of the same kernels (kh_engine_kernel: "ellstream/csr"; N <= 4096, rows up to 32 entries:
  * the same arrays with S = N rounded up to 64, read from memory in every term instead of living in registers), and
- * the generic CSR kernels beyond that (N <= 2540: their vectors must fit LDS). */
+ * the generic CSR kernels beyond that (N <= 2540: their vectors must fit LDS).  What none of these holds -- N > 4096, or
+ * N > 2540 with a row wider than 32 -- runs the form with every vector in global memory ("ellglobal/csr", N <= 2^20):
+ * kh_ell_layout_global gives its arrays, the streamed form's (S = N rounded up to 64) with rows of any width;
+ * KH_ERR_UNSUPPORTED when N > 2^20. */
 int32_t kh_ell_rows_of(int32_t N);
 int kh_ell_layout(int32_t N, int32_t n_ops, const kh_csr *ops_host, int32_t *E, int32_t *Ec, int32_t *off,
                   kh_cdouble *vals, int32_t E_cap);
+int kh_ell_layout_global(int32_t N, int32_t n_ops, const kh_csr *ops_host, int32_t *E, int32_t *Ec, int32_t *off,
+                         kh_cdouble *vals, int32_t E_cap);
 
 /* Test hook (no counterpart in the reference): keep `workgroups` CUs busy for `milliseconds` on `stream` with a
  * kernel that does nothing but hold a CU's LDS -- the situation the single-launch update sweep must survive

@@ -117,6 +117,8 @@ SYMBOLS = {
     'kh_ell_rows_of': (ctypes.c_int32, [ctypes.c_int32]),
     'kh_ell_layout': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, _P, ctypes.POINTER(ctypes.c_int32),
                                      ctypes.POINTER(ctypes.c_int32), _P, _P, ctypes.c_int32]),
+    'kh_ell_layout_global': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, _P, ctypes.POINTER(ctypes.c_int32),
+                                            ctypes.POINTER(ctypes.c_int32), _P, _P, ctypes.c_int32]),
 }
 
 _lib = None

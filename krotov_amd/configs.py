@@ -21,6 +21,7 @@ __all__ = [
     'config_c3',
     'config_c4',
     'config_c5',
+    'config_spin_chain',
     'config_mixed',
     'mixed_to_objectives',
     'spec_to_objectives',
@@ -372,6 +373,55 @@ def sparse_ops(spec):
         return made[id(a)][0]
 
     return [[conv(spec.H0[k])] + [conv(spec.Hc[k][l]) for l in range(spec.L)] for k in range(spec.K)]
+
+
+def config_spin_chain(n=13, nt=4, K=2, J=1.0, h=0.5, dt=0.1):
+    """An open Ising chain of ``n`` spins in Hilbert space (N = 2^n): diagonal drift ``J sum_i Z_i Z_{i+1}`` plus a
+    fixed transverse field ``h sum_i X_i``, one control on ``sum_i Z_i``; objective k takes the basis state |k> to the
+    state with every spin flipped.  ``H0`` / ``Hc`` hold ``scipy.sparse`` CSR matrices (n + 1 entries per row) built
+    directly as Kronecker products -- nothing dense is ever formed, so the builder serves n = 13 (N = 8192) and
+    beyond, where sparse operators are the only form that fits; :func:`sparse_ops` passes them on as they are."""
+    import scipy.sparse as sp
+
+    N = 2 ** n
+    X = sp.csr_matrix(np.array([[0.0, 1.0], [1.0, 0.0]], dtype=np.complex128))
+    Z = sp.csr_matrix(np.array([[1.0, 0.0], [0.0, -1.0]], dtype=np.complex128))
+
+    def site(op, i, op2=None):
+        """op on spin i (and op2 on spin i + 1), the identity elsewhere"""
+        out = sp.identity(1, dtype=np.complex128, format='csr')
+        for j in range(n):
+            f = op if j == i else (op2 if op2 is not None and j == i + 1 else sp.identity(2, dtype=np.complex128, format='csr'))
+            out = sp.kron(out, f, format='csr')
+        return out
+
+    H0 = sp.csr_matrix((N, N), dtype=np.complex128)
+    H1 = sp.csr_matrix((N, N), dtype=np.complex128)
+    for i in range(n - 1):
+        H0 = H0 + J * site(Z, i, Z)
+    for i in range(n):
+        H0 = H0 + h * site(X, i)
+        H1 = H1 + site(Z, i)
+    H0, H1 = sp.csr_matrix(H0), sp.csr_matrix(H1)
+    for m in (H0, H1):
+        m.sum_duplicates()
+        m.sort_indices()
+    T = dt * (nt - 1)
+    init = np.zeros((K, N), dtype=np.complex128)
+    init[np.arange(K), np.arange(K)] = 1.0
+    target = np.zeros((K, N), dtype=np.complex128)
+    target[np.arange(K), N - 1 - np.arange(K)] = 1.0
+
+    def guess(t, args):
+        return 0.3 * np.sin(np.pi * t / T) ** 2 + 0.05
+
+    def S(t):
+        return _shapes.flattop(t, t_start=0.0, t_stop=T, t_rise=0.2 * T, func='sinsq')
+
+    return ProblemSpec(
+        name='spin_chain_n%d' % n, H0=[H0] * K, Hc=[[H1]] * K, is_super=False, init=init, target=target,
+        tlist=np.linspace(0, T, nt), controls=[guess], update_shape=S, lambda_a=2.0, chi='re',
+    )
 
 
 # --------------------------------------------------------------------------

@@ -31,6 +31,8 @@
 #include "kh_coop.h"
 #elif KH_TU == KH_TU_ELL_STORE || KH_TU == KH_TU_ELL_UPDATE_A || KH_TU == KH_TU_ELL_UPDATE_B
 #include "kh_ell.h"
+#elif KH_TU == KH_TU_ELLG
+#include "kh_ellg.h"
 #else
 #error "unknown KH_TU"
 #endif

@@ -36,6 +36,7 @@
 #include "kh_coop.h"
 #include "kh_mini.h"
 #include "kh_ell.h"
+#include "kh_ellg.h"
 #include "kh_tilen.h"
 #include "kh_ens.h"
 #include "kh_lind.h"
@@ -75,7 +76,7 @@ enum KernelKind { KIND_GENERIC = 0, KIND_TILE_RPT2 = 1, KIND_TILE_RPT1 = 2, KIND
 // Switches, read from the environment ONCE, at creation (read_switches; not per launch, not per process: engines with
 // different settings coexist)
 struct KhSwitches {
-    std::string kernel;  // KH_KERNEL (testing): "generic" | "tile256" | "tile512" | "q2" | "mini" | "coop" | "tilen" | "tilex" | "ellstream"
+    std::string kernel;  // KH_KERNEL (testing): "generic" | "tile256" | "tile512" | "q2" | "mini" | "coop" | "tilen" | "tilex" | "ellstream" | "ellglobal"
     bool kernel_set = false;
     bool kernel_is(const char *name) const { return kernel_set && kernel == name; }
     bool taylor, no_adj, near_imag, ellstream, stepwise, stream, coop_xcd, coop_sq, coop_adj, tn_h1reg, tx, q2_store, ens2, gen_adj;
@@ -148,6 +149,7 @@ struct KhFacts {
     bool csr, shared;            // sparse operators; every objective has the same operator list
     bool has_h1, all_h1;         // objective 0 / every objective has its first control
     bool ell = false, ell_stream = false;  // the padded row form (kh_ell.h) was built, in its streamed form
+    bool ell_global = false;     // ... in the form with its vectors in global memory (kh_ellg.h; ell_stream: its pools)
     int ell_E = 0;               // ... widest row over all objectives and both directions
     int ens_ncg = 0;             // column groups of the ensemble kernel where the detection found (H0, s_k H1), else 0
     double adj_sign = 0.0;       // +1 / -1: every control operator equals +/- its adjoint exactly (else 0)
@@ -173,6 +175,7 @@ struct KhPlan {
     int tn_EP = 0;
     bool tx = false, tx_update = false;    // kh_tile64x.h lane-order copies (plain sweeps); its update sweep too
     bool ell_stream = false;               // kh_ell.h: streamed form, row width
+    bool ell_global = false;               // kh_ellg.h: the streamed form's pools, every vector in global memory
     int ell_E = 0;
     bool ens = false, ens2 = true;         // kh_ens.h: the single-launch update sweep, whatever `kind` says; the A^2-chain form
     int ens_ncg = 0, ens_G = 0;
@@ -226,6 +229,9 @@ struct kh_engine {
     bool gen_fits = true;             // the generic kernels' LDS vectors fit (N <= 2540)
     cplx *d_ell_scratch = nullptr;    // the streamed padded-row form's per-workgroup scratch planes [workgroups][stride]
     long long ell_scratch_stride = 0;
+    cplx *d_ellg_ws = nullptr;        // kh_ellg.h: per-workgroup workspaces [ellg_wgs][stride] (term planes, running sum, values)
+    long long ellg_ws_stride = 0;
+    int ellg_wgs = 0;
     const cplx **d_coop_fops_fw = nullptr, **d_coop_fops_bw = nullptr;  // [1+L] fragment-ordered operator copies
     const cplx **d_coop_sq_fw = nullptr, **d_coop_sq_bw = nullptr;      // [3] the same for P0, P1, P2 (one control)
     kh_u64 *d_coop_vbuf = nullptr;
@@ -433,7 +439,7 @@ static int check_residency(const kh_engine *e, const void *func, int threads, si
     return KH_OK;
 }
 
-extern "C" const char *kh_version(void) { return "krotov_hip 0.6 (gfx950; tile64q2, tile64, tile64/stream, tile64x, ens64/mfma, mini16, mini4, coop16/mfma, ell/csr, ellstream/csr, tile128, generic, generic/csr, generic/mixed, lindblad/matrix kernels)"; }
+extern "C" const char *kh_version(void) { return "krotov_hip 0.6 (gfx950; tile64q2, tile64, tile64/stream, tile64x, ens64/mfma, mini16, mini4, coop16/mfma, ell/csr, ellstream/csr, ellglobal/csr, tile128, generic, generic/csr, generic/mixed, lindblad/matrix kernels)"; }
 
 extern "C" const char *kh_engine_kernel(const kh_engine *e) {
     if (e == nullptr) return "";
@@ -446,7 +452,7 @@ extern "C" const char *kh_engine_kernel(const kh_engine *e) {
         case KIND_TILE_RPT1: return p.stepwise_only ? (p.stream ? "tile64/stream" : "tile64/512 per interval") : "tile64/512";
         case KIND_TILE_Q2: return p.mini ? (p.quad ? "mini4/wave" : "mini16/wave") : "tile64q2/512";
         case KIND_COOP: return "coop16/mfma";
-        case KIND_ELL: return p.ell_stream ? "ellstream/csr" : "ell/csr";
+        case KIND_ELL: return p.ell_global ? "ellglobal/csr" : (p.ell_stream ? "ellstream/csr" : "ell/csr");
         case KIND_TILEN: return "tile128/512";
         default: return e->d_csr_fw != nullptr ? "generic/csr" : (p.tx ? "tile64x/512" : "generic");
     }
@@ -631,7 +637,7 @@ static double csr_part_fro2(const HostCsr &a, const HostCsr &adj, double sign) {
 // the union of the patterns, entries some control touches first.  Returns false when a row is wider than the kernels'
 // register budget (kh_ell_emax(N): 32 entries with one row per lane, 16 with two, 8 with three or four).
 static bool build_ell_host(const std::vector<const HostCsr *> &ops, int N, std::vector<int> &off, std::vector<cplx> &vals,
-                           int &E, int &Ec, bool stream = false) {
+                           int &E, int &Ec, bool stream = false, bool any_width = false) {
     const int Lp1 = (int)ops.size();
     std::vector<std::vector<std::pair<int, int>>> rows(N);  // (column, touched by a control)
     E = Ec = 0;
@@ -654,7 +660,8 @@ static bool build_ell_host(const std::vector<const HostCsr *> &ops, int N, std::
         Ec = std::max(Ec, nc);
     }
     // (stream: the pools of the streamed kernels -- nothing lives in registers, so rows up to 32 entries for any N they take)
-    const int emax = stream ? KH_ELL_EMAX : kh_ell_emax(N), S = stream ? (N + 63) / 64 * 64 : kh_ell_rows(N);
+    // (any_width: the pools of kh_ellg.h, which loops over a row's entries at run time)
+    const int emax = any_width ? INT_MAX - 3 : (stream ? KH_ELL_EMAX : kh_ell_emax(N)), S = stream ? (N + 63) / 64 * 64 : kh_ell_rows(N);
     if (E > emax) return false;
     // every row: its control-touched entries in slots [0, Ec), the others behind them from slot Ec on (so that a rebuild
     // of slots [0, Ec) never touches a drift-only entry); padding: value 0, the lane's own row
@@ -735,6 +742,7 @@ static KhPlan plan_families(const KhFacts &f, const KhSwitches &sw) {
         return p;
     }
     p.ell_stream = f.ell_stream;
+    p.ell_global = f.ell_global;
     p.ell_E = f.ell_E;
     const bool tile_shape = dense && N <= KH_TILE_N && L >= 1 && L <= 4;
     const bool tile_ok = tile_shape && K <= max_wgs;
@@ -846,6 +854,12 @@ static KhPlan plan_families(const KhFacts &f, const KhSwitches &sw) {
         if (K <= max_wgs) {
             p.kind = KIND_ELL;
             p.grid_update = K;
+        }
+        // vectors in global memory (kh_ellg.h): a workgroup takes its objectives in turns, so any K runs -- on
+        // min(K, #CUs) workgroups, or fewer (kh_set_update_workgroups)
+        if (f.ell_global) {
+            p.kind = KIND_ELL;
+            p.grid_update = K < max_wgs ? K : max_wgs;
         }
         // a term of the series costs a workgroup-wide round whatever it multiplies: fewer, longer sub-steps pay, as
         // for the cooperative kernels (theta <= 4: round-off ~ e^theta eps per step, far inside the parity budget);
@@ -1060,7 +1074,9 @@ static int detect_dense(kh_engine *e, const kh_problem *pr, KhFacts &f) {
 // Sparse operators: the same questions asked of canonical host copies, and the padded row form (kh_ell.h), one structure
 // per distinct operator list and direction: the matrix in registers where the rows fit (N <= 2048), else -- or with
 // KH_KERNEL=ellstream -- the streamed form (N <= 4096, rows up to 32 entries): the same pools with their own row count,
-// read per term.
+// read per term.  Where neither applies and the generic kernels cannot hold N either (N > 4096, or N > 2540 with a row
+// wider than 32) -- or with KH_KERNEL=ellglobal -- the streamed form's pools with rows of any width and every vector in
+// global memory (kh_ellg.h, N <= 2^20).
 static int build_sparse(kh_engine *e, const kh_problem *pr, const kh_csr *csr_fw, const kh_csr *csr_bw,
                         const std::vector<const cplx *> &fw, KhFacts &f) {
     const size_t nops = fw.size();
@@ -1087,11 +1103,12 @@ static int build_sparse(kh_engine *e, const kh_problem *pr, const kh_csr *csr_fw
         }
         KH_TRY(classify_operators(e, pr, ctl_plus, ctl_minus, drift_plus, [&](double &v) { return v = fro2, KH_OK; }, f));
     }
-    const bool want_stream = e->sw.kernel_is("ellstream");
-    for (int form = want_stream ? 1 : 0; form < 2 && !f.ell; ++form) {
-        const bool stream = form == 1;
-        if (e->N > (stream ? KH_ELLS_NMAX : KH_ELL_NMAX) || e->L > KH_MAX_L || e->sw.kernel_is("generic")) continue;
-        if (stream && !e->sw.ellstream) continue;
+    const bool want_stream = e->sw.kernel_is("ellstream"), want_global = e->sw.kernel_is("ellglobal");
+    for (int form = want_global ? 2 : (want_stream ? 1 : 0); form < 3 && !f.ell; ++form) {
+        const bool global = form == 2, stream = form >= 1;
+        if (e->N > (global ? KH_ELLG_NMAX : (stream ? KH_ELLS_NMAX : KH_ELL_NMAX)) || e->L > KH_MAX_L || e->sw.kernel_is("generic")) continue;
+        if (form == 1 && !e->sw.ellstream) continue;
+        if (global && !want_global && e->gen_fits) continue;  // (only where nothing else runs: every other dispatch keeps its family)
         bool ok = true;
         int E_max = 0, ec_max = 0;
         std::map<std::vector<const void *>, std::pair<KhEll, KhEll>> made;
@@ -1110,7 +1127,7 @@ static int build_sparse(kh_engine *e, const kh_problem *pr, const kh_csr *csr_fw
                     std::vector<int> off;
                     std::vector<cplx> vals;
                     int E = 0, Ec = 0;
-                    ok = build_ell_host(ops_h, e->N, off, vals, E, Ec, stream);
+                    ok = build_ell_host(ops_h, e->N, off, vals, E, Ec, stream, global);
                     if (!ok) break;
                     ec_max = std::max(ec_max, Ec);
                     pair[dir].off_at = (long long)off_pool.size();
@@ -1132,12 +1149,19 @@ static int build_sparse(kh_engine *e, const kh_problem *pr, const kh_csr *csr_fw
         if (!ok) continue;
         f.ell = true;
         f.ell_stream = stream;
+        f.ell_global = global;
         f.ell_E = E_max;
         KH_TRY(dev_upload(e, &e->d_ell_off, off_pool.data(), sizeof(int) * off_pool.size()));
         KH_TRY(dev_upload(e, &e->d_ell_vals, vals_pool.data(), sizeof(cplx) * vals_pool.size()));
         KH_TRY(dev_upload(e, &e->d_ell_fw, ell_fw.data(), sizeof(KhEll) * e->K));
         KH_TRY(dev_upload(e, &e->d_ell_bw, ell_bw.data(), sizeof(KhEll) * e->K));
-        if (stream) {
+        if (global) {
+            // one workspace per workgroup, here and not at the first launch: the plain sweeps and the update sweep run on
+            // at most min(K, #CUs) workgroups
+            e->ellg_ws_stride = kh_ellg_ws_stride(e->N, ec_max);
+            e->ellg_wgs = e->K < e->num_cus ? e->K : e->num_cus;
+            KH_TRY(dev_alloc(e, &e->d_ellg_ws, sizeof(cplx) * (size_t)e->ellg_ws_stride * e->ellg_wgs));
+        } else if (stream) {
             // one scratch plane per workgroup (update sweep: K of them; plain sweeps: at most one per CU)
             e->ell_scratch_stride = (long long)std::max(ec_max, 4) * ((e->N + 63) / 64 * 64);
             const int wgs = e->K < e->num_cus ? e->K : e->num_cus;  // (the update sweep takes K <= #CUs workgroups, the plain sweeps at most #CUs)
@@ -1284,11 +1308,12 @@ static int engine_build(kh_engine *e, const kh_problem *pr, const kh_csr *csr_fw
     KH_HIP(hipGetDeviceProperties(&prop, e->device));
     e->num_cus = prop.multiProcessorCount;
     // the generic kernels -- every engine's last resort -- keep four vectors of N elements in LDS: N <= 2540.  Sparse
-    // operators up to N = 4096 may still run the streamed padded-row kernels (gen_fits stays false then and whatever
-    // would need the generic kernels -- one launch per interval, more objectives than CUs -- is refused)
+    // operators may still run the padded-row kernels -- streamed up to N = 4096, with their vectors in global memory up to
+    // N = 2^20 -- (gen_fits stays false then and whatever would need the generic kernels -- one launch per interval -- is
+    // refused)
     const size_t gen_lds = kh_gen_lds_bytes(e->N, csr_fw == nullptr);
     e->gen_fits = !(gen_lds > (size_t)prop.sharedMemPerBlock && gen_lds > 160 * 1024);
-    if (!e->gen_fits && !(csr_fw != nullptr && e->N <= KH_ELLS_NMAX))
+    if (!e->gen_fits && !(csr_fw != nullptr && e->N <= KH_ELLG_NMAX))
         return kh_fail(KH_ERR_UNSUPPORTED, "N=%d needs %zu bytes of LDS", e->N, gen_lds);
 
     // ---- facts
@@ -1311,7 +1336,7 @@ static int engine_build(kh_engine *e, const kh_problem *pr, const kh_csr *csr_fw
         KH_TRY(build_sparse(e, pr, csr_fw, csr_bw, fw, f));
     }
     if (!e->gen_fits && !f.ell)
-        return kh_fail(KH_ERR_UNSUPPORTED, "N=%d: rows wider than 32 entries and no room for the generic kernels' vectors in LDS", e->N);
+        return kh_fail(KH_ERR_UNSUPPORTED, "N=%d: no padded-row form for this problem (more than %d controls, or KH_KERNEL) and no room for the generic kernels' vectors in LDS", e->N, KH_MAX_L);
     if (const int ncg = ens_candidate(f, e->sw)) {
         bool found = false;
         KH_TRY(detect_ensemble(e, fw, found));
@@ -1944,6 +1969,12 @@ static int sweep_store(kh_engine *e, bool backward, const double *pulses, const 
         }
         case KIND_ELL: {
             const KhEll *ells = backward ? e->d_ell_bw : e->d_ell_fw;
+            if (pl.ell_global) {
+                launch_plain<kh_ellg_sweep_store<KH_ELLG_THREADS>>(dim3(e->ellg_wgs), dim3(KH_ELLG_THREADS), kh_ellg_lds_bytes(), st, p, ells,
+                                                                   (const int *)e->d_ell_off, (const cplx *)e->d_ell_vals, pulses, in, store, out,
+                                                                   direction, e->d_ellg_ws, e->ellg_ws_stride);
+                break;
+            }
             const int grid = pl.ell_stream ? grid_cus : (e->K < 4 * e->num_cus ? e->K : 4 * e->num_cus);
             // (two vector buffers of KH_ELL_NMAX elements: more than the 64 KiB a kernel gets without asking)
             const size_t lds = kh_ell_lds_bytes(pl.ell_stream);
@@ -2044,6 +2075,7 @@ static KhRoute update_route(const KhPlan &p, int K, bool stepwise, bool whole, b
         const int ncg = p.ens_cols(K, reduced_G, &G);
         return !so && ncg == 2 && p.ens2 && have_sq && adj_store() ? ROUTE_ENS2 : ROUTE_ENS;
     }
+    if (p.kind == KIND_ELL && p.ell_global && !stepwise) return ROUTE_ELL;  // (any grid: kh_ellg.h)
     if ((p.stream || (reduced_G > 0 && reduced_G < p.grid_update && world == 1)) && whole) return ROUTE_STREAM;
     if (p.kind == KIND_TILE_Q2 && p.quad && whole) return ROUTE_QUAD;
     if (p.kind == KIND_TILE_Q2 && p.mini && whole) return ROUTE_MINI;
@@ -2161,7 +2193,23 @@ static int update_tilen(kh_engine *e, const KhSweepArgs &p, const KhUpdateArgs &
     });
 }
 
+// the padded-row form with its vectors in global memory (kh_ellg.h): a workgroup takes its objectives in turns, so the
+// grid is min(K, #CUs) or what kh_set_update_workgroups allows
+static int update_ellg(kh_engine *e, const KhSweepArgs &p, const KhUpdateArgs &u, const KhExchange &ex, hipStream_t st) {
+    int G = e->plan.grid_update;
+    if (e->reduced_G > 0 && e->reduced_G < G) G = e->reduced_G;
+    KhExchange exg = ex;
+    exg.G = G;
+    e->last_update_grid = G;
+    return with_bool(u.sigma != nullptr, [&](auto so) {
+        return launch_persistent<kh_ellg_forward_update<KH_ELLG_THREADS, decltype(so)::value>>(
+            e, dim3(G), dim3(KH_ELLG_THREADS), kh_ellg_lds_bytes(), st, p, (const KhEll *)e->d_ell_fw, (const int *)e->d_ell_off,
+            (const cplx *)e->d_ell_vals, u, exg, e->d_ellg_ws, e->ellg_ws_stride);
+    });
+}
+
 static int update_ell(kh_engine *e, const KhSweepArgs &p, const KhUpdateArgs &u, const KhExchange &ex, hipStream_t st) {
+    if (e->plan.ell_global) return update_ellg(e, p, u, ex, st);
     const size_t lds = kh_ell_lds_bytes(e->plan.ell_stream);
     return with_ell(e->N, e->plan.ell_E, e->plan.ell_stream, [&](auto t, auto r, auto em, auto stm) {
         return with_bool(u.sigma != nullptr, [&](auto so) {
@@ -2404,9 +2452,14 @@ extern "C" int kh_set_update_workgroups(kh_engine *e, int32_t max_workgroups, in
             return kh_fail(KH_ERR_UNSUPPORTED, "the ensemble kernel needs at least %d workgroups for %d objectives", widest, e->K);
         const void *forms[2];
         KH_TRY(ens_forms(e, p.ens_cols(e->K, max_workgroups, &G), forms));
+    } else if (p.kind == KIND_ELL && p.ell_global) {
+        const int fewest = (e->K + KH_ELLG_MMAX - 1) / KH_ELLG_MMAX;
+        if (max_workgroups < fewest)
+            return kh_fail(KH_ERR_UNSUPPORTED, "%d objectives need at least %d workgroups (%d per workgroup)", e->K, fewest, KH_ELLG_MMAX);
+        G = p.grid_update < max_workgroups ? p.grid_update : max_workgroups;
     } else {
         if (!p.tile_family() || e->d_csr_fw != nullptr || e->N > KH_TILE_N || e->L < 1 || e->L > 4)
-            return kh_fail(KH_ERR_UNSUPPORTED, "only the register-tile families (N <= 64, 1..4 controls) have a form with fewer workgroups");
+            return kh_fail(KH_ERR_UNSUPPORTED, "only the register-tile families (N <= 64, 1..4 controls) and the sparse form with global vectors have a form with fewer workgroups");
         const int fewest = (e->K + KH_STREAM_MMAX - 1) / KH_STREAM_MMAX;
         if (max_workgroups < fewest)
             return kh_fail(KH_ERR_UNSUPPORTED, "%d objectives need at least %d workgroups (%d per workgroup)", e->K, fewest, KH_STREAM_MMAX);
@@ -2765,11 +2818,12 @@ extern "C" int kh_last_stats(kh_engine *e, double stats[4]) {
 
 extern "C" int32_t kh_ell_rows_of(int32_t N) { return N >= 1 && N <= KH_ELL_NMAX ? kh_ell_rows(N) : 0; }
 
-extern "C" int kh_ell_layout(int32_t N, int32_t n_ops, const kh_csr *ops_host, int32_t *E_out, int32_t *Ec_out, int32_t *off_out,
-                             kh_cdouble *vals_out, int32_t E_cap) {
+static int ell_layout(int32_t N, int32_t n_ops, const kh_csr *ops_host, int32_t *E_out, int32_t *Ec_out, int32_t *off_out,
+                      kh_cdouble *vals_out, int32_t E_cap, bool global) {
     if (ops_host == nullptr || E_out == nullptr || Ec_out == nullptr || n_ops < 1 || N < 1)
         return kh_fail(KH_ERR_INVALID, "bad argument");
-    if (N > KH_ELL_NMAX) return kh_fail(KH_ERR_UNSUPPORTED, "N = %d: the padded row form serves N <= %d", N, KH_ELL_NMAX);
+    const int nmax = global ? KH_ELLG_NMAX : KH_ELL_NMAX;
+    if (N > nmax) return kh_fail(KH_ERR_UNSUPPORTED, "N = %d: the padded row form serves N <= %d", N, nmax);
     std::vector<HostCsr> host(n_ops);
     std::vector<const HostCsr *> ptrs(n_ops, nullptr);
     for (int o = 0; o < n_ops; ++o) {
@@ -2781,7 +2835,7 @@ extern "C" int kh_ell_layout(int32_t N, int32_t n_ops, const kh_csr *ops_host, i
     std::vector<int> off;
     std::vector<cplx> vals;
     int E = 0, Ec = 0;
-    if (!build_ell_host(ptrs, N, off, vals, E, Ec))
+    if (!build_ell_host(ptrs, N, off, vals, E, Ec, global, global))
         return kh_fail(KH_ERR_UNSUPPORTED, "rows wider than the kernels' register budget (%d entries for N = %d)", kh_ell_emax(N), N);
     *E_out = E;
     *Ec_out = Ec;
@@ -2791,4 +2845,14 @@ extern "C" int kh_ell_layout(int32_t N, int32_t n_ops, const kh_csr *ops_host, i
         if (vals_out != nullptr) memcpy(vals_out, vals.data(), sizeof(cplx) * vals.size());
     }
     return KH_OK;
+}
+
+extern "C" int kh_ell_layout(int32_t N, int32_t n_ops, const kh_csr *ops_host, int32_t *E_out, int32_t *Ec_out, int32_t *off_out,
+                             kh_cdouble *vals_out, int32_t E_cap) {
+    return ell_layout(N, n_ops, ops_host, E_out, Ec_out, off_out, vals_out, E_cap, false);
+}
+
+extern "C" int kh_ell_layout_global(int32_t N, int32_t n_ops, const kh_csr *ops_host, int32_t *E_out, int32_t *Ec_out,
+                                    int32_t *off_out, kh_cdouble *vals_out, int32_t E_cap) {
+    return ell_layout(N, n_ops, ops_host, E_out, Ec_out, off_out, vals_out, E_cap, true);
 }
