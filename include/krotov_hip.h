@@ -384,6 +384,16 @@ int kh_ell_layout(int32_t N, int32_t n_ops, const kh_csr *ops_host, int32_t *E, 
 int kh_ell_layout_global(int32_t N, int32_t n_ops, const kh_csr *ops_host, int32_t *E, int32_t *Ec, int32_t *off,
                          kh_cdouble *vals, int32_t E_cap);
 
+/* Spread every objective's rows over `workgroups_per_objective` workgroups (kh_engine_kernel: "ellsplit/csr"; no
+ * counterpart in the reference): for sparse problems with a few large objectives, which otherwise use as many compute
+ * units as there are objectives.  Only CSR engines in the form with global vectors ("ellglobal/csr") take it; every
+ * other engine answers KH_ERR_UNSUPPORTED, as do S < 1, S beyond the device's compute units and a sharded engine.  1
+ * restores the kernels of "ellglobal/csr" exactly.  The rows are dealt in 64-row chunks (kh_ellsplit_rows: part `part`
+ * of S owns [*first, *first + *count), possibly nothing; host only); both sweeps then need all their workgroups resident
+ * at once, every in-kernel wait is bounded (kh_check: KH_ERR_TIMEOUT), and kh_set_update_workgroups accepts only 0. */
+int kh_set_row_split(kh_engine *engine, int workgroups_per_objective);
+int kh_ellsplit_rows(int32_t N, int32_t S, int32_t part, int32_t *first, int32_t *count);
+
 /* Test hook (no counterpart in the reference): keep `workgroups` CUs busy for `milliseconds` on `stream` with a
  * kernel that does nothing but hold a CU's LDS -- the situation the single-launch update sweep must survive
  * (another stream of the process holding compute units while its workgroups need to be resident all at once).

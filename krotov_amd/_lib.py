@@ -109,6 +109,9 @@ SYMBOLS = {
     'kh_debug_occupy': (ctypes.c_int, [_P, ctypes.c_int32, ctypes.c_double, _P]),
     'kh_p2p_stats': (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double)]),
     'kh_set_update_workgroups': (ctypes.c_int, [_P, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)]),
+    'kh_set_row_split': (ctypes.c_int, [_P, ctypes.c_int]),
+    'kh_ellsplit_rows': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
+                                        ctypes.POINTER(ctypes.c_int32)]),
     'kh_debug_launched': (ctypes.c_int, [ctypes.c_int32, ctypes.c_char_p, ctypes.c_int32]),
     'kh_series_tables': (ctypes.c_int, [ctypes.c_int32, ctypes.c_double, ctypes.POINTER(ctypes.c_double),
                                         ctypes.POINTER(ctypes.c_double)]),

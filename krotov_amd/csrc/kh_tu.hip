@@ -33,6 +33,8 @@
 #include "kh_ell.h"
 #elif KH_TU == KH_TU_ELLG
 #include "kh_ellg.h"
+#elif KH_TU == KH_TU_ELLGS
+#include "kh_ellgs.h"
 #else
 #error "unknown KH_TU"
 #endif

@@ -37,6 +37,7 @@
 #include "kh_mini.h"
 #include "kh_ell.h"
 #include "kh_ellg.h"
+#include "kh_ellgs.h"
 #include "kh_tilen.h"
 #include "kh_ens.h"
 #include "kh_lind.h"
@@ -76,11 +77,12 @@ enum KernelKind { KIND_GENERIC = 0, KIND_TILE_RPT2 = 1, KIND_TILE_RPT1 = 2, KIND
 // Switches, read from the environment ONCE, at creation (read_switches; not per launch, not per process: engines with
 // different settings coexist)
 struct KhSwitches {
-    std::string kernel;  // KH_KERNEL (testing): "generic" | "tile256" | "tile512" | "q2" | "mini" | "coop" | "tilen" | "tilex" | "ellstream" | "ellglobal"
+    std::string kernel;  // KH_KERNEL (testing): "generic" | "tile256" | "tile512" | "q2" | "mini" | "coop" | "tilen" | "tilex" | "ellstream" | "ellglobal" | "ellsplit"
     bool kernel_set = false;
     bool kernel_is(const char *name) const { return kernel_set && kernel == name; }
     bool taylor, no_adj, near_imag, ellstream, stepwise, stream, coop_xcd, coop_sq, coop_adj, tn_h1reg, tx, q2_store, ens2, gen_adj;
     double ell_cap;
+    int ell_split, ell_groups;  // KH_ELL_SPLIT (0: 'auto'), KH_ELL_GROUPS (0: no cap)
     int stream_G, coop_cols, ens, ens_min_k, ens_ncg;
     bool coop_launch, q2_single, tile_single, coop_single, poll_delay_set, timeout_set;
     int poll_delay, adj_poll_delay, coop_poll_delay;  // (s_sleep units of 64 cycles)
@@ -100,6 +102,8 @@ static KhSwitches read_switches() {
     s.near_imag = !off("KH_NEAR_IMAG");        // =0: Taylor instead of the near-imaginary form's coefficients (A/B)
     s.ell_cap = 0.0;                           // KH_ELL_CAP (> 0): another theta cap of the padded-row kernels' Chebyshev form
     if (const char *d = getenv("KH_ELL_CAP")) s.ell_cap = atof(d);
+    s.ell_split = num("KH_ELL_SPLIT", 0);      // workgroups per objective under KH_KERNEL=ellsplit (unset: 'auto')
+    s.ell_groups = num("KH_ELL_GROUPS", 0);    // at most this many groups of the split form (testing: objectives in turns)
     s.ellstream = !on("KH_NO_ELLSTREAM");      // no streamed padded-row form
     s.stepwise = !on("KH_NO_STEPWISE");        // no register-tile kernel with one launch per interval
     s.stream = !on("KH_NO_STREAM");            // that launch per interval instead of the streaming kernel (A/B)
@@ -232,6 +236,10 @@ struct kh_engine {
     cplx *d_ellg_ws = nullptr;        // kh_ellg.h: per-workgroup workspaces [ellg_wgs][stride] (term planes, running sum, values)
     long long ellg_ws_stride = 0;
     int ellg_wgs = 0;
+    // kh_ellgs.h (kh_set_row_split): S workgroups per objective on `groups` groups; 1: the kernels of kh_ellg.h
+    int row_split = 1, split_groups = 0;
+    unsigned int *d_split_counters = nullptr;  // [groups] barrier counters, a memory line each: one block, zeroed per launch
+    size_t split_counters_bytes = 0;
     const cplx **d_coop_fops_fw = nullptr, **d_coop_fops_bw = nullptr;  // [1+L] fragment-ordered operator copies
     const cplx **d_coop_sq_fw = nullptr, **d_coop_sq_bw = nullptr;      // [3] the same for P0, P1, P2 (one control)
     kh_u64 *d_coop_vbuf = nullptr;
@@ -439,7 +447,7 @@ static int check_residency(const kh_engine *e, const void *func, int threads, si
     return KH_OK;
 }
 
-extern "C" const char *kh_version(void) { return "krotov_hip 0.6 (gfx950; tile64q2, tile64, tile64/stream, tile64x, ens64/mfma, mini16, mini4, coop16/mfma, ell/csr, ellstream/csr, ellglobal/csr, tile128, generic, generic/csr, generic/mixed, lindblad/matrix kernels)"; }
+extern "C" const char *kh_version(void) { return "krotov_hip 0.6 (gfx950; tile64q2, tile64, tile64/stream, tile64x, ens64/mfma, mini16, mini4, coop16/mfma, ell/csr, ellstream/csr, ellglobal/csr, ellsplit/csr, tile128, generic, generic/csr, generic/mixed, lindblad/matrix kernels)"; }
 
 extern "C" const char *kh_engine_kernel(const kh_engine *e) {
     if (e == nullptr) return "";
@@ -452,7 +460,7 @@ extern "C" const char *kh_engine_kernel(const kh_engine *e) {
         case KIND_TILE_RPT1: return p.stepwise_only ? (p.stream ? "tile64/stream" : "tile64/512 per interval") : "tile64/512";
         case KIND_TILE_Q2: return p.mini ? (p.quad ? "mini4/wave" : "mini16/wave") : "tile64q2/512";
         case KIND_COOP: return "coop16/mfma";
-        case KIND_ELL: return p.ell_global ? "ellglobal/csr" : (p.ell_stream ? "ellstream/csr" : "ell/csr");
+        case KIND_ELL: return p.ell_global ? (e->row_split > 1 ? "ellsplit/csr" : "ellglobal/csr") : (p.ell_stream ? "ellstream/csr" : "ell/csr");
         case KIND_TILEN: return "tile128/512";
         default: return e->d_csr_fw != nullptr ? "generic/csr" : (p.tx ? "tile64x/512" : "generic");
     }
@@ -1075,7 +1083,7 @@ static int detect_dense(kh_engine *e, const kh_problem *pr, KhFacts &f) {
 // per distinct operator list and direction: the matrix in registers where the rows fit (N <= 2048), else -- or with
 // KH_KERNEL=ellstream -- the streamed form (N <= 4096, rows up to 32 entries): the same pools with their own row count,
 // read per term.  Where neither applies and the generic kernels cannot hold N either (N > 4096, or N > 2540 with a row
-// wider than 32) -- or with KH_KERNEL=ellglobal -- the streamed form's pools with rows of any width and every vector in
+// wider than 32) -- or with KH_KERNEL=ellglobal / ellsplit -- the streamed form's pools with rows of any width and every vector in
 // global memory (kh_ellg.h, N <= 2^20).
 static int build_sparse(kh_engine *e, const kh_problem *pr, const kh_csr *csr_fw, const kh_csr *csr_bw,
                         const std::vector<const cplx *> &fw, KhFacts &f) {
@@ -1103,7 +1111,7 @@ static int build_sparse(kh_engine *e, const kh_problem *pr, const kh_csr *csr_fw
         }
         KH_TRY(classify_operators(e, pr, ctl_plus, ctl_minus, drift_plus, [&](double &v) { return v = fro2, KH_OK; }, f));
     }
-    const bool want_stream = e->sw.kernel_is("ellstream"), want_global = e->sw.kernel_is("ellglobal");
+    const bool want_stream = e->sw.kernel_is("ellstream"), want_global = e->sw.kernel_is("ellglobal") || e->sw.kernel_is("ellsplit");
     for (int form = want_global ? 2 : (want_stream ? 1 : 0); form < 3 && !f.ell; ++form) {
         const bool global = form == 2, stream = form >= 1;
         if (e->N > (global ? KH_ELLG_NMAX : (stream ? KH_ELLS_NMAX : KH_ELL_NMAX)) || e->L > KH_MAX_L || e->sw.kernel_is("generic")) continue;
@@ -1300,6 +1308,7 @@ static int ens_forms(kh_engine *e, int ncg, const void *forms[2]) {
 }
 
 static int stage_workspaces(kh_engine *e);
+static int kh_row_split_auto(int num_cus, int K, int N);
 
 // Everything but the validation of engine_create; on failure the caller destroys the half-built engine.
 static int engine_build(kh_engine *e, const kh_problem *pr, const kh_csr *csr_fw, const kh_csr *csr_bw) {
@@ -1458,7 +1467,12 @@ static int engine_create(const kh_problem *pr, const kh_csr *csr_fw, const kh_cs
     e->is_super = pr->is_super ? 1 : 0;
     e->tol = pr->tol > 0.0 ? pr->tol : ldexp(1.0, -53);
     e->sw = read_switches();
-    const int rc = engine_build(e, pr, csr_fw, csr_bw);
+    int rc = engine_build(e, pr, csr_fw, csr_bw);
+    // KH_KERNEL=ellsplit: the global form (forced above) on KH_ELL_SPLIT workgroups per objective, or 'auto'
+    if (rc == KH_OK && e->sw.kernel_is("ellsplit") && e->plan.kind == KIND_ELL && e->plan.ell_global) {
+        const int S = e->sw.ell_split != 0 ? e->sw.ell_split : kh_row_split_auto(e->num_cus, e->K, e->N);
+        if (S != 1) rc = kh_set_row_split(e, S);
+    }
     if (rc != KH_OK) {
         kh_engine_destroy(e);
         return rc;
@@ -1969,6 +1983,17 @@ static int sweep_store(kh_engine *e, bool backward, const double *pulses, const 
         }
         case KIND_ELL: {
             const KhEll *ells = backward ? e->d_ell_bw : e->d_ell_fw;
+            if (pl.ell_global && e->row_split > 1) {
+                // all S x groups workgroups wait for each other at every term: resident at once, as an update sweep's
+                KH_HIP(hipMemsetAsync(e->d_split_counters, 0, e->split_counters_bytes, st));
+                KhExchange ex = exchange_args(e, false);
+                ex.G = e->split_groups * e->row_split;
+                rc = launch_persistent<kh_ellgs_sweep_store<KH_ELLGS_THREADS>>(
+                    e, dim3(e->split_groups * e->row_split), dim3(KH_ELLGS_THREADS), kh_ellgs_lds_bytes(), st, p, ells,
+                    (const int *)e->d_ell_off, (const cplx *)e->d_ell_vals, pulses, in, store, out, direction, e->d_ellg_ws,
+                    e->ellg_ws_stride, ex, e->row_split, e->d_split_counters);
+                break;
+            }
             if (pl.ell_global) {
                 launch_plain<kh_ellg_sweep_store<KH_ELLG_THREADS>>(dim3(e->ellg_wgs), dim3(KH_ELLG_THREADS), kh_ellg_lds_bytes(), st, p, ells,
                                                                    (const int *)e->d_ell_off, (const cplx *)e->d_ell_vals, pulses, in, store, out,
@@ -2035,7 +2060,7 @@ static int sweep_store(kh_engine *e, bool backward, const double *pulses, const 
     if (rc != KH_OK) return rc;
     KH_HIP(hipGetLastError());
     e->last_intervals = e->nt - 1;
-    e->last_wgs = e->K;
+    e->last_wgs = pl.kind_store == KIND_ELL && pl.ell_global && e->row_split > 1 ? e->split_groups * e->row_split : e->K;
     return KH_OK;
 }
 
@@ -2196,6 +2221,18 @@ static int update_tilen(kh_engine *e, const KhSweepArgs &p, const KhUpdateArgs &
 // the padded-row form with its vectors in global memory (kh_ellg.h): a workgroup takes its objectives in turns, so the
 // grid is min(K, #CUs) or what kh_set_update_workgroups allows
 static int update_ellg(kh_engine *e, const KhSweepArgs &p, const KhUpdateArgs &u, const KhExchange &ex, hipStream_t st) {
+    if (e->row_split > 1) {  // kh_ellgs.h: every workgroup of every group takes part in the exchange
+        const int S = e->row_split, G = e->split_groups * S;
+        KH_HIP(hipMemsetAsync(e->d_split_counters, 0, e->split_counters_bytes, st));
+        KhExchange exs = ex;
+        exs.G = G;
+        e->last_update_grid = G;
+        return with_bool(u.sigma != nullptr, [&](auto so) {
+            return launch_persistent<kh_ellgs_forward_update<KH_ELLGS_THREADS, decltype(so)::value>>(
+                e, dim3(G), dim3(KH_ELLGS_THREADS), kh_ellgs_lds_bytes(), st, p, (const KhEll *)e->d_ell_fw, (const int *)e->d_ell_off,
+                (const cplx *)e->d_ell_vals, u, exs, e->d_ellg_ws, e->ellg_ws_stride, S, e->d_split_counters);
+        });
+    }
     int G = e->plan.grid_update;
     if (e->reduced_G > 0 && e->reduced_G < G) G = e->reduced_G;
     KhExchange exg = ex;
@@ -2438,10 +2475,12 @@ extern "C" int kh_forward_update(kh_engine *e, const kh_cdouble *chi_store_dev, 
 extern "C" int kh_set_update_workgroups(kh_engine *e, int32_t max_workgroups, int32_t *chosen) {
     if (e == nullptr || max_workgroups < 0) return kh_fail(KH_ERR_INVALID, "bad argument");
     if (chosen != nullptr) *chosen = e->plan.single_grid();
+    if (e->row_split > 1 && chosen != nullptr) *chosen = e->split_groups * e->row_split;
     if (max_workgroups == 0) {
         e->reduced_G = 0;
         return KH_OK;
     }
+    if (e->row_split > 1) return kh_fail(KH_ERR_UNSUPPORTED, "a split engine (kh_set_row_split) keeps its own grid: set the row split to 1 first");
     if (e->lind) return kh_fail(KH_ERR_UNSUPPORTED, "Lindblad-form engines (kh_engine_create_lindblad) have no form with fewer workgroups");
     if (e->p2p_ready) return kh_fail(KH_ERR_UNSUPPORTED, "sharded sweeps keep their grid (all ranks must agree on the form)");
     const KhPlan &p = e->plan;
@@ -2468,6 +2507,69 @@ extern "C" int kh_set_update_workgroups(kh_engine *e, int32_t max_workgroups, in
     }
     e->reduced_G = max_workgroups;
     if (chosen != nullptr) *chosen = G;
+    return KH_OK;
+}
+
+// 'auto': the largest power of two <= min(CUs / K, chunks / 8, 64); 1 where N <= 4096.  The N floor and the chunks / 8
+// term (at least 512 rows per part) are PLACEHOLDERS until scripts/perf_ellsplit.py has been run.
+static int kh_row_split_auto(int num_cus, int K, int N) {
+    if (N <= 4096 || K < 1) return 1;
+    const int chunks = (int)(kh_ellg_rows(N) / 64);
+    int cap = num_cus / K;
+    if (chunks / 8 < cap) cap = chunks / 8;
+    if (cap > 64) cap = 64;
+    int S = 1;
+    while (2 * S <= cap) S *= 2;
+    return S;
+}
+
+extern "C" int kh_ellsplit_rows(int32_t N, int32_t S, int32_t part, int32_t *first, int32_t *count) {
+    if (first == nullptr || count == nullptr) return kh_fail(KH_ERR_INVALID, "null argument");
+    if (N < 1 || N > KH_ELLG_NMAX || S < 1 || part < 0 || part >= S) return kh_fail(KH_ERR_INVALID, "bad N = %d, S = %d or part = %d", N, S, part);
+    int f = 0, c = 0;
+    kh_ellsplit_range(N, S, part, &f, &c);
+    *first = f;
+    *count = c;
+    return KH_OK;
+}
+
+// S workgroups per objective for both sweeps of a CSR engine in the global form (kh_ellgs.h); 1: the kernels of kh_ellg.h
+extern "C" int kh_set_row_split(kh_engine *e, int workgroups_per_objective) {
+    if (e == nullptr) return kh_fail(KH_ERR_INVALID, "null engine");
+    const int S = workgroups_per_objective;
+    if (!(e->plan.kind == KIND_ELL && e->plan.ell_global && e->d_csr_fw != nullptr))
+        return kh_fail(KH_ERR_UNSUPPORTED, "only sparse (CSR) engines in the form with global vectors (\"ellglobal/csr\") split an objective's rows; this one runs %s", kh_engine_kernel(e));
+    if (S < 1) return kh_fail(KH_ERR_UNSUPPORTED, "%d workgroups per objective: at least 1", S);
+    if (S == 1) {
+        e->row_split = 1;
+        return KH_OK;
+    }
+    const int max_wgs = e->plan.max_wgs;  // (what the exchange takes: at most 256, at most one per CU)
+    if (S > e->num_cus || S > max_wgs)
+        return kh_fail(KH_ERR_UNSUPPORTED, "%d workgroups per objective: this device runs at most %d at once", S, e->num_cus < max_wgs ? e->num_cus : max_wgs);
+    const int chunks = (int)(kh_ellg_rows(e->N) / 64);
+    if (S > chunks && chunks == 1 && S > 64)
+        return kh_fail(KH_ERR_UNSUPPORTED, "%d workgroups per objective for one 64-row chunk: every part but one would be empty", S);
+    if (e->p2p_ready) return kh_fail(KH_ERR_UNSUPPORTED, "sharded sweeps keep one workgroup per objective");
+    if (e->reduced_G > 0) return kh_fail(KH_ERR_UNSUPPORTED, "the update sweep's grid was reduced (kh_set_update_workgroups): restore it first");
+    int groups = e->K < max_wgs / S ? e->K : max_wgs / S;
+    if (e->sw.ell_groups > 0 && e->sw.ell_groups < groups) groups = e->sw.ell_groups;
+    if (groups > e->ellg_wgs) groups = e->ellg_wgs;  // (one workspace per group)
+    if ((e->K + groups - 1) / groups > KH_ELLG_MMAX)
+        return kh_fail(KH_ERR_UNSUPPORTED, "%d objectives on %d groups of %d workgroups: more than %d per group", e->K, groups, S, KH_ELLG_MMAX);
+    const int Lx = e->L > 0 ? e->L : 1;
+    const size_t slots = sizeof(kh_u64) * 2 * (size_t)groups * S * Lx * 2;
+    if (slots > e->slots_bytes) {  // (the earlier block stays with the engine until it is destroyed)
+        KH_TRY(dev_alloc(e, &e->d_slots, slots));
+        e->slots_bytes = slots;
+    }
+    const size_t counters = (size_t)groups * KH_ELLGS_LINE;  // (a multiple of 16 bytes from its allocation's start)
+    if (counters > e->split_counters_bytes) {
+        KH_TRY(dev_alloc(e, &e->d_split_counters, counters));
+        e->split_counters_bytes = counters;
+    }
+    e->row_split = S;
+    e->split_groups = groups;
     return KH_OK;
 }
 

@@ -16,7 +16,7 @@ import torch
 from . import _lib
 from .sharding import run_update_loop
 
-__all__ = ['HipKrotovEngine', 'LAST_ENGINE']
+__all__ = ['HipKrotovEngine', 'LAST_ENGINE', 'auto_row_split']
 
 _last_engine = None
 
@@ -30,6 +30,20 @@ def LAST_ENGINE():
     kernel family of an engine built inside optimize_pulses).  Held strongly until the next engine is created:
     nothing in a :class:`~krotov_amd.result.Result` is guaranteed to keep it alive."""
     return _last_engine
+
+
+def auto_row_split(num_cus, K, N):
+    """``row_split='auto'``: the largest power of two <= min(num_cus // K, chunks // 8, 64) with chunks = ceil(N / 64), and
+    1 where N <= 4096.  The ``chunks // 8`` term (at least 512 rows per part) and the N floor are PLACEHOLDERS: they are
+    to be replaced by what ``scripts/perf_ellsplit.py`` measures (``profiles/ellsplit.txt``), which has
+    not been recorded yet."""
+    if N <= 4096 or K < 1:
+        return 1
+    cap = min(num_cus // K, ((N + 63) // 64) // 8, 64)
+    S = 1
+    while 2 * S <= cap:
+        S *= 2
+    return S
 
 
 def _require_gpu():
@@ -67,9 +81,13 @@ class HipKrotovEngine:
             ``liouvillian(H, c_ops)``, whose d^2 x d^2 operators are never built.  d <= 32, at most 4 Lindblad operators
             and 4 controls (``KrotovHipError`` with ``KH_ERR_UNSUPPORTED`` beyond); first-order update on one GPU only.
             ``op_norms``: (K, 1+L+n_c) bounds for (H0, H_l, C_j).
+        row_split: sparse engines in the form with global vectors (``"ellglobal/csr"``) only: the rows of every
+            objective on this many workgroups (``"ellsplit/csr"``, :meth:`set_row_split`) -- an int, ``'auto'``
+            (:func:`auto_row_split`) or ``None``: one workgroup per objective, as before.
     """
 
-    def __init__(self, ops, dt, is_super=False, op_norms=None, device=None, tol=0.0, theta_max=0.0, c_ops=None):
+    def __init__(self, ops, dt, is_super=False, op_norms=None, device=None, tol=0.0, theta_max=0.0, c_ops=None,
+                 row_split=None):
         _require_gpu()
         self._lib = _lib.load()
         self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
@@ -114,6 +132,15 @@ class HipKrotovEngine:
                 norms = self._create_dense(ops, dt, op_norms, tol, theta_max)
         self.op_norms = norms.reshape(self.K, -1)
         self.kernel = self._lib.kh_engine_kernel(self._handle).decode()
+        self.row_split = 1
+        if self.kernel == 'ellsplit/csr':  # (KH_KERNEL=ellsplit: the library chose KH_ELL_SPLIT or 'auto')
+            self.row_split = int(os.environ.get('KH_ELL_SPLIT', '0')) or auto_row_split(self._num_cus(), self.K, self.N)
+        if row_split is not None:
+            try:
+                self.set_row_split(row_split)
+            except Exception:
+                self.close()
+                raise
         # optional per-launch timing with HIP events on the launch stream
         self.profile = os.environ.get('KH_PROFILE', '0') == '1'
         self._events = {'forward': [], 'backward': [], 'update': []}
@@ -410,6 +437,24 @@ class HipKrotovEngine:
         chosen = ctypes.c_int32(0)
         _lib.check(self._lib.kh_set_update_workgroups(self._handle, int(max_workgroups), ctypes.byref(chosen)))
         return int(chosen.value)
+
+    def _num_cus(self):
+        return torch.cuda.get_device_properties(self.device).multi_processor_count
+
+    def set_row_split(self, workgroups_per_objective):
+        """Spread every objective's rows over this many workgroups in both sweeps (``kh_set_row_split``; kernel family
+        ``"ellsplit/csr"``), or ``'auto'`` (:func:`auto_row_split`); 1 restores ``"ellglobal/csr"`` exactly.  Only sparse
+        engines in the form with global vectors take it: ``KrotovHipError`` (``KH_ERR_UNSUPPORTED``) otherwise.  Returns
+        the factor in force."""
+        S = workgroups_per_objective
+        if S == 'auto':
+            S = auto_row_split(self._num_cus(), self.K, self.N)
+            if S == 1 and self.kernel not in ('ellglobal/csr', 'ellsplit/csr'):
+                return 1
+        _lib.check(self._lib.kh_set_row_split(self._handle, int(S)))
+        self.row_split = int(S)
+        self.kernel = self._lib.kh_engine_kernel(self._handle).decode()
+        return self.row_split
 
     def forward_update(self, chi_store, chi_norms, init, guess, shape, lambdas):
         """Forward sweep with sequential update; returns ``(opt, psi_T, g_a)``."""

@@ -513,8 +513,13 @@ class _HipBackend:
         self.is_super = layout.kinds[self.k0:self.k1] if layout.mixed else layout.kinds[self.k0]
         self.N, self.L = N, L
         tlist = np.asarray(tlist, dtype=np.float64)
+        # (HipExpm(sparse=True, row_split=...) / DensityMatrixODEPropagator(row_split=...): an objective's rows on several workgroups)
+        row_split = next((p.row_split for p in props if isinstance(p, HipExpm) and getattr(p, 'sparse', False)
+                          and getattr(p, 'row_split', None) is not None), None)
         if self.lindblad is not None:
             self.engine = HipKrotovEngine(ops, np.diff(tlist), c_ops=c_rows)
+        elif row_split is not None:
+            self.engine = HipKrotovEngine(ops, np.diff(tlist), is_super=self.is_super, row_split=row_split)
         else:
             self.engine = HipKrotovEngine(ops, np.diff(tlist), is_super=self.is_super)
         self.nt = len(tlist)
@@ -576,6 +581,27 @@ class _HipBackend:
             return self.layout.vector(state, k)
         return state_to_vector(state, self.N, self.is_super)
 
+    def _split_guarded(self, sweep, what):
+        """``sweep()`` on an engine that spreads an objective's rows over several workgroups (``row_split`` > 1): its
+        workgroups wait for each other inside BOTH kinds of sweep, so each is checked when it is done, and one that
+        reports KH_ERR_TIMEOUT (its workgroups were not all resident) is redone with one workgroup per objective -- the
+        form the engine then keeps for the rest of the optimisation.  Any other engine: just ``sweep()``."""
+        eng = self.engine
+        if getattr(eng, 'row_split', 1) <= 1:
+            return sweep()
+        try:
+            out = sweep()
+            eng.check()
+            return out
+        except _KrotovHipError as exc:
+            if exc.code != _KH_ERR_TIMEOUT:
+                raise
+            logging.getLogger('krotov').info(
+                "row split %d: the %s sweep timed out (%s); redoing it, and going on, with one workgroup per objective",
+                eng.row_split, what, exc)
+            eng.set_row_split(1)
+            return sweep()
+
     def _gather_rows(self, local):
         """(K_loc, ...) host array on every rank -> (K_total, ...) on every rank."""
         return gather_rows(local, self.K_total, self.world, self.group, self.engine.device)
@@ -583,9 +609,10 @@ class _HipBackend:
     def initial_forward(self, pulses, store=False):
         forward_states = None
         if store:
-            self.fw_T_dev, self.fw_prev = self.engine.forward(self._pulses(pulses), self.init, store=True)
+            self.fw_T_dev, self.fw_prev = self._split_guarded(
+                lambda: self.engine.forward(self._pulses(pulses), self.init, store=True), 'forward')
         else:
-            self.fw_T_dev = self.engine.forward(self._pulses(pulses), self.init)
+            self.fw_T_dev = self._split_guarded(lambda: self.engine.forward(self._pulses(pulses), self.init), 'forward')
         fw_states_T = self._final_states(self.fw_T_dev)
         if store:
             forward_states = _DeviceTrajectories(self.fw_prev, self.likes, self.k0, final=fw_states_T._array,
@@ -642,7 +669,7 @@ class _HipBackend:
             chi_loc = eng.dev(chi_T[self.k0:self.k1], t.complex128)
             norms_loc = eng.dev(np.asarray(chi_norms, dtype=np.float64)[self.k0:self.k1], t.float64)
         self.last_chi = (chi_loc, norms_loc)
-        self.chi_store = eng.backward(chi_loc, guess, out=self.chi_store)
+        self.chi_store = self._split_guarded(lambda: eng.backward(chi_loc, guess, out=self.chi_store), 'backward')
         done = False
         if self.group is None:
             if self._single_launch_ok:
@@ -667,6 +694,13 @@ class _HipBackend:
                     except _KrotovHipError as exc:
                         if exc.code not in (_KH_ERR_TIMEOUT, _KH_ERR_UNSUPPORTED):
                             raise
+                        if exc.code == _KH_ERR_TIMEOUT and getattr(eng, 'row_split', 1) > 1:
+                            # first rung: one workgroup per objective again (kept from here on); then the ladder below
+                            logging.getLogger('krotov').info(
+                                "row split %d: the update sweep timed out (%s); redoing it, and going on, with one "
+                                "workgroup per objective", eng.row_split, exc)
+                            eng.set_row_split(1)
+                            continue
                         try:
                             # every rung costs a timed-out sweep (KH_TIMEOUT_MS, 1 s by default): two of them at most --
                             # half the workgroups (what gets through next to a stream holding half of the device), then

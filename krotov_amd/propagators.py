@@ -107,11 +107,14 @@ class HipExpm(Propagator):
     ``liouville`` switch (None = infer from ``.type`` / state shape).  With
     ``sparse=True`` ``optimize_pulses`` keeps the operators in CSR form on the
     device (large operators with a few entries per row); results are the same
-    to round-off."""
+    to round-off.  ``row_split`` (with ``sparse=True``): the rows of every objective on that many workgroups where the
+    engine runs the form with global vectors -- an int, ``'auto'`` or ``None`` (one workgroup per objective, as before);
+    see :meth:`krotov_amd.engine.HipKrotovEngine.set_row_split`."""
 
-    def __init__(self, liouville=None, sparse=False):
+    def __init__(self, liouville=None, sparse=False, row_split=None):
         self.liouville = liouville
         self.sparse = bool(sparse)
+        self.row_split = row_split
 
     def __call__(self, H, state, dt, c_ops=None, backwards=False, initialize=False):
         return _single_step(H, state, dt, c_ops, backwards, self.liouville)
@@ -177,11 +180,11 @@ class DensityMatrixODEPropagator(HipExpm):
     sparse generator to machine precision (CSR matrix-vector products inside the
     same sweep kernels), so the integrator options are accepted for
     compatibility and have no effect, and the object holds no state
-    (``reentrant`` is moot: one instance serves any number of objectives)."""
+    (``reentrant`` is moot: one instance serves any number of objectives).  ``row_split``: as for :class:`HipExpm`."""
 
     def __init__(self, method='adams', order=12, atol=1e-8, rtol=1e-6, nsteps=1000, first_step=0, min_step=0,
-                 max_step=0, reentrant=False):
-        super().__init__(liouville=True, sparse=True)
+                 max_step=0, reentrant=False, row_split=None):
+        super().__init__(liouville=True, sparse=True, row_split=row_split)
         self.method, self.order, self.atol, self.rtol = method, order, atol, rtol
         self.nsteps, self.first_step, self.min_step, self.max_step = nsteps, first_step, min_step, max_step
         self.reentrant = reentrant
