@@ -320,6 +320,25 @@ int kh_p2p_stats(kh_engine *engine, double out[4]);
 int kh_tau(kh_engine *engine, const kh_cdouble *targets_dev,
            const kh_cdouble *psi_T_dev, kh_cdouble *tau_dev, void *stream);
 
+/* Expectation values of a stored trajectory, for every objective and grid point at once (what the reference's
+ * Objective.propagate(..., e_ops=...) evaluates state by state on the host, objectives.py:338-433; the trajectory
+ * stays on the device).  K, nt, N and the kind come from the engine; the kernel family does not matter, only the
+ * store's layout: any engine of kh_engine_create, _csr or _lindblad qualifies.
+ *   states_dev [K][nt][N]  what kh_forward_store (or kh_backward_store) stored
+ *   e_ops      [K*n_e]     HOST array of device pointers, e_ops[k*n_e + e]: dense row-major operator e of objective
+ *                          k; equal pointers = a shared operator (as kh_problem.ops); NULL = skipped, its outputs
+ *                          are exact zeros.  Copied with hipMemcpyAsync on `stream`: keep it until that copy is done.
+ *   out_dev    [n_e][K][nt]
+ * Hilbert-space engines (is_super = 0): operators N x N, out[e][k][n] = <psi_k(t_n)| O_ke |psi_k(t_n)> (fp64 MFMA).
+ * Liouville-space engines (is_super = 1, kh_engine_create_lindblad): N = d*d, operators d x d,
+ * out[e][k][n] = tr(O_ke rho_k(t_n)) for column-stacked vec(rho).
+ * One pass over the store serves up to 8 operators; more take ceil(n_e / 8) passes.  Results are bitwise repeatable.
+ * KH_ERR_INVALID for a NULL engine, states, table or out and for n_e < 1 (checked before the device is touched);
+ * KH_ERR_UNSUPPORTED for engines of kh_engine_create_mixed (per-objective operator shapes: not yet).  Calls on one
+ * engine share a table buffer: issue them on one stream. */
+int kh_expect(kh_engine *engine, const kh_cdouble *states_dev, const kh_cdouble *const *e_ops, int32_t n_e,
+              kh_cdouble *out_dev, void *stream);
+
 /* Boundary co-states of the built-in functionals, normalised for the backward
  * sweep: v_k = c_k target_k + d_k psi_k(T), chi_T[k] = v_k / ||v_k||_2,
  * chi_norms[k] = ||v_k||_2.  Replaces the chi_constructor call and the

@@ -19,7 +19,7 @@ from . import (
     second_order,
     shapes,
 )
-from .objectives import Objective, ensemble_objectives, gate_objectives
+from .objectives import Objective, ensemble_objectives, gate_objectives, propagate_objectives
 from .optimize import optimize_pulses
 from .result import Result
 
@@ -38,6 +38,7 @@ __all__ = [
     'objectives',
     'optimize_pulses',
     'parallelization',
+    'propagate_objectives',
     'propagators',
     'result',
     'second_order',

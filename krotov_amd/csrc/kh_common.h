@@ -39,6 +39,7 @@ typedef double2 cplx;
 #define KH_TU_LIND 16
 #define KH_TU_ELLG 17
 #define KH_TU_ELLGS 18
+#define KH_TU_EXPECT 19
 #ifndef KH_TU
 #define KH_TU KH_TU_ALL
 #endif

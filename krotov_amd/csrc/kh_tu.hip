@@ -35,6 +35,8 @@
 #include "kh_ellg.h"
 #elif KH_TU == KH_TU_ELLGS
 #include "kh_ellgs.h"
+#elif KH_TU == KH_TU_EXPECT
+#include "kh_expect.h"
 #else
 #error "unknown KH_TU"
 #endif

@@ -41,6 +41,7 @@
 #include "kh_tilen.h"
 #include "kh_ens.h"
 #include "kh_lind.h"
+#include "kh_expect.h"
 // the parallel build (krotov_amd/build.py, -DKH_TU=KH_TU_MAIN): the sweep kernels are instantiated in the family units
 // (kh_tu.hip), here they are `extern template`; compiled by itself this file is the whole library in one unit
 #include "kh_instances.inc"
@@ -291,6 +292,8 @@ struct kh_engine {
     int last_update_grid = 0;  // workgroups of the last single-launch update sweep where the ensemble / streaming kernels ran it
     int reduced_G = 0;  // kh_set_update_workgroups: the single-launch update sweep on at most this many workgroups (0: off)
     std::set<const void *> lds_raised;  // kernels whose dynamic-LDS limit was raised on this engine's device
+    const cplx **d_expect_tab = nullptr;  // [K * n_e] kh_expect: the last call's operator table (grown on demand)
+    size_t expect_tab_entries = 0;
 };
 
 // Kernels with more than 64 KiB of dynamic LDS need the limit raised once per device: remembered per
@@ -548,6 +551,7 @@ extern "C" void kh_engine_destroy(kh_engine *e) {
     (void)hipFree(e->d_gen_scratch);
     (void)hipFree(e->d_gen_adj);
     (void)hipFree(e->d_coop_adj);
+    (void)hipFree((void *)e->d_expect_tab);
     for (void *ptr : e->p2p_opened) (void)hipIpcCloseMemHandle(ptr);
     (void)hipFree(e->p2p_window);
     (void)hipFree((void *)e->d_p2p_peers);
@@ -2796,6 +2800,49 @@ extern "C" int kh_tau(kh_engine *e, const kh_cdouble *targets_dev, const kh_cdou
     const int blocks = (e->K + waves_per_block - 1) / waves_per_block;
     kh_tau_kernel<<<blocks, 64 * waves_per_block, 0, (hipStream_t)stream>>>(
         (const cplx *)targets_dev, (const cplx *)psi_T_dev, (cplx *)tau_dev, e->K, e->N);
+    KH_HIP(hipGetLastError());
+    return KH_OK;
+}
+
+// Expectation values of a stored trajectory (kh_expect.h): <psi|O|psi> on Hilbert-space engines, tr(O rho) on
+// Liouville-space ones, KH_EXPECT_MAX_OPS operators per pass over the store.
+extern "C" int kh_expect(kh_engine *e, const kh_cdouble *states_dev, const kh_cdouble *const *e_ops, int32_t n_e,
+                         kh_cdouble *out_dev, void *stream) {
+    if (e == nullptr || states_dev == nullptr || e_ops == nullptr || out_dev == nullptr)
+        return kh_fail(KH_ERR_INVALID, "null argument");
+    if (n_e < 1) return kh_fail(KH_ERR_INVALID, "n_e = %d: at least one operator", n_e);
+    if (e->mixed)
+        return kh_fail(KH_ERR_UNSUPPORTED, "mixed engines (kh_engine_create_mixed) have no expectation-value kernel: "
+                                           "their objectives would need operators of their own dimensions");
+    const bool super = e->is_super != 0;
+    const int points = super ? KH_EXPECT_L_POINTS : KH_EXPECT_H_POINTS;
+    const long long blocks = ((long long)e->nt + points - 1) / points;
+    if (blocks > 65535) return kh_fail(KH_ERR_UNSUPPORTED, "nt = %d: more than 65535 blocks of %d time points", e->nt, points);
+    hipStream_t st = (hipStream_t)stream;
+    const size_t entries = (size_t)e->K * (size_t)n_e;
+    if (entries > e->expect_tab_entries) {
+        (void)hipFree((void *)e->d_expect_tab);  // (waits for whatever still reads it)
+        e->d_expect_tab = nullptr, e->expect_tab_entries = 0;
+        void *mem = nullptr;
+        if (hipMalloc(&mem, entries * sizeof(cplx *)) != hipSuccess) {
+            (void)hipGetLastError();
+            return kh_fail(KH_ERR_NOMEM, "no device memory for a table of %zu operator pointers", entries);
+        }
+        e->d_expect_tab = (const cplx **)mem, e->expect_tab_entries = entries;
+    }
+    // (ordered on the stream behind an earlier call's kernels, which read the same table)
+    KH_HIP(hipMemcpyAsync((void *)e->d_expect_tab, (const void *)e_ops, entries * sizeof(cplx *), hipMemcpyHostToDevice, st));
+    const dim3 grid((unsigned)e->K, (unsigned)blocks), block(KH_EXPECT_THREADS);
+    for (int e0 = 0; e0 < n_e; e0 += KH_EXPECT_MAX_OPS) {
+        const int ne = n_e - e0 < KH_EXPECT_MAX_OPS ? n_e - e0 : KH_EXPECT_MAX_OPS;
+        cplx *plane = (cplx *)out_dev + (size_t)e0 * e->K * e->nt;
+        if (super)
+            launch_plain<kh_expect_liouville>(grid, block, 0, st, e->d_expect_tab + e0, (int)n_e, ne, (const cplx *)states_dev, plane,
+                                              e->K, e->N, e->nt);
+        else
+            launch_plain<kh_expect_hilbert>(grid, block, 0, st, e->d_expect_tab + e0, (int)n_e, ne, (const cplx *)states_dev, plane,
+                                            e->K, e->N, e->nt);
+    }
     KH_HIP(hipGetLastError());
     return KH_OK;
 }

@@ -646,6 +646,59 @@ class HipKrotovEngine:
         _lib.check(self._lib.kh_tau(self._handle, targets.data_ptr(), psi_T.data_ptr(), out.data_ptr(), self._stream()))
         return out
 
+    def expect(self, states, e_ops, out=None):
+        """Expectation values of a stored trajectory on the device (``kh_expect``): ``states`` is the ``(K, nt, N)``
+        tensor :meth:`forward` returns with ``store=True``; ``e_ops`` a list of ``n_e`` operators applied to every
+        objective, or a list of K such lists (``None``: skipped, exact zeros) -- arrays, tensors or Qobj-like objects,
+        every distinct object uploaded once.  Hilbert-space engines take N x N operators and give
+        ``<psi_k(t_n)|O|psi_k(t_n)>``; Liouville-space ones (``is_super``, Lindblad form) take d x d operators, N = d*d,
+        and give ``tr(O rho_k(t_n))``.  Returns a ``(n_e, K, nt)`` complex128 tensor.  A wrong operator shape raises
+        ``ValueError`` before any launch; mixed engines raise ``KrotovHipError`` (``KH_ERR_UNSUPPORTED``)."""
+        from ._ingest import to_dense
+
+        e_ops = list(e_ops)
+        per_objective = len(e_ops) > 0 and all(isinstance(row, (list, tuple)) for row in e_ops)
+        rows = [list(row) for row in e_ops] if per_objective else [e_ops] * self.K
+        if len(rows) != self.K:
+            raise ValueError("e_ops: %d operator lists for %d objectives" % (len(rows), self.K))
+        n_e = len(rows[0])
+        if n_e < 1 or any(len(row) != n_e for row in rows):
+            raise ValueError("e_ops: every objective needs the same number (>= 1) of operators")
+        if self.mixed:
+            side = None  # (refused by the library below, whatever the shapes)
+        else:
+            side = int(round(np.sqrt(self.N))) if self.is_super else self.N
+            if side * side != self.N and self.is_super:
+                raise ValueError("Liouville-space engine with N = %d, which is not a square" % self.N)
+        uploaded = {}
+        table = (ctypes.c_void_p * (self.K * n_e))()
+        for k, row in enumerate(rows):
+            for i, op in enumerate(row):
+                if op is None:
+                    table[k * n_e + i] = None
+                    continue
+                key = id(op)
+                if key not in uploaded:
+                    host = op.detach().cpu().numpy() if isinstance(op, torch.Tensor) else to_dense(op)
+                    host = np.ascontiguousarray(host, dtype=np.complex128)
+                    if side is not None and host.shape != (side, side):
+                        raise ValueError("e_ops[%d] of objective %d has shape %s, expected %s" % (
+                            i, k, host.shape, (side, side)))
+                    uploaded[key] = (torch.from_numpy(host).to(self.device), op)  # keep `op` alive: id() stays unique
+                table[k * n_e + i] = uploaded[key][0].data_ptr()
+        if tuple(states.shape) != (self.K, self.nt, self.N) or states.dtype != torch.complex128 \
+                or not states.is_contiguous() or states.device != self.device:
+            raise ValueError("states must be a contiguous (K, nt, N) = %s complex128 tensor on %s" % (
+                (self.K, self.nt, self.N), self.device))
+        if out is None:
+            out = torch.empty((n_e, self.K, self.nt), dtype=torch.complex128, device=self.device)
+        elif tuple(out.shape) != (n_e, self.K, self.nt) or out.dtype != torch.complex128 or not out.is_contiguous():
+            raise ValueError("out must be a contiguous (n_e, K, nt) complex128 tensor")
+        _lib.check(self._lib.kh_expect(self._handle, states.data_ptr(), table, n_e, out.data_ptr(), self._stream()))
+        # the table and the operators until the stream has passed the launch (the next call replaces them)
+        self._expect_keep = (table, uploaded)
+        return out
+
     def chi_boundary(self, targets, psi_T, c, d):
         """Normalised boundary co-states ``(c_k target_k + d_k psi_k(T)) / ||.||`` and
         their norms, ``(K, N)`` and ``(K,)`` device tensors (kh_chi_boundary)."""

@@ -15,7 +15,8 @@ from collections import defaultdict
 
 import numpy as np
 
-__all__ = ['Objective', 'PropagationResult', 'gate_objectives', 'ensemble_objectives', 'liouvillian']
+__all__ = ['Objective', 'PropagationResult', 'gate_objectives', 'ensemble_objectives', 'liouvillian',
+           'propagate_objectives']
 
 
 def _shallow_nested(l):
@@ -415,6 +416,102 @@ def _expectation_value(oper, state):
         vec = psi.reshape(-1)
         val = np.vdot(vec, O @ vec)
     return val.real if np.array_equal(O, O.conj().T) else val
+
+
+def _e_ops_per_objective(e_ops, K):
+    """``e_ops`` (None, one list for all objectives, or one list per objective) as K lists."""
+    e_ops = [] if e_ops is None else list(e_ops)
+    if len(e_ops) > 0 and all(isinstance(row, (list, tuple)) for row in e_ops):
+        if len(e_ops) != K:
+            raise ValueError("e_ops: %d operator lists for %d objectives" % (len(e_ops), K))
+        return [list(row) for row in e_ops]
+    return [e_ops] * K
+
+
+def propagate_objectives(objectives, tlist, *, propagator, e_ops=None, args=None, initial_states=None, expect=None):
+    """:meth:`Objective.propagate` for a whole list of objectives: element k of the returned list equals
+    ``objectives[k].propagate(tlist, propagator=propagator, e_ops=e_ops, args=args, rho0=initial_states[k],
+    expect=expect)`` -- the ``guess_dynamics`` / ``opt_dynamics`` of every workflow, for an ensemble at once.
+
+    ``e_ops`` is one list of operators for all objectives or a list of one list per objective; ``initial_states``
+    (default: every objective's own ``initial_state``) one state per objective.
+
+    With the device propagators (the condition of :meth:`Objective.propagate`) the list runs on ONE engine -- dense,
+    sparse or Lindblad form as in :func:`~krotov_amd.optimize.optimize_pulses` -- with ONE forward sweep with storage,
+    the controls discretized once.  With ``e_ops`` and the default ``expect`` the expectation values are formed on the
+    device from the stored trajectory (``kh_expect``: ``<psi|O|psi>`` for state vectors, ``tr(O rho)`` for density
+    matrices) and come back in one copy of ``(n_e, K, nt)`` numbers; ``expect[i]`` is real where ``e_ops[i]`` equals
+    its adjoint bit for bit.  A custom ``expect`` callable, lists of mixed dimension or kind and states handed over in
+    another form than the engine's kind are evaluated on the host from the fetched trajectories; any other propagator
+    (or a single grid point) runs the per-objective loop.  One GPU."""
+    from ._ingest import state_array, to_dense
+    from .conversions import control_onto_interval, discretize, extract_controls, extract_controls_mapping
+    from .optimize import _HipBackend, _use_device_path  # (imports this module)
+
+    objectives = list(objectives)
+    K = len(objectives)
+    rows = _e_ops_per_objective(e_ops, K)
+    if initial_states is None:
+        initial_states = [None] * K
+    if len(initial_states) != K:
+        raise ValueError("initial_states: %d states for %d objectives" % (len(initial_states), K))
+    tlist = np.asarray(tlist, dtype=np.float64)
+    props = propagator if isinstance(propagator, list) else [propagator] * K
+    systems = [Objective(initial_state=obj.initial_state if initial_states[k] is None else initial_states[k], H=obj.H,
+                         target=obj.target, c_ops=obj.c_ops) for k, obj in enumerate(objectives)]
+    if K == 0 or len(props) != K or len(tlist) < 2 \
+            or not _use_device_path(propagator, None, None, None, 'array', systems):
+        return [obj.propagate(tlist, propagator=props[k] if len(props) == K else propagator, rho0=initial_states[k],
+                              e_ops=rows[k], args=args, expect=expect) for k, obj in enumerate(objectives)]
+
+    args = {} if args is None else args
+    controls = extract_controls(systems)
+    mapping = extract_controls_mapping(systems, controls)
+    pulses = [control_onto_interval(discretize(control, tlist, args=(args,))) for control in controls]
+    results = []
+    for k in range(K):
+        res = PropagationResult()
+        res.solver = getattr(props[k], '__name__', props[k].__class__.__name__)
+        res.times = np.array(tlist)
+        res.num_expect, res.num_collapse = len(rows[k]), len(systems[k].c_ops)
+        results.append(res)
+
+    def is_matrix(state):
+        arr = state_array(state)
+        return arr.ndim == 2 and arr.shape[0] == arr.shape[1] and arr.shape[0] > 1
+
+    backend = _HipBackend(systems, mapping, tlist, len(controls), propagator)
+    try:
+        _, trajectories = backend.initial_forward(pulses, store=True)
+        store = backend.fw_prev  # (K, nt, N) on the device
+        with_ops = [k for k in range(K) if len(rows[k]) > 0]
+        on_device = (expect is None and len(with_ops) > 0 and backend.layout is None
+                     and all(is_matrix(systems[k].initial_state) == bool(backend.is_super) for k in with_ops))
+        if on_device:
+            n_e = max(len(rows[k]) for k in range(K))
+            table = [rows[k] + [None] * (n_e - len(rows[k])) for k in range(K)]
+            values = backend.engine.expect(store, table).cpu().numpy()  # (n_e, K, nt): the one copy to the host
+            hermitian = {}
+            for k in with_ops:
+                results[k].expect = []
+                for i, oper in enumerate(rows[k]):
+                    if id(oper) not in hermitian:
+                        O = to_dense(oper)
+                        hermitian[id(oper)] = (bool(np.array_equal(O, O.conj().T)), oper)
+                    results[k].expect.append(values[i, k].real.copy() if hermitian[id(oper)][0] else values[i, k].copy())
+        need_states = [k for k in range(K) if len(rows[k]) == 0 or not on_device]
+        if need_states:
+            host = store.cpu().numpy()
+            value = _expectation_value if expect is None else expect
+            for k in need_states:
+                states = [trajectories._state(host[k, n], k, systems[k].initial_state) for n in range(len(tlist))]
+                if len(rows[k]) == 0:
+                    results[k].states = states
+                else:
+                    results[k].expect = [np.array([value(oper, st) for st in states]) for oper in rows[k]]
+    finally:
+        backend.engine.close()
+    return results
 
 
 # ---------------------------------------------------------------------------
