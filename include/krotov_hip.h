@@ -172,8 +172,36 @@ typedef struct kh_problem_lindblad {
 } kh_problem_lindblad;
 int kh_engine_create_lindblad(const kh_problem_lindblad *problem, kh_engine **out);
 
+/* Many independent small optimisations as ONE batch (kh_engine_kernel: "replica16/wave"): `replicas` = B problems of
+ * the same shape -- K_r objectives each, dimension N, L controls, nt grid points, one kind -- that differ in
+ * everything else: operators, states, weights, pulses, shapes, lambda_a and the time grid.  problem->K is the total
+ * B * K_r (divisible by B); the objectives of replica b are k = b K_r ... (b + 1) K_r - 1.  Every sweep is one launch
+ * over the batch; a replica's update sums never leave its workgroup, nothing waits on another workgroup, and a
+ * replica's results depend neither on B nor on where in the batch it sits.
+ *   dt_replicas  host [B][nt-1] time steps of every replica, or NULL: problem->dt for all of them (problem->dt may be
+ *                NULL when dt_replicas is given)
+ * Limits: dense operators, N <= 16, K_r <= 8, 1 <= L <= 4, first-order update, one GPU (KH_ERR_UNSUPPORTED beyond;
+ * NULL or non-divisible arguments: KH_ERR_INVALID; both decided before the first HIP call).  The coefficient set of
+ * the series (Taylor, real spectrum, defect) is chosen from ALL operators of the batch.
+ * kh_forward_store / kh_backward_store / kh_forward_update keep their signatures and their state shapes at K total;
+ * their pulse-like arguments are per replica (see there).  kh_tau, kh_chi_boundary and kh_expect are per objective and
+ * work unchanged.  kh_set_second_order (non-NULL arguments), kh_set_update_workgroups (> 0), kh_set_row_split,
+ * kh_p2p_create_window and kh_update_begin / _step / _step_dev / _end answer KH_ERR_UNSUPPORTED.
+ * kh_last_stats counts products per objective, summed. */
+int kh_engine_create_replicas(const kh_problem *problem, int32_t replicas, const double *dt_replicas, kh_engine **out);
+
+/* Which replicas the following sweeps of a replica engine work on: active_host [B] (host, copied; non-zero: active),
+ * or NULL: all of them.  An inactive replica's workgroups return at once: its slices of EVERY output buffer of every
+ * sweep (stored states, final states, optimized pulses, g_a) keep what they held.  KH_ERR_UNSUPPORTED on any other
+ * engine. */
+int kh_set_active_replicas(kh_engine *engine, const int32_t *active_host);
+
+/* Workgroups of the replica update kernel (64 K_r threads) that one compute unit holds at once, as built
+ * (hipOccupancyMaxActiveBlocksPerMultiprocessor).  Batches up to that x the number of compute units run in one turn. */
+int kh_replica_occupancy(kh_engine *engine, int32_t *workgroups_per_cu);
+
 /* Which kernel family the engine selected: "lindblad/matrix" (kh_engine_create_lindblad), "tile64q2/512", "tile64/512", "tile64/256", "tile64/stream" (more objectives
- * than stay co-resident: one launch, the operators streamed; KH_NO_STREAM=1: "tile64/512 per interval"), "mini16/wave", "mini4/wave", "coop16/mfma", "tile128/512" (per-objective operators, 64 < N <= 128), "ell/csr"
+ * than stay co-resident: one launch, the operators streamed; KH_NO_STREAM=1: "tile64/512 per interval"), "mini16/wave", "mini4/wave", "replica16/wave" (kh_engine_create_replicas), "coop16/mfma", "tile128/512" (per-objective operators, 64 < N <= 128), "ell/csr"
  * (sparse operators with the matrix in registers), "generic", "generic/csr" or "generic/mixed" (kh_engine_create_mixed). */
 const char *kh_engine_kernel(const kh_engine *engine);
 
@@ -185,6 +213,7 @@ const char *kh_engine_kernel(const kh_engine *engine);
  *   states_dev   [K][nt][N] all stored states (index 0 = init), or NULL to
  *                store nothing (first-order Krotov discards them, :329)
  *   psi_T_dev    [K][N] final states
+ * Replica engines (kh_engine_create_replicas): pulses_dev is [B][L][nt-1], every replica under its own pulses.
  */
 int kh_forward_store(kh_engine *engine, const double *pulses_dev,
                      const kh_cdouble *init_dev, kh_cdouble *states_dev,
@@ -196,6 +225,7 @@ int kh_forward_store(kh_engine *engine, const double *pulses_dev,
  * operators, conjugated (real) pulse values, backwards=True.
  *   chi_T_dev    [K][N]
  *   chi_store_dev[K][nt][N]; [:, nt-1] = chi_T
+ * Replica engines (kh_engine_create_replicas): pulses_dev is [B][L][nt-1].
  */
 int kh_backward_store(kh_engine *engine, const kh_cdouble *chi_T_dev,
                       const double *pulses_dev, kh_cdouble *chi_store_dev,
@@ -215,6 +245,8 @@ int kh_backward_store(kh_engine *engine, const kh_cdouble *chi_T_dev,
  *   psi_T_dev     [K][N]    OUT
  *   g_a_dev       [L]       OUT integrals of g_a (optimize.py:475)
  * The cross-objective sum is evaluated in a fixed order (bitwise repeatable).
+ * Replica engines (kh_engine_create_replicas): guess_dev, shape_dev and opt_dev are [B][L][nt-1], lambda_dev and
+ * g_a_dev [B][L]; the sum runs over the K_r objectives of each replica, in objective order.
  */
 int kh_forward_update(kh_engine *engine, const kh_cdouble *chi_store_dev,
                       const double *chi_norms_dev, const kh_cdouble *init_dev,

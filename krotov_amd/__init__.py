@@ -20,6 +20,7 @@ from . import (
     shapes,
 )
 from .objectives import Objective, ensemble_objectives, gate_objectives, propagate_objectives
+from .batch import optimize_pulses_batch
 from .optimize import optimize_pulses
 from .result import Result
 
@@ -37,6 +38,7 @@ __all__ = [
     'mu',
     'objectives',
     'optimize_pulses',
+    'optimize_pulses_batch',
     'parallelization',
     'propagate_objectives',
     'propagators',

@@ -88,6 +88,10 @@ SYMBOLS = {
     'kh_engine_create_mixed': (ctypes.c_int, [ctypes.POINTER(kh_problem), ctypes.POINTER(ctypes.c_int32),
                                               ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_P)]),
     'kh_engine_create_lindblad': (ctypes.c_int, [ctypes.POINTER(kh_problem_lindblad), ctypes.POINTER(_P)]),
+    'kh_engine_create_replicas': (ctypes.c_int, [ctypes.POINTER(kh_problem), ctypes.c_int32, ctypes.POINTER(ctypes.c_double),
+                                                 ctypes.POINTER(_P)]),
+    'kh_set_active_replicas': (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int32)]),
+    'kh_replica_occupancy': (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int32)]),
     'kh_engine_destroy': (None, [_P]),
     'kh_engine_kernel': (ctypes.c_char_p, [_P]),
     'kh_forward_store': (ctypes.c_int, [_P, _P, _P, _P, _P, _P]),

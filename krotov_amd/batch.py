@@ -1,0 +1,394 @@
+"""``optimize_pulses_batch``: many independent small optimisations as one batch on the device.
+
+A *replica* is one complete :func:`~krotov_amd.optimize.optimize_pulses` problem -- its own objectives,
+``pulse_options`` and ``tlist``.  B replicas of the same shape (objectives per replica, dimension, number of
+controls, grid length, kind) run on ONE replica engine (``kh_engine_create_replicas``, kernel family
+``"replica16/wave"``): per Krotov iteration of the whole batch one ``kh_tau``, one ``kh_chi_boundary``, one backward
+sweep and one update sweep, where a Python loop over ``optimize_pulses`` creates B engines and pays three launches per
+replica and iteration.  Replicas stop on their own (``check_convergence``, ``iter_stop``): a finished one is frozen
+through the engine's active mask.  Whatever does not fit one batch runs the replicas one after another through
+``optimize_pulses``, with the same results.
+"""
+import copy
+import logging
+import time
+
+import numpy as np
+
+from . import functionals as _functionals
+from . import optimize as _opt
+from .conversions import pulse_onto_tlist
+from .info_hooks import chain
+from .mixed import layout_of
+from .mu import derivative_wrt_pulse
+from .propagators import HipExpm, LindbladExpm, expm
+from .result import Result
+
+__all__ = ['optimize_pulses_batch']
+
+# the limits of the replica kernels (krotov_amd/csrc/kh_mini.h: KH_MINI_N, KH_MINI_MAXK; kh_replica.h: 1..4 controls)
+REPLICA_NMAX, REPLICA_KMAX, REPLICA_LMAX = 16, 8, 4
+
+
+def _free_device_bytes():
+    """Free memory of the current device, or None where there is none to ask (engine doubles on the host)."""
+    import torch
+
+    if not torch.cuda.is_available():
+        return None
+    return int(torch.cuda.mem_get_info()[0])
+
+
+class _Replica:
+    """One problem of the batch: what ``optimize_pulses`` keeps in local variables, per replica."""
+
+    def __init__(self, problem, propagator, chi_constructor, iter_stop, store_all_pulses, continue_from):
+        self.objectives = problem['objectives']
+        self.pulse_options = problem['pulse_options']
+        self.tlist = problem['tlist']
+        self.adjoint_objectives = [obj.adjoint() for obj in self.objectives]
+        (self.guess_controls, self.guess_pulses, self.pulses_mapping, self.lambda_vals,
+         self.shape_arrays) = _opt._initialize_krotov_controls(self.objectives, self.pulse_options, self.tlist)
+        if continue_from is not None:
+            self.guess_controls, self.guess_pulses = _opt._restore_from_previous_result(
+                continue_from, self.objectives, self.tlist, store_all_pulses)
+        self.continue_from = continue_from
+        self.L = len(self.guess_pulses)
+        self.g_a_integrals = np.zeros(self.L)
+        self.iter_start = 0
+        self.range_stop = iter_stop  # (the driver's loop bound is fixed at the start; a hook changes static_args only)
+        if continue_from is None:
+            self.result = Result()
+            self.result.start_local_time = time.localtime()
+        else:
+            self.result = copy.deepcopy(continue_from)
+        self.static_args = dict(
+            objectives=self.objectives, adjoint_objectives=self.adjoint_objectives, lambda_vals=self.lambda_vals,
+            shape_arrays=self.shape_arrays, tlist=self.tlist, propagator=propagator, chi_constructor=chi_constructor,
+            mu=derivative_wrt_pulse, sigma=None, iter_start=0, iter_stop=iter_stop,
+        )
+        self.optimized_pulses = copy.deepcopy(self.guess_pulses)
+        self.tau_vals = None
+        self.fw_states_T = None
+        self.active = True
+        self.iteration = 0
+
+    def finish(self):
+        """What ``optimize_pulses`` does behind its loop; the Result is not touched afterwards."""
+        self.active = False
+        res = self.result
+        res.end_local_time = time.localtime()
+        res.optimized_controls = [pulse_onto_tlist(np.asarray(p)) for p in self.optimized_pulses]
+        if isinstance(res.states, _opt._LazyStates):
+            res.states = list(res.states)
+
+
+def _batch_obstacle(problems, reps, propagator):
+    """Why these problems cannot run as one batch (a short reason), or None."""
+    if isinstance(propagator, list) or not (propagator is expm or isinstance(propagator, HipExpm)):
+        return "the propagator is not expm / HipExpm"
+    if isinstance(propagator, LindbladExpm) or any(len(o.c_ops) > 0 for r in reps for o in r.objectives):
+        return "objectives with c_ops"
+    if isinstance(propagator, HipExpm) and getattr(propagator, 'sparse', False):
+        return "sparse propagator"
+    layouts = [layout_of(r.objectives, propagator) for r in reps]
+    if any(lay.mixed for lay in layouts):
+        return "objectives of mixed dimension or kind"
+    shapes = {(len(r.objectives), lay.stride, lay.kinds[0], r.L, len(r.tlist)) for r, lay in zip(reps, layouts)}
+    if len(shapes) > 1:
+        return "the problems differ in shape"
+    Kr, N, _, L, _ = next(iter(shapes))
+    if N > REPLICA_NMAX:
+        return "N = %d > %d" % (N, REPLICA_NMAX)
+    if Kr > REPLICA_KMAX:
+        return "%d objectives per problem > %d" % (Kr, REPLICA_KMAX)
+    if L < 1 or L > REPLICA_LMAX:
+        return "%d controls (1..%d)" % (L, REPLICA_LMAX)
+    return None
+
+
+class _ReplicaBackend:
+    """The B replicas of one (sub-)batch resident on one replica engine; every buffer a sweep writes is persistent, so
+    that a frozen replica's slices keep their last values."""
+
+    def __init__(self, reps, propagator):
+        import torch
+
+        from .engine import HipKrotovEngine
+
+        self.torch = t = torch
+        self.reps = reps
+        self.B, self.Kr, self.L = len(reps), len(reps[0].objectives), reps[0].L
+        self.K = self.B * self.Kr
+        layout = layout_of(reps[0].objectives, propagator)
+        self.N, self.is_super = layout.stride, layout.kinds[0]
+        self.nt = len(reps[0].tlist)
+        ops = []
+        for r in reps:
+            ops += _opt._operator_rows(r.objectives, r.pulses_mapping, self.L, _opt.to_dense)[0]
+        dts = np.array([np.diff(np.asarray(r.tlist, dtype=np.float64)) for r in reps])
+        self.engine = eng = HipKrotovEngine(ops, dts, is_super=self.is_super, replicas=self.B)
+        init, targets = [], []
+        for r in reps:
+            lay = layout_of(r.objectives, propagator)
+            r.likes = [obj.initial_state for obj in r.objectives]
+            vecs = [lay.vector(obj.initial_state, k) for k, obj in enumerate(r.objectives)]
+            if any(v is None for v in vecs):
+                raise ValueError("initial states do not match the operator dimension %s" % self.N)
+            init += vecs
+            targets += [lay.vector(obj.target, k) for k, obj in enumerate(r.objectives)]
+            w = [getattr(obj, 'weight', None) for obj in r.objectives]
+            r.weights = None if all(x is None for x in w) else np.array([1.0 if x is None else x for x in w])
+        self.init = eng.dev(np.array(init), t.complex128)
+        self.targets = None if any(v is None for v in targets) else eng.dev(np.array(targets), t.complex128)
+        c128, f64, dev = t.complex128, t.float64, eng.device
+        self.psi_T = t.zeros((self.K, self.N), dtype=c128, device=dev)
+        self.chi_store = t.zeros((self.K, self.nt, self.N), dtype=c128, device=dev)
+        self.opt = t.zeros((self.B, self.L, self.nt - 1), dtype=f64, device=dev)
+        self.g_a = t.zeros((self.B, self.L), dtype=f64, device=dev)
+        self._uploads = {}
+        self._mask = None
+
+    def _cached_upload(self, key, host, dtype=None):
+        hit = self._uploads.get(key)
+        if hit is not None and hit[0].shape == host.shape and np.array_equal(hit[0], host):
+            return hit[1]
+        dev = self.engine.dev(host, dtype if dtype is not None else self.torch.float64)
+        self._uploads[key] = (host.copy(), dev)
+        return dev
+
+    def _pulses(self, key, which):
+        host = np.array([np.array(getattr(r, which), dtype=np.float64).reshape(self.L, self.nt - 1) for r in self.reps])
+        return self._cached_upload(key, host)
+
+    def set_active(self):
+        mask = [1 if r.active else 0 for r in self.reps]
+        if mask != self._mask:
+            self.engine.set_active_replicas(None if all(mask) else mask)
+            self._mask = mask
+
+    def initial_forward(self):
+        self.engine.forward(self._pulses('pulses', 'guess_pulses'), self.init, out=self.psi_T)
+        return self.psi_T.cpu().numpy()
+
+    def tau_vals(self):
+        """(B, K_r) on the host from one kh_tau over all objectives, or None without state targets."""
+        if self.targets is None:
+            return None
+        return self.engine.tau(self.targets, self.psi_T).cpu().numpy().reshape(self.B, self.Kr)
+
+    def iterate(self, chi_T, chi_norms, chi_coef):
+        """One backward and one update sweep over the active replicas.  chi_coef = (c, d), (K,) each: the boundary
+        co-states are formed on the device (kh_chi_boundary); else chi_T (K, N) normalised, chi_norms (K,), host."""
+        t, eng = self.torch, self.engine
+        guess = self._pulses('pulses', 'guess_pulses')
+        shapes = self._pulses('shapes', 'shape_arrays')
+        lambdas = self._cached_upload('lambdas', np.array([np.asarray(r.lambda_vals, dtype=np.float64) for r in self.reps]))
+        if chi_coef is not None:
+            c_dev = self._cached_upload('chi_c', np.ascontiguousarray(chi_coef[0], dtype=np.complex128), t.complex128)
+            d_dev = self._cached_upload('chi_d', np.ascontiguousarray(chi_coef[1], dtype=np.complex128), t.complex128)
+            chi_loc, norms_loc = eng.chi_boundary(self.targets, self.psi_T, c_dev, d_dev)
+        else:
+            chi_loc = eng.dev(chi_T, t.complex128)
+            norms_loc = eng.dev(np.asarray(chi_norms, dtype=np.float64), t.float64)
+        self.set_active()
+        eng.backward(chi_loc, guess, out=self.chi_store)
+        # (the update sweep reads init and the boundary states' buffer is its own: psi_T may be written in place)
+        eng.forward_update(self.chi_store, norms_loc, self.init, guess, shapes, lambdas, out=(self.opt, self.psi_T, self.g_a))
+        eng.check()
+        opt_host = self.opt.cpu().numpy()
+        self._uploads['pulses'] = (opt_host.copy(), self.opt.clone())  # (the next guess of the replicas that go on)
+        return opt_host, self.psi_T.cpu().numpy(), self.g_a.cpu().numpy()
+
+
+def _run_batch(reps, propagator, chi_constructor, check_convergence, info_hook, store_all_pulses):
+    logger = logging.getLogger('krotov')
+    backend = _ReplicaBackend(reps, propagator)
+    Kr = backend.Kr
+
+    def states_of(psi_host, b):
+        return _opt._LazyStates(psi_host[b * Kr:(b + 1) * Kr], reps[b].likes)
+
+    def taus_of(tau, b):
+        return np.array([None] * Kr) if tau is None else tau[b]
+
+    # ---- iteration 0: forward propagation under the guess (optimize.py:295-322), all replicas in one sweep
+    tic = time.time()
+    psi_host = backend.initial_forward()
+    tau = backend.tau_vals()
+    toc = time.time()
+    for b, r in enumerate(reps):
+        r.fw_states_T = states_of(psi_host, b)
+        r.tau_vals = taus_of(tau, b)
+        info = None
+        if info_hook is not None:
+            info = info_hook(
+                backward_states=None, forward_states=None, forward_states0=None, guess_pulses=r.guess_pulses,
+                optimized_pulses=r.optimized_pulses, g_a_integrals=r.g_a_integrals, fw_states_T=r.fw_states_T,
+                tau_vals=r.tau_vals, start_time=tic, stop_time=toc, iteration=0, info_vals=[], shared_data={},
+                **r.static_args,
+            )
+        res = r.result
+        res.tlist = r.tlist
+        res.objectives = r.objectives
+        res.guess_controls = r.guess_controls
+        res.optimized_controls = r.optimized_pulses
+        res.controls_mapping = r.pulses_mapping
+        if r.continue_from is None:
+            if info is not None:
+                res.info_vals.append(info)
+            res.iters.append(0)
+            res.iter_seconds.append(int(toc - tic))
+            if not np.all(r.tau_vals == None):  # noqa: E711
+                res.tau_vals.append(r.tau_vals)
+            if store_all_pulses:
+                res.all_pulses.append(r.guess_pulses)
+        else:
+            r.iter_start = r.continue_from.iters[-1]
+            logger.info("Continuing from previous result, with iteration %d", r.iter_start + 1)
+        res.states = r.fw_states_T
+        r.iteration = r.iter_start
+        if r.iteration + 1 > r.range_stop:  # (an empty loop: optimize.py's for-else)
+            res.message = "Reached %d iterations" % max(r.iter_start, r.range_stop)
+            r.finish()
+
+    # ---- main loop (optimize.py:392-581): one iteration of every active replica per pass
+    while any(r.active for r in reps):
+        tic = time.time()
+        coefs = None
+        if backend.targets is not None:
+            coefs = [_functionals.chi_coefficients(chi_constructor, r.weights, r.tau_vals, Kr) for r in reps]
+            if any(c is None for c in coefs):
+                coefs = None
+        chi_T = chi_norms = chi_coef = None
+        if coefs is not None:
+            chi_coef = (np.concatenate([c[0] for c in coefs]), np.concatenate([c[1] for c in coefs]))
+        else:  # a user's chi_constructor: on the host, per replica, as optimize_pulses does
+            chi_T = np.zeros((backend.K, backend.N), dtype=np.complex128)
+            chi_norms = np.ones(backend.K)
+            layout = layout_of(reps[0].objectives, propagator)
+            for b, r in enumerate(reps):
+                if not r.active:
+                    continue
+                chis = chi_constructor(fw_states_T=r.fw_states_T, objectives=r.objectives, tau_vals=r.tau_vals)
+                norms = [chi.norm() if hasattr(chi, 'norm') else float(np.linalg.norm(np.asarray(chi))) for chi in chis]
+                vecs = [layout.vector(chi / nrm, k) for k, (chi, nrm) in enumerate(zip(chis, norms))]
+                if any(v is None for v in vecs):
+                    raise ValueError("chi_constructor returned states that do not match the state dimension")
+                chi_T[b * Kr:(b + 1) * Kr] = np.array(vecs)
+                chi_norms[b * Kr:(b + 1) * Kr] = norms
+        opt_host, psi_host, g_a = backend.iterate(chi_T, chi_norms, chi_coef)
+        tau = backend.tau_vals()
+        toc = time.time()
+
+        for b, r in enumerate(reps):
+            if not r.active:
+                continue
+            r.iteration += 1
+            logger.info("Finished Krotov iteration %d of problem %d", r.iteration, b)
+            r.optimized_pulses = [opt_host[b, l].copy() for l in range(r.L)]
+            r.fw_states_T = states_of(psi_host, b)
+            r.g_a_integrals[:] = g_a[b]
+            r.tau_vals = taus_of(tau, b)
+            res = r.result
+            info = None
+            if info_hook is not None:
+                info = info_hook(
+                    backward_states=_opt._DeviceTrajectories(backend.chi_store[b * Kr:(b + 1) * Kr], r.likes),
+                    forward_states=None, forward_states0=None, fw_states_T=r.fw_states_T, guess_pulses=r.guess_pulses,
+                    optimized_pulses=r.optimized_pulses, g_a_integrals=r.g_a_integrals, tau_vals=r.tau_vals,
+                    start_time=tic, stop_time=toc, info_vals=res.info_vals, shared_data={}, iteration=r.iteration,
+                    **r.static_args,
+                )
+            res.iters.append(r.iteration)
+            res.iter_seconds.append(int(toc - tic))
+            if info is not None:
+                res.info_vals.append(info)
+            if not np.all(r.tau_vals == None):  # noqa: E711
+                res.tau_vals.append(r.tau_vals)
+            res.optimized_controls = r.optimized_pulses
+            if store_all_pulses:
+                res.all_pulses.append(copy.deepcopy(r.optimized_pulses))
+            res.states = r.fw_states_T
+            msg = None
+            if check_convergence is not None:
+                msg = check_convergence(res)
+            if r.iteration >= r.static_args['iter_stop']:  # a hook may have changed it
+                res.message = "Reached %d iterations" % r.static_args['iter_stop']
+                r.finish()
+            elif bool(msg) is True:
+                res.message = "Reached convergence"
+                if isinstance(msg, str):
+                    res.message += ": " + msg
+                r.finish()
+            elif r.iteration + 1 > r.range_stop:  # (the loop's own end: optimize.py's for-else)
+                res.message = "Reached %d iterations" % max(r.iter_start, r.range_stop)
+                r.finish()
+            else:
+                r.guess_pulses = r.optimized_pulses
+    backend.engine.close()
+
+
+def optimize_pulses_batch(problems, *, propagator, chi_constructor, iter_stop=5000, check_convergence=None,
+                          info_hook=None, modify_params_after_iter=None, store_all_pulses=False, continue_from=None):
+    """Optimise B independent problems (*replicas*) as one batch on the device.
+
+    ``problems``: a sequence of B mappings with the keys ``objectives``, ``pulse_options`` and ``tlist`` -- the first
+    three arguments of :func:`~krotov_amd.optimize.optimize_pulses`; the keywords are shared by all of them
+    (``continue_from``: None or a list of B ``Result`` s).  Returns a list of B ``Result`` s: ``results[b]`` is what
+    ``optimize_pulses(**problems[b], <the shared keywords>)`` returns (``iters``, ``tau_vals``, ``info_vals``,
+    ``all_pulses``, ``optimized_controls``, ``guess_controls``, ``controls_mapping``, ``states``, ``message``; the
+    wall-clock fields aside), and ``info_hook`` / ``modify_params_after_iter`` are called once per replica and
+    iteration with that replica's own keyword arguments (its ``lambda_vals``, ``shape_arrays`` and ``iter_stop`` may be
+    changed in place, as today).
+
+    Replicas of one shape -- the same number of objectives (at most 8), dimension (N <= 16), number of controls (1..4),
+    grid length and kind, dense operators, ``propagator`` :func:`~krotov_amd.propagators.expm` /
+    :class:`~krotov_amd.propagators.HipExpm` -- run on one replica engine (``"replica16/wave"``): one ``kh_tau``, one
+    ``kh_chi_boundary``, one backward and one update sweep per iteration of the whole batch.  ``check_convergence`` and
+    each replica's ``iter_stop`` decide per replica; a finished replica is frozen (the engine's active mask) and its
+    ``Result`` is not touched again; the batch ends when no replica is active.  A batch whose co-state store
+    (B K_r nt N 16 bytes) exceeds a quarter of the free device memory is split into consecutive sub-batches of equal
+    size.  Everything else runs the replicas one after another through ``optimize_pulses`` (logged once as
+    ``"optimize_pulses_batch: sequential (<reason>)"`` on the ``krotov`` logger)."""
+    logger = logging.getLogger('krotov')
+    problems = [dict(p) for p in problems]
+    B = len(problems)
+    if continue_from is not None and len(continue_from) != B:
+        raise ValueError("continue_from must be None or a list of one Result per problem")
+    previous = [None] * B if continue_from is None else list(continue_from)
+    if B == 0:
+        return []
+
+    def sequential(reason):
+        logger.info("optimize_pulses_batch: sequential (%s)", reason)
+        return [_opt.optimize_pulses(
+            p['objectives'], p['pulse_options'], p['tlist'], propagator=propagator, chi_constructor=chi_constructor,
+            iter_stop=iter_stop, check_convergence=check_convergence, info_hook=info_hook,
+            modify_params_after_iter=modify_params_after_iter, store_all_pulses=store_all_pulses, continue_from=prev)
+            for p, prev in zip(problems, previous)]
+
+    if isinstance(propagator, list) or not (propagator is expm or isinstance(propagator, HipExpm)):
+        return sequential("the propagator is not expm / HipExpm")
+    reps = [_Replica(p, propagator, chi_constructor, iter_stop, store_all_pulses, prev)
+            for p, prev in zip(problems, previous)]
+    reason = _batch_obstacle(problems, reps, propagator)
+    if reason is not None:
+        return sequential(reason)
+    if modify_params_after_iter is not None:
+        info_hook = modify_params_after_iter if info_hook is None else chain(modify_params_after_iter, info_hook)
+    logger.info("optimize_pulses_batch: %d problems of %d objectives in one batch", B, len(reps[0].objectives))
+
+    # the co-state store of the whole batch against a quarter of the free device memory
+    size = B
+    free = _free_device_bytes()
+    if free is not None:
+        per_replica = len(reps[0].objectives) * len(reps[0].tlist) * layout_of(reps[0].objectives, propagator).stride * 16
+        while size > 1 and (B % size != 0 or size * per_replica > free // 4):
+            size -= 1
+        if size < B:
+            logger.info("optimize_pulses_batch: %d sub-batches of %d problems (the co-state store of all %d would take "
+                        "%d bytes, a quarter of the free device memory is %d)", B // size, size, B, B * per_replica, free // 4)
+    for i in range(0, B, size):
+        _run_batch(reps[i:i + size], propagator, chi_constructor, check_convergence, info_hook, store_all_pulses)
+    return [r.result for r in reps]

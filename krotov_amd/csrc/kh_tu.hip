@@ -13,6 +13,7 @@
 #include "kh_generic.h"
 #elif KH_TU == KH_TU_MINI
 #include "kh_mini.h"
+#include "kh_replica.h"
 #elif KH_TU == KH_TU_TILE
 #include "kh_tile64.h"
 #elif KH_TU == KH_TU_Q2

@@ -35,6 +35,7 @@
 #include "kh_tile64q2.h"
 #include "kh_coop.h"
 #include "kh_mini.h"
+#include "kh_replica.h"
 #include "kh_ell.h"
 #include "kh_ellg.h"
 #include "kh_ellgs.h"
@@ -73,7 +74,7 @@ static int kh_fail(int code, const char *fmt, ...) {
                            __FILE__, __LINE__);                                               \
     } while (0)
 
-enum KernelKind { KIND_GENERIC = 0, KIND_TILE_RPT2 = 1, KIND_TILE_RPT1 = 2, KIND_TILE_Q2 = 3, KIND_COOP = 4, KIND_ELL = 5, KIND_TILEN = 6, KIND_TILEX = 7 /* plain sweeps only: kind_store */, KIND_LIND = 8 /* kh_engine_create_lindblad */ };
+enum KernelKind { KIND_GENERIC = 0, KIND_TILE_RPT2 = 1, KIND_TILE_RPT1 = 2, KIND_TILE_Q2 = 3, KIND_COOP = 4, KIND_ELL = 5, KIND_TILEN = 6, KIND_TILEX = 7 /* plain sweeps only: kind_store */, KIND_LIND = 8 /* kh_engine_create_lindblad */, KIND_REPLICA = 9 /* kh_engine_create_replicas */ };
 
 // Switches, read from the environment ONCE, at creation (read_switches; not per launch, not per process: engines with
 // different settings coexist)
@@ -214,6 +215,11 @@ struct kh_engine {
     // kh_engine_create_lindblad: d x d Hamiltonians in d_ops_fw / d_ops_bw, the Lindblad operators and A0, B0 per direction
     bool lind = false;
     KhLindArgs lind_fw{}, lind_bw{};
+    // kh_engine_create_replicas: B independent problems of Kr objectives each (K = B Kr; kh_replica.h); d_dt is [B][nt-1]
+    int replicas = 0, Kr = 0;
+    int *d_active = nullptr;     // [B] kh_set_active_replicas
+    bool all_active = true;      // (the kernels then get no mask at all)
+    const int *active_mask() const { return all_active ? nullptr : d_active; }
     KhMixedArgs mixed_fw{}, mixed_bw{};  // device arrays: dims [K], f [K] per direction, mu [K] (both share dims, mu)
     double tol;
     int device, num_cus;
@@ -450,13 +456,14 @@ static int check_residency(const kh_engine *e, const void *func, int threads, si
     return KH_OK;
 }
 
-extern "C" const char *kh_version(void) { return "krotov_hip 0.6 (gfx950; tile64q2, tile64, tile64/stream, tile64x, ens64/mfma, mini16, mini4, coop16/mfma, ell/csr, ellstream/csr, ellglobal/csr, ellsplit/csr, tile128, generic, generic/csr, generic/mixed, lindblad/matrix kernels)"; }
+extern "C" const char *kh_version(void) { return "krotov_hip 0.6 (gfx950; tile64q2, tile64, tile64/stream, tile64x, ens64/mfma, mini16, mini4, replica16/wave, coop16/mfma, ell/csr, ellstream/csr, ellglobal/csr, ellsplit/csr, tile128, generic, generic/csr, generic/mixed, lindblad/matrix kernels)"; }
 
 extern "C" const char *kh_engine_kernel(const kh_engine *e) {
     if (e == nullptr) return "";
     if (e->mixed) return "generic/mixed";
     const KhPlan &p = e->plan;
     if (p.kind == KIND_LIND) return "lindblad/matrix";
+    if (p.kind == KIND_REPLICA) return "replica16/wave";
     if (p.ens) return "ens64/mfma";
     switch (p.kind) {
         case KIND_TILE_RPT2: return "tile64/256";
@@ -1721,6 +1728,128 @@ extern "C" int kh_engine_create_lindblad(const kh_problem_lindblad *pl, kh_engin
     return KH_OK;
 }
 
+// ---- replica engines (kh_engine_create_replicas): B independent small problems in one launch per sweep, kh_replica.h
+// One family for every sweep; the coefficient set comes from the analysis of ALL operators of the batch (one set
+// serves the whole engine); theta <= 1 per sub-step: a term costs no round here.
+static KhPlan plan_replicas(const KhFacts &f, const KhSwitches &sw, int replicas) {
+    KhPlan p;
+    p.kind = p.kind_store = KIND_REPLICA;
+    p.max_wgs = max_update_wgs(f.num_cus);
+    p.grid_update = replicas;
+    p.theta_max = f.theta_max > 0.0 ? f.theta_max : 1.0;
+    p.stage_sq = f.L == 1;  // (one control: the A^2 chain)
+    p.series_rows = true;
+    if (f.real_spectrum) {
+        p.series_cap = 2.0, p.series_defect = 0.0;
+    } else if (f.imag_defect > 0.0 && f.imag_defect <= 0.05 && sw.near_imag) {
+        p.series_cap = 2.0, p.series_defect = f.imag_defect;
+    } else {
+        p.series_rows = false;
+    }
+    return p;
+}
+
+// pr->dt: the largest step of every interval over the replicas (what the operator analysis takes); dt_all: [B][nt-1]
+static int engine_build_replicas(kh_engine *e, const kh_problem *pr, const double *dt_all) {
+    KH_HIP(hipGetDevice(&e->device));
+    hipDeviceProp_t prop;
+    KH_HIP(hipGetDeviceProperties(&prop, e->device));
+    e->num_cus = prop.multiProcessorCount;
+    std::vector<const cplx *> fw, bw;
+    KH_TRY(stage_operators(e, pr, nullptr, nullptr, fw, bw));
+    KH_TRY(dev_upload(e, &e->d_dt, dt_all, sizeof(double) * (size_t)e->replicas * (e->nt - 1)));
+    KhFacts f;
+    f.K = e->K, f.N = e->N, f.L = e->L, f.num_cus = e->num_cus;
+    f.csr = false, f.shared = false;
+    f.has_h1 = fw[1] != nullptr;
+    f.all_h1 = false;
+    f.theta_max = pr->theta_max;
+    KH_TRY(detect_dense(e, pr, f));
+    if (e->sw.taylor) f.real_spectrum = false, f.imag_defect = -1.0;
+    e->adj_sign = 0.0;  // (the sums stay on the forward side)
+    e->plan = plan_replicas(f, e->sw, e->replicas);
+    e->gen_adj_failed = true;
+    std::vector<const cplx *> sq[2];
+    if (e->plan.stage_sq) KH_TRY(stage_squares(e, fw, bw, sq));
+    KH_TRY(stage_series(e));
+    const std::vector<int> ones((size_t)e->replicas, 1);
+    KH_TRY(dev_upload(e, &e->d_active, ones.data(), sizeof(int) * ones.size()));
+    return stage_workspaces(e);
+}
+
+extern "C" int kh_engine_create_replicas(const kh_problem *problem, int32_t replicas, const double *dt_replicas, kh_engine **out) {
+    if (problem == nullptr || out == nullptr) return kh_fail(KH_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (replicas < 1 || problem->K < 1 || problem->K % replicas != 0)
+        return kh_fail(KH_ERR_INVALID, "K = %d objectives are not %d replicas of equal size", problem->K, replicas);
+    if (problem->nt < 2) return kh_fail(KH_ERR_INVALID, "bad sizes K=%d N=%d L=%d nt=%d", problem->K, problem->N, problem->L, problem->nt);
+    // the time steps of every replica, [B][nt-1], and the largest of every interval
+    const size_t M = (size_t)problem->nt - 1;
+    if (dt_replicas == nullptr && problem->dt == nullptr) return kh_fail(KH_ERR_INVALID, "dt/ops missing");
+    std::vector<double> dt_all((size_t)replicas * M), dt_max(M, 0.0);
+    for (int b = 0; b < replicas; ++b)
+        for (size_t n = 0; n < M; ++n) {
+            const double v = dt_replicas != nullptr ? dt_replicas[(size_t)b * M + n] : problem->dt[n];
+            if (!(v > 0.0)) return kh_fail(KH_ERR_INVALID, "replica %d: dt[%zu] = %g is not positive", b, n, v);
+            dt_all[(size_t)b * M + n] = v;
+            dt_max[n] = v > dt_max[n] ? v : dt_max[n];
+        }
+    kh_problem pr = *problem;
+    pr.dt = dt_max.data();
+    KH_TRY(validate_problem(&pr));
+    const int Kr = pr.K / replicas;
+    if (pr.N > KH_MINI_N || Kr > KH_MINI_MAXK || pr.L < 1 || pr.L > 4)
+        return kh_fail(KH_ERR_UNSUPPORTED, "replica engines take N <= %d, at most %d objectives per replica and 1..4 controls (N=%d K_r=%d L=%d)",
+                       KH_MINI_N, KH_MINI_MAXK, pr.N, Kr, pr.L);
+
+    kh_engine *e = new kh_engine();
+    e->K = pr.K;
+    e->N = pr.N;
+    e->L = pr.L;
+    e->nt = pr.nt;
+    e->is_super = pr.is_super ? 1 : 0;
+    e->replicas = replicas;
+    e->Kr = Kr;
+    e->tol = pr.tol > 0.0 ? pr.tol : ldexp(1.0, -53);
+    e->sw = read_switches();
+    const int rc = engine_build_replicas(e, &pr, dt_all.data());
+    if (rc != KH_OK) {
+        kh_engine_destroy(e);
+        return rc;
+    }
+    *out = e;
+    return KH_OK;
+}
+
+extern "C" int kh_set_active_replicas(kh_engine *e, const int32_t *active_host) {
+    if (e == nullptr) return kh_fail(KH_ERR_INVALID, "null engine");
+    if (e->replicas < 1) return kh_fail(KH_ERR_UNSUPPORTED, "only replica engines (kh_engine_create_replicas) take an active mask; this one runs %s", kh_engine_kernel(e));
+    e->all_active = true;
+    if (active_host == nullptr) return KH_OK;
+    std::vector<int> mask((size_t)e->replicas);
+    for (int b = 0; b < e->replicas; ++b) {
+        mask[b] = active_host[b] != 0 ? 1 : 0;
+        if (mask[b] == 0) e->all_active = false;
+    }
+    // (a blocking copy on the null stream: ordered behind the sweeps already launched, done before the next one)
+    KH_HIP(hipMemcpy(e->d_active, mask.data(), sizeof(int) * mask.size(), hipMemcpyHostToDevice));
+    return KH_OK;
+}
+
+// resident workgroups per CU of the replica update kernel as built (hipOccupancyMaxActiveBlocksPerMultiprocessor)
+extern "C" int kh_replica_occupancy(kh_engine *e, int32_t *workgroups_per_cu) {
+    if (e == nullptr || workgroups_per_cu == nullptr) return kh_fail(KH_ERR_INVALID, "null argument");
+    if (e->replicas < 1) return kh_fail(KH_ERR_UNSUPPORTED, "not a replica engine");
+    const void *fn = e->L == 1   ? (const void *)kh_rep_forward_update<1>
+                     : e->L == 2 ? (const void *)kh_rep_forward_update<2>
+                     : e->L == 3 ? (const void *)kh_rep_forward_update<3>
+                                 : (const void *)kh_rep_forward_update<4>;
+    int per_cu = 0;
+    KH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64 * e->Kr, 0));
+    *workgroups_per_cu = per_cu;
+    return KH_OK;
+}
+
 // ---------------------------------------------------------------------------
 // launches
 // ---------------------------------------------------------------------------
@@ -2024,6 +2153,13 @@ static int sweep_store(kh_engine *e, bool backward, const double *pulses, const 
             });
             break;
         }
+        case KIND_REPLICA:  // one single-wave workgroup per objective; pulses [B][L][nt-1]
+            rc = with_tile_L(e->L, [&](auto lt) {
+                launch_plain<kh_rep_sweep_store<decltype(lt)::value>>(dim3(e->K), dim3(64), 0, st, p, sq, pulses, in, store, out, direction,
+                                                                      e->Kr, e->active_mask());
+                return KH_OK;
+            });
+            break;
         case KIND_TILE_RPT2:
         case KIND_TILE_RPT1:
             rc = with_tile(pl.kind_store == KIND_TILE_RPT2, e->L, [&](auto rpt, auto lt) {
@@ -2441,6 +2577,22 @@ extern "C" int kh_forward_update(kh_engine *e, const kh_cdouble *chi_store_dev, 
     if (e->L < 1) return kh_fail(KH_ERR_INVALID, "no controls to update");
     if (opt_dev == guess_dev) return kh_fail(KH_ERR_INVALID, "opt_dev must not alias guess_dev");
     hipStream_t st = (hipStream_t)stream;
+    if (e->replicas > 0) {
+        // replica engines (kh_replica.h): one workgroup per replica, wave w = objective b K_r + w; the kernel reads init_dev
+        // and writes psi_T_dev itself, so that an inactive replica's rows keep what they held
+        KH_HIP(hipMemsetAsync(e->d_stats, 0, sizeof(double) * 4, st));
+        const KhUpdateArgs u = update_args(e, chi_store_dev, chi_norms_dev, guess_dev, shape_dev, lambda_dev, opt_dev, g_a_dev);
+        const KhSweepArgs p = sweep_args(e, false);
+        KH_TRY(with_tile_L(e->L, [&](auto lt) {
+            launch_plain<kh_rep_forward_update<decltype(lt)::value>>(dim3(e->replicas), dim3(64 * e->Kr), 0, st, p, e->d_sq_fw, u,
+                                                                     (const cplx *)init_dev, (cplx *)psi_T_dev, e->Kr, e->active_mask());
+            return KH_OK;
+        }));
+        KH_HIP(hipGetLastError());
+        e->last_intervals = e->nt - 1;
+        e->last_wgs = e->replicas;
+        return KH_OK;
+    }
     if (e->plan.per_interval()) {
         // one launch per interval; on one GPU the "all-reduced" sums are the local ones (kh_reduce_partials has
         // summed the workgroups' pieces in a fixed order)
@@ -2484,6 +2636,7 @@ extern "C" int kh_set_update_workgroups(kh_engine *e, int32_t max_workgroups, in
         e->reduced_G = 0;
         return KH_OK;
     }
+    if (e->replicas > 0) return kh_fail(KH_ERR_UNSUPPORTED, "replica engines (kh_engine_create_replicas) run one workgroup per replica: no form with fewer workgroups");
     if (e->row_split > 1) return kh_fail(KH_ERR_UNSUPPORTED, "a split engine (kh_set_row_split) keeps its own grid: set the row split to 1 first");
     if (e->lind) return kh_fail(KH_ERR_UNSUPPORTED, "Lindblad-form engines (kh_engine_create_lindblad) have no form with fewer workgroups");
     if (e->p2p_ready) return kh_fail(KH_ERR_UNSUPPORTED, "sharded sweeps keep their grid (all ranks must agree on the form)");
@@ -2584,6 +2737,7 @@ extern "C" int kh_set_second_order(kh_engine *e, const kh_cdouble *fw_prev_dev, 
     if (given != 0 && given != 3)
         return kh_fail(KH_ERR_INVALID, "fw_prev, fw_store and sigma must be given together (or all NULL)");
     if (e->lind && given != 0) return kh_fail(KH_ERR_UNSUPPORTED, "Lindblad-form engines (kh_engine_create_lindblad) run the first-order update only");
+    if (e->replicas > 0 && given != 0) return kh_fail(KH_ERR_UNSUPPORTED, "replica engines (kh_engine_create_replicas) run the first-order update only");
     if (fw_prev_dev != nullptr && (const void *)fw_prev_dev == (const void *)fw_store_dev)
         return kh_fail(KH_ERR_INVALID, "fw_store must not alias fw_prev");
     e->so_fw_prev = (const cplx *)fw_prev_dev;
@@ -2600,6 +2754,7 @@ extern "C" int kh_update_begin(kh_engine *e, const kh_cdouble *chi_store_dev, co
         return kh_fail(KH_ERR_INVALID, "null argument");
     if (e->L < 1) return kh_fail(KH_ERR_INVALID, "no controls to update");
     if (e->lind) return kh_fail(KH_ERR_UNSUPPORTED, "Lindblad-form engines (kh_engine_create_lindblad) have no per-interval update sweep");
+    if (e->replicas > 0) return kh_fail(KH_ERR_UNSUPPORTED, "replica engines (kh_engine_create_replicas) have no per-interval update sweep");
     hipStream_t st = (hipStream_t)stream;
     e->guess_dev = guess_dev;
     KH_HIP(hipMemsetAsync(e->d_stats, 0, sizeof(double) * 4, st));
@@ -2619,6 +2774,7 @@ extern "C" int kh_update_step(kh_engine *e, int32_t n, const double *D_dev, cons
         partial_dev == nullptr)
         return kh_fail(KH_ERR_INVALID, "null argument");
     if (e->lind) return kh_fail(KH_ERR_UNSUPPORTED, "Lindblad-form engines (kh_engine_create_lindblad) have no per-interval update sweep");
+    if (e->replicas > 0) return kh_fail(KH_ERR_UNSUPPORTED, "replica engines (kh_engine_create_replicas) have no per-interval update sweep");
     if (e->guess_dev == nullptr) return kh_fail(KH_ERR_INVALID, "kh_update_begin was not called");
     if (n < 0 || n >= e->nt - 1) return kh_fail(KH_ERR_INVALID, "interval %d out of range", n);
     const KhUpdateArgs u = update_args(e, chi_store_dev, chi_norms_dev, e->guess_dev, shape_dev, lambda_dev, opt_dev, g_a_dev);
@@ -2634,6 +2790,7 @@ extern "C" int kh_update_step_dev(kh_engine *e, int32_t *n_dev, const double *D_
         g_a_dev == nullptr || partial_dev == nullptr)
         return kh_fail(KH_ERR_INVALID, "null argument");
     if (e->lind) return kh_fail(KH_ERR_UNSUPPORTED, "Lindblad-form engines (kh_engine_create_lindblad) have no per-interval update sweep");
+    if (e->replicas > 0) return kh_fail(KH_ERR_UNSUPPORTED, "replica engines (kh_engine_create_replicas) have no per-interval update sweep");
     if (e->guess_dev == nullptr) return kh_fail(KH_ERR_INVALID, "kh_update_begin was not called");
     const KhUpdateArgs u = update_args(e, chi_store_dev, chi_norms_dev, e->guess_dev, shape_dev, lambda_dev, opt_dev, g_a_dev);
     return update_interval(e, u, D_dev, 0, 1, n_dev, partial_dev, true, (hipStream_t)stream);  // (n_begin: overridden on the device)
@@ -2642,6 +2799,7 @@ extern "C" int kh_update_step_dev(kh_engine *e, int32_t *n_dev, const double *D_
 extern "C" int kh_update_end(kh_engine *e, kh_cdouble *psi_T_dev, void *stream) {
     if (e == nullptr || psi_T_dev == nullptr) return kh_fail(KH_ERR_INVALID, "null argument");
     if (e->lind) return kh_fail(KH_ERR_UNSUPPORTED, "Lindblad-form engines (kh_engine_create_lindblad) have no per-interval update sweep");
+    if (e->replicas > 0) return kh_fail(KH_ERR_UNSUPPORTED, "replica engines (kh_engine_create_replicas) have no per-interval update sweep");
     KH_HIP(hipMemcpyAsync(psi_T_dev, e->d_phi, sizeof(cplx) * (size_t)e->K * e->N, hipMemcpyDeviceToDevice,
                           (hipStream_t)stream));
     e->guess_dev = nullptr;
@@ -2685,6 +2843,7 @@ extern "C" int kh_p2p_create_window(kh_engine *e, int32_t world, int32_t rank, u
     if (world < 1 || rank < 0 || rank >= world) return kh_fail(KH_ERR_INVALID, "bad world/rank %d/%d", rank, world);
     if (e->mixed) return kh_fail(KH_ERR_UNSUPPORTED, "mixed engines (kh_engine_create_mixed) are not sharded");
     if (e->lind) return kh_fail(KH_ERR_UNSUPPORTED, "Lindblad-form engines (kh_engine_create_lindblad) are not sharded");
+    if (e->replicas > 0) return kh_fail(KH_ERR_UNSUPPORTED, "replica engines (kh_engine_create_replicas) are not sharded");
     const int Lx = e->L > 0 ? e->L : 1;
     if (world * Lx * 2 > 64 || Lx > KH_MAX_L)
         return kh_fail(KH_ERR_UNSUPPORTED, "world * L = %d exceeds the 32 exchange lanes (or more than %d controls)", world * Lx, KH_MAX_L);

@@ -84,12 +84,19 @@ class HipKrotovEngine:
         row_split: sparse engines in the form with global vectors (``"ellglobal/csr"``) only: the rows of every
             objective on this many workgroups (``"ellsplit/csr"``, :meth:`set_row_split`) -- an int, ``'auto'``
             (:func:`auto_row_split`) or ``None``: one workgroup per objective, as before.
+        replicas: B > 0 makes a *replica engine* (``kh_engine_create_replicas``, kernel family ``"replica16/wave"``): the K
+            objectives are B independent problems of K_r = K / B objectives each (objectives b K_r ... (b + 1) K_r - 1
+            belong to replica b), every sweep is one launch over the batch.  ``dt`` is then (nt-1,) for all replicas or
+            (B, nt-1); the sweeps take pulses, shapes and return optimized pulses as (B, L, nt-1), ``lambdas`` and
+            ``g_a`` as (B, L); states keep their (K, ...) shapes.  Dense operators, one kind, N <= 16, K_r <= 8,
+            1 <= L <= 4, first order (``KrotovHipError`` with ``KH_ERR_UNSUPPORTED`` beyond).
     """
 
     def __init__(self, ops, dt, is_super=False, op_norms=None, device=None, tol=0.0, theta_max=0.0, c_ops=None,
-                 row_split=None):
+                 row_split=None, replicas=None):
         _require_gpu()
         self._lib = _lib.load()
+        self.replicas = int(replicas) if replicas else 0
         self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
         self.K = len(ops)
         self.L = len(ops[0]) - 1
@@ -97,7 +104,16 @@ class HipKrotovEngine:
         if len(kinds) != self.K:
             raise ValueError("is_super: %d entries for %d objectives" % (len(kinds), self.K))
         dt = np.ascontiguousarray(np.asarray(dt, dtype=np.float64))
-        self.nt = len(dt) + 1
+        if self.replicas:
+            if self.K % self.replicas != 0:
+                raise ValueError("%d objectives are not %d replicas of equal size" % (self.K, self.replicas))
+            if dt.ndim == 1:
+                dt = np.ascontiguousarray(np.broadcast_to(dt, (self.replicas, len(dt))))
+            if dt.ndim != 2 or dt.shape[0] != self.replicas:
+                raise ValueError("dt must be (nt-1,) or (replicas, nt-1)")
+        elif dt.ndim != 1:
+            raise ValueError("dt must be (nt-1,)")
+        self.nt = dt.shape[-1] + 1
         self._dt = dt
         self._handle = ctypes.c_void_p()
         self._op_tensors = {}
@@ -115,6 +131,10 @@ class HipKrotovEngine:
             dims = [self.d * self.d] * self.K
             kinds = [True] * self.K
         self.mixed = len(set(dims)) > 1 or len(set(kinds)) > 1
+        if self.replicas and (self.lindblad or self.mixed or row_split is not None or
+                              any(_is_sparse(op) for row in ops for op in row)):
+            raise _lib.KrotovHipError("replica engines take dense operators of one dimension and one kind (no c_ops, no "
+                                      "sparse operators, no row split)", _lib.KH_ERR_UNSUPPORTED)
         self.dims = dims
         self.kinds = kinds
         self.N = max(dims)
@@ -210,7 +230,11 @@ class HipKrotovEngine:
         pr.op_norms = norms.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
         pr.tol = float(tol)
         pr.theta_max = float(theta_max)
-        if self.mixed:
+        if self.replicas:
+            pr.dt = None  # (every replica's own steps: dt is (B, nt-1))
+            _lib.check(self._lib.kh_engine_create_replicas(
+                ctypes.byref(pr), self.replicas, dt.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.byref(self._handle)))
+        elif self.mixed:
             dims = (ctypes.c_int32 * self.K)(*self.dims)
             kinds = (ctypes.c_int32 * self.K)(*[1 if x else 0 for x in self.kinds])
             _lib.check(self._lib.kh_engine_create_mixed(ctypes.byref(pr), dims, kinds, ctypes.byref(self._handle)))
@@ -385,15 +409,47 @@ class HipKrotovEngine:
         return t
 
     # -- sweeps ------------------------------------------------------------
-    def forward(self, pulses, init, store=False):
-        """Propagate ``init`` (K, N) over the grid under ``pulses`` (L, nt-1).
+    def _pulse_shape(self):
+        """(L, nt-1), or (B, L, nt-1) on a replica engine."""
+        return (self.replicas, self.L, self.nt - 1) if self.replicas else (self.L, self.nt - 1)
 
-        Returns ``psi_T`` or ``(psi_T, states)`` with states (K, nt, N).
+    def _out(self, t, shape, dtype):
+        """``t`` as an output buffer (written in place), or a new one."""
+        if t is None:
+            return torch.empty(shape, dtype=dtype, device=self.device)
+        if tuple(t.shape) != tuple(shape) or t.dtype != dtype or not t.is_contiguous() or t.device != self.device:
+            raise ValueError("output buffer must be a contiguous %s %s tensor on %s" % (tuple(shape), dtype, self.device))
+        return t
+
+    def set_active_replicas(self, mask=None):
+        """Replica engines: the following sweeps work on the replicas whose ``mask`` entry (B of them) is non-zero, or on
+        all of them (``None``).  An inactive replica's slices of every output buffer keep what they held
+        (``kh_set_active_replicas``); ``KrotovHipError`` (``KH_ERR_UNSUPPORTED``) on any other engine."""
+        if mask is None:
+            _lib.check(self._lib.kh_set_active_replicas(self._handle, None))
+            return
+        mask = [1 if x else 0 for x in np.asarray(mask).reshape(-1)]
+        if self.replicas and len(mask) != self.replicas:
+            raise ValueError("mask: %d entries for %d replicas" % (len(mask), self.replicas))
+        _lib.check(self._lib.kh_set_active_replicas(self._handle, (ctypes.c_int32 * len(mask))(*mask)))
+
+    def replica_occupancy(self):
+        """Workgroups of the replica update kernel one compute unit holds at once (``kh_replica_occupancy``)."""
+        n = ctypes.c_int32(0)
+        _lib.check(self._lib.kh_replica_occupancy(self._handle, ctypes.byref(n)))
+        return int(n.value)
+
+    def forward(self, pulses, init, store=False, out=None):
+        """Propagate ``init`` (K, N) over the grid under ``pulses`` (L, nt-1) -- replica engines: (B, L, nt-1).
+
+        Returns ``psi_T`` or ``(psi_T, states)`` with states (K, nt, N).  ``out``: ``psi_T`` (``store``: the pair) to
+        write into instead of new tensors.
         """
-        pulses = self._f(pulses, (self.L, self.nt - 1))
+        pulses = self._f(pulses, self._pulse_shape())
         init = self._c(init, (self.K, self.N))
-        psi_T = torch.empty_like(init)
-        states = torch.empty((self.K, self.nt, self.N), dtype=torch.complex128, device=self.device) if store else None
+        out_T, out_states = (out if store else (out, None)) if out is not None else (None, None)
+        psi_T = self._out(out_T, (self.K, self.N), torch.complex128)
+        states = self._out(out_states, (self.K, self.nt, self.N), torch.complex128) if store else None
         with self._timed('forward'):
             _lib.check(self._lib.kh_forward_store(
                 self._handle, pulses.data_ptr(), init.data_ptr(),
@@ -401,8 +457,8 @@ class HipKrotovEngine:
         return (psi_T, states) if store else psi_T
 
     def backward(self, chi_T, pulses, out=None):
-        """Backward sweep storing chi(t_n); returns (K, nt, N)."""
-        pulses = self._f(pulses, (self.L, self.nt - 1))
+        """Backward sweep storing chi(t_n); returns (K, nt, N).  ``pulses``: (L, nt-1) -- replica engines: (B, L, nt-1)."""
+        pulses = self._f(pulses, self._pulse_shape())
         chi_T = self._c(chi_T, (self.K, self.N))
         if out is None:
             out = torch.empty((self.K, self.nt, self.N), dtype=torch.complex128, device=self.device)
@@ -456,17 +512,20 @@ class HipKrotovEngine:
         self.kernel = self._lib.kh_engine_kernel(self._handle).decode()
         return self.row_split
 
-    def forward_update(self, chi_store, chi_norms, init, guess, shape, lambdas):
-        """Forward sweep with sequential update; returns ``(opt, psi_T, g_a)``."""
+    def forward_update(self, chi_store, chi_norms, init, guess, shape, lambdas, out=None):
+        """Forward sweep with sequential update; returns ``(opt, psi_T, g_a)``.  Replica engines: ``guess``, ``shape`` and
+        ``opt`` are (B, L, nt-1), ``lambdas`` and ``g_a`` (B, L).  ``out``: ``(opt, psi_T, g_a)`` tensors to write into."""
+        per_control = (self.replicas, self.L) if self.replicas else (self.L,)
         chi_store = self._c(chi_store, (self.K, self.nt, self.N))
         chi_norms = self._f(chi_norms, (self.K,))
         init = self._c(init, (self.K, self.N))
-        guess = self._f(guess, (self.L, self.nt - 1))
-        shape = self._f(shape, (self.L, self.nt - 1))
-        lambdas = self._f(lambdas, (self.L,))
-        opt = torch.empty_like(guess)
-        psi_T = torch.empty_like(init)
-        g_a = torch.empty((self.L,), dtype=torch.float64, device=self.device)
+        guess = self._f(guess, self._pulse_shape())
+        shape = self._f(shape, self._pulse_shape())
+        lambdas = self._f(lambdas, per_control)
+        out = (None, None, None) if out is None else out
+        opt = self._out(out[0], self._pulse_shape(), torch.float64)
+        psi_T = self._out(out[1], (self.K, self.N), torch.complex128)
+        g_a = self._out(out[2], per_control, torch.float64)
         with self._timed('update'):
             _lib.check(self._lib.kh_forward_update(
                 self._handle, chi_store.data_ptr(), chi_norms.data_ptr(), init.data_ptr(), guess.data_ptr(),

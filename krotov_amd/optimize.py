@@ -417,6 +417,46 @@ def _use_device_path(propagator, mu, overlap, sigma, storage, objectives):
     return all(isinstance(p, LindbladExpm) for p in props)
 
 
+def _operator_rows(objectives, pulses_mapping, L, convert, k0=0, k1=None):
+    """The engine's operator rows ``[H0, H_1 .. H_L]`` (``None``: the control does not occur) and Lindblad operators of
+    objectives k0 .. k1 - 1, every distinct operator converted once: objectives sharing an operator share its copy."""
+    dense = {}
+
+    def dense_of(op):
+        key = id(op)
+        if key not in dense:
+            dense[key] = (convert(op), op)
+        return dense[key][0]
+
+    sums = {}
+
+    def summed(terms):
+        """Dense sum of several operators, cached on their identities so
+        objectives sharing the same nested list share one device copy."""
+        if len(terms) == 1:
+            return dense_of(terms[0])
+        key = tuple(id(t) for t in terms)
+        if key not in sums:
+            total = dense_of(terms[0]).copy()
+            for t in terms[1:]:
+                total = total + dense_of(t)
+            sums[key] = (total, terms)
+        return sums[key][0]
+
+    ops, c_rows = [], []
+    for k in range(k0, len(objectives) if k1 is None else k1):
+        obj = objectives[k]
+        H = obj.H if isinstance(obj.H, list) else [obj.H]
+        drift = [t for t in H if not isinstance(t, list)]
+        row = [summed(drift)]
+        for l in range(L):
+            where = pulses_mapping[k][0][l]
+            row.append(summed([H[i][0] for i in where]) if len(where) else None)
+        ops.append(row)
+        c_rows.append([dense_of(c) for c in obj.c_ops])
+    return ops, c_rows
+
+
 class _HipBackend:
     """All objectives of this rank resident on one GPU."""
 
@@ -470,45 +510,12 @@ class _HipBackend:
         self.layout = layout if layout.mixed else None
         self.K_total = K_total
         L = n_controls
-        dense = {}
         props = propagator if isinstance(propagator, list) else [propagator]
         # operators stay in CSR form on the device when the propagator asks for it
         # (DensityMatrixODEPropagator / HipExpm(sparse=True): large sparse Liouvillians)
         self.sparse = any(isinstance(p, HipExpm) and getattr(p, 'sparse', False) for p in props)
-        convert = to_sparse if self.sparse else to_dense
-
-        def dense_of(op):
-            key = id(op)
-            if key not in dense:
-                dense[key] = (convert(op), op)
-            return dense[key][0]
-
-        sums = {}
-
-        def summed(terms):
-            """Dense sum of several operators, cached on their identities so
-            objectives sharing the same nested list share one device copy."""
-            if len(terms) == 1:
-                return dense_of(terms[0])
-            key = tuple(id(t) for t in terms)
-            if key not in sums:
-                total = dense_of(terms[0]).copy()
-                for t in terms[1:]:
-                    total = total + dense_of(t)
-                sums[key] = (total, terms)
-            return sums[key][0]
-
-        ops, c_rows = [], []
-        for k in range(self.k0, self.k1):
-            obj = objectives[k]
-            H = obj.H if isinstance(obj.H, list) else [obj.H]
-            drift = [t for t in H if not isinstance(t, list)]
-            row = [summed(drift)]
-            for l in range(L):
-                where = pulses_mapping[k][0][l]
-                row.append(summed([H[i][0] for i in where]) if len(where) else None)
-            ops.append(row)
-            c_rows.append([dense_of(c) for c in obj.c_ops])
+        ops, c_rows = _operator_rows(objectives, pulses_mapping, L, to_sparse if self.sparse else to_dense,
+                                     self.k0, self.k1)
         N = layout.stride
         self.is_super = layout.kinds[self.k0:self.k1] if layout.mixed else layout.kinds[self.k0]
         self.N, self.L = N, L
