@@ -360,12 +360,15 @@ def config_sparse_lindblad(d=12, nt=61, K=3, gamma=0.05, lindblad_form=False):
 
 def sparse_ops(spec):
     """``[[op_0, op_1, ...] per objective]`` of a spec as ``scipy.sparse.csr_matrix``
-    objects (one per distinct array, so sharing is preserved)."""
+    objects (one per distinct array, so sharing is preserved; ``None`` -- the control does
+    not occur in the objective -- stays ``None``)."""
     import scipy.sparse as sp
 
     made = {}
 
     def conv(a):
+        if a is None:
+            return None
         if id(a) not in made:
             m = sp.csr_matrix(a)
             m.eliminate_zeros()
@@ -492,11 +495,12 @@ def spec_to_objectives(spec, krotov_module, column_states=True):
     States are handed over as (N, 1) column arrays when ``column_states`` (the
     convention of the reference's numpy mode), else as flat (N,) vectors.
     Objectives whose ``H0``/``Hc`` entries are the same object share the same
-    operator arrays in the nested lists.
+    operator arrays in the nested lists.  Where ``Hc[k][l]`` is ``None`` the
+    control does not occur in objective k: its term is left out of ``H``.
     """
     objectives = []
     for k in range(spec.K):
-        H = [spec.H0[k]] + [[spec.Hc[k][l], spec.controls[l]] for l in range(spec.L)]
+        H = [spec.H0[k]] + [[spec.Hc[k][l], spec.controls[l]] for l in range(spec.L) if spec.Hc[k][l] is not None]
         psi0, tgt = spec.init[k], spec.target[k]
         if column_states:
             psi0, tgt = psi0.reshape(-1, 1), tgt.reshape(-1, 1)

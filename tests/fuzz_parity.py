@@ -6,13 +6,16 @@ scaled and per-objective operators; objectives without one of their controls; Hi
 
 Test infrastructure (it imports ``oracle/``): run on a GPU box,
 
-    python tests/fuzz_parity.py [--seconds 300] [--seed 1] [--cases 0] [--level sweeps|optimize] [--regimes]
+    python tests/fuzz_parity.py [--seconds 300] [--seed 1] [--cases 0] [--level sweeps|optimize] [--regimes] [--drop-any]
 
 prints one line per case (kernel, shape, largest deviation) and a summary; exit code 1 if any case is off by more than
 the tolerance of tests/test_hip_parity.py (1e-12, 1e-11 in Liouville space).  ``tests/test_hip_parity.py::
 test_fuzz_parity_fixed_seed`` runs a fixed-seed slice of it in the suite.  ``--regimes`` (sweeps level) puts every drawn
 problem into a randomly chosen regime of the per-interval series (``ramp``, ``pulse_ramp``, ``tiny``: tests/helpers.py) and adds
 Lindblad-form and mixed-dimension problems; it draws from a generator of its own, so the default stream stays what it is.
+``--drop-any`` (sweeps level) takes a control from an objective of the drawn ``config_c5`` problems more often and where the
+default stream never does -- with one control, with one objective, from objective 0, a middle objective or the last one
+(tests/test_absent_controls.py) -- again decided by a generator of its own.
 """
 import argparse
 import os
@@ -36,8 +39,24 @@ L_CHOICES = [1, 1, 1, 2, 2, 3, 4, 4, 5, 5, 6, 7, 8, 8, 9, 12]
 K_CHOICES = [1, 2, 3, 4, 5, 6, 8, 9]
 
 
-def draw(rng, drop_controls=True):
-    """A random ProblemSpec (and a tag that says how it was made)."""
+def drop_any_control(rng_drop, spec, tag):
+    """``--drop-any``: with probability 0.6 one control leaves objective 0, a middle objective or the last one (one control
+    and one objective included); ``rng_drop`` is NOT the generator of :func:`draw`."""
+    if rng_drop.random() < 0.6:
+        k, l = int(rng_drop.choice([0, spec.K // 2, spec.K - 1])), int(rng_drop.integers(0, spec.L))
+        if spec.Hc[k][l] is not None:
+            spec.Hc[k] = list(spec.Hc[k])
+            spec.Hc[k][l] = None
+            tag += ' -Hc[%d][%d]' % (k, l)
+    return tag
+
+
+def has_absent_control(spec):
+    return any(op is None for row in getattr(spec, 'Hc', ()) for op in row)
+
+
+def draw(rng, drop_controls=True, rng_drop=None):
+    """A random ProblemSpec (and a tag that says how it was made).  ``rng_drop``: the generator of ``--drop-any``."""
     kind = rng.choice(['c5', 'c5', 'c5', 'c5', 'c5', 'c4', 'sparse', 'manyK'])
     if kind == 'c4':  # Liouville space, shared operator list, one control (cooperative / generic kernels)
         d = int(rng.choice([3, 4, 5, 6, 8, 9]))
@@ -57,7 +76,10 @@ def draw(rng, drop_controls=True):
         nt = int(rng.integers(3, 7))
         distinct = bool(rng.integers(0, 2))
         spec = configs.config_c5(K=K, N=N, nt=nt, L=L, distinct=distinct, seed=int(rng.integers(0, 1000)))
-        return spec, 'c5(K=%d, N=%d, nt=%d, L=%d%s)' % (K, N, nt, L, ', distinct' if distinct else ''), None
+        tag = 'c5(K=%d, N=%d, nt=%d, L=%d%s)' % (K, N, nt, L, ', distinct' if distinct else '')
+        if rng_drop is not None:
+            tag = drop_any_control(rng_drop, spec, tag)
+        return spec, tag, None
     N = int(rng.choice(N_CHOICES))
     L = int(rng.choice(L_CHOICES))
     K = int(rng.choice(K_CHOICES))
@@ -71,6 +93,8 @@ def draw(rng, drop_controls=True):
         k, l = int(rng.integers(0, K)), int(rng.integers(0, L))
         spec.Hc[k][l] = None
         tag += ' -Hc[%d][%d]' % (k, l)
+    if rng_drop is not None:
+        tag = drop_any_control(rng_drop, spec, tag)
     if rng.random() < 0.15:  # all objectives share ONE operator list (what gate_objectives builds)
         for k in range(1, K):
             spec.H0[k] = spec.H0[0]
@@ -223,10 +247,14 @@ def run_optimize_case(spec, fmt, rng):
     return '%s chis_%s%s' % (engine_mod.LAST_ENGINE().kernel, spec.chi, ' 2nd' if second else ''), dev
 
 
-def fuzz(seed, seconds=None, cases=None, verbose=True, level='sweeps', regimes=False):
-    """Run random cases until `seconds` have passed or `cases` are done; returns (number run, list of failures)."""
+def fuzz(seed, seconds=None, cases=None, verbose=True, level='sweeps', regimes=False, drop_any=False, stats=None):
+    """Run random cases until `seconds` have passed or `cases` are done; returns (number run, list of failures).
+    ``stats``: a dict that receives how many cases had an absent control (``'absent'``) and how many of those had one
+    control (``'absent_L1'``)."""
     rng = np.random.default_rng(seed)
     rng_regimes = np.random.default_rng([int(seed), 0x7e91]) if regimes else None  # (the default stream stays untouched)
+    rng_drop = np.random.default_rng([int(seed), 0xd709]) if drop_any and level == 'sweeps' else None  # (likewise)
+    counts = {'absent': 0, 'absent_L1': 0}
     t0 = time.time()
     done, failures, by_kernel = 0, [], {}
     while True:
@@ -235,7 +263,10 @@ def fuzz(seed, seconds=None, cases=None, verbose=True, level='sweeps', regimes=F
         if seconds is not None and time.time() - t0 > seconds:
             break
         # (optimize level: every Objective lists every control -- configs.spec_to_objectives has no form for a missing one)
-        spec, tag, fmt = draw(rng, drop_controls=level != 'optimize')
+        spec, tag, fmt = draw(rng, drop_controls=level != 'optimize', rng_drop=rng_drop)
+        if has_absent_control(spec):  # (counted on the problem itself: a shared operator list may have taken the entry back)
+            counts['absent'] += 1
+            counts['absent_L1'] += 1 if spec.L == 1 else 0
         if level == 'optimize' and spec.L > spec.N:
             # more controls than state dimensions: after two iterations with the host's own ||chi|| any two implementations
             # are 1e-10 apart (seed 24: generic kernels, K = 1, N = 2, L = 12, first order) -- conditioning, not a kernel
@@ -264,6 +295,8 @@ def fuzz(seed, seconds=None, cases=None, verbose=True, level='sweeps', regimes=F
         if verbose:
             print(('ok   ' if ok else 'FAIL ') + line, flush=True)
         done += 1
+    if stats is not None:
+        stats.update(counts)
     if verbose:
         print('%d cases in %.0f s, %d failed; kernels: %s' % (done, time.time() - t0, len(failures),
                                                              ', '.join('%s x %d' % kv for kv in sorted(by_kernel.items()))))
@@ -280,6 +313,10 @@ if __name__ == '__main__':
     ap.add_argument('--regimes', action='store_true',
                     help="put every drawn problem into a random regime of the series (ramp, pulse_ramp, tiny) and add Lindblad-form "
                          "and mixed-dimension problems; drawn from a separate generator")
+    ap.add_argument('--drop-any', action='store_true',
+                    help="drawn config_c5 problems lose a control more often, also with one control or one objective and from "
+                         "objective 0, a middle or the last objective; decided by a separate generator (sweeps level)")
     a = ap.parse_args()
-    n, bad = fuzz(a.seed, seconds=None if a.cases else a.seconds, cases=a.cases or None, level=a.level, regimes=a.regimes)
+    n, bad = fuzz(a.seed, seconds=None if a.cases else a.seconds, cases=a.cases or None, level=a.level, regimes=a.regimes,
+                  drop_any=a.drop_any)
     sys.exit(1 if bad else 0)

@@ -2550,3 +2550,18 @@ def test_fuzz_parity_fixed_seed():
     done, failures = fuzz_parity.fuzz(seed=20260930, cases=40, verbose=False)
     assert done == 40 and not failures, '\n'.join(failures)
 
+
+def test_fuzz_parity_absent_controls_fixed_seed():
+    """A fixed-seed slice of ``tests/fuzz_parity.py --drop-any``: 40 drawn problems (as many as the test above: the
+    oracle's share, which dominates, is 4 s here against 8 s there), 18 of them with a control that an objective does not
+    have -- 4 with one control: K = 513 and 520 ensemble members without it (objective 0, the last one), N = 81 on the
+    register-generator kernels, K = 9 at N = 4; two problems of one objective (K = 1) among the rest."""
+    import fuzz_parity
+
+    stats = {}
+    done, failures = fuzz_parity.fuzz(seed=20261018, cases=40, verbose=True, drop_any=True, stats=stats)
+    print(stats)
+    assert done == 40 and not failures, '\n'.join(failures)
+    assert stats == {'absent': 18, 'absent_L1': 4}
+    assert 3 * stats['absent'] >= done and stats['absent_L1'] >= 1
+

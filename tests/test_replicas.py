@@ -50,6 +50,11 @@ def _tls(j, nt=5):
 def batch(name):
     if name == 'L1_small':
         return [_replica(_c5(b, 3, 5, 9), b) for b in range(5)]
+    if name == 'L1_absent':  # (tests/test_absent_controls.py) objective 0 of replica 1 lacks the only control
+        reps = [_replica(_c5(b, 3, 5, 9), b) for b in range(3)]
+        reps[1].Hc = [list(row) for row in reps[1].Hc]
+        reps[1].Hc[0][0] = None
+        return reps
     if name == 'L1_full':
         return [_replica(_c5(b, 8, 16, 7, seed0=10), b) for b in range(3)]
     if name == 'L2':
