@@ -6,7 +6,7 @@ scaled and per-objective operators; objectives without one of their controls; Hi
 
 Test infrastructure (it imports ``oracle/``): run on a GPU box,
 
-    python tests/fuzz_parity.py [--seconds 300] [--seed 1] [--cases 0] [--level sweeps|optimize] [--regimes] [--drop-any]
+    python tests/fuzz_parity.py [--seconds 300] [--seed 1] [--cases 0] [--level sweeps|optimize] [--regimes] [--drop-any] [--nonselfadjoint]
 
 prints one line per case (kernel, shape, largest deviation) and a summary; exit code 1 if any case is off by more than
 the tolerance of tests/test_hip_parity.py (1e-12, 1e-11 in Liouville space).  ``tests/test_hip_parity.py::
@@ -15,7 +15,9 @@ problem into a randomly chosen regime of the per-interval series (``ramp``, ``pu
 Lindblad-form and mixed-dimension problems; it draws from a generator of its own, so the default stream stays what it is.
 ``--drop-any`` (sweeps level) takes a control from an objective of the drawn ``config_c5`` problems more often and where the
 default stream never does -- with one control, with one objective, from objective 0, a middle objective or the last one
-(tests/test_absent_controls.py) -- again decided by a generator of its own.
+(tests/test_absent_controls.py) -- again decided by a generator of its own.  ``--nonselfadjoint`` (sweeps level) replaces a
+random subset of the controls of the drawn ``config_c5`` problems by operators that are not Hermitian (``lower``, ``ladder``,
+``anti``: tests/test_nonselfadjoint_controls.py), by a third generator of its own.
 """
 import argparse
 import os
@@ -51,12 +53,44 @@ def drop_any_control(rng_drop, spec, tag):
     return tag
 
 
+NSA_KINDS = ('lower', 'ladder', 'anti')
+
+
+def nonselfadjoint_controls(rng_nsa, spec, tag):
+    """``--nonselfadjoint``: one or two controls (of all objectives, of the last one, or of a random subset) become
+    ``lower`` / ``ladder`` / ``anti`` variants of themselves, the ensemble's scales kept (``spec.mu``); ``spec.changed``:
+    {(k, l): kind}.  The part that makes the generator non-normal is scaled so that, times the guess's 0.5 and the total
+    time, it stays at 0.5 per changed control: the states stay O(1).  ``rng_nsa`` is NOT the generator of :func:`draw`."""
+    spec.changed = {}
+    if rng_nsa.random() < 0.15:  # (some problems stay as they are)
+        return tag
+    nt = len(spec.tlist)
+    weight = min(1.0, 10.0 / (nt - 1))
+    for l in sorted({int(l) for l in rng_nsa.integers(0, spec.L, size=int(rng_nsa.integers(1, 3)))}):
+        kind = str(rng_nsa.choice(NSA_KINDS))
+        where = str(rng_nsa.choice(['all', 'last', 'some']))
+        ks = {'all': list(range(spec.K)), 'last': [spec.K - 1]}.get(where) or [k for k in range(spec.K) if rng_nsa.random() < 0.5]
+        base = next((spec.Hc[k][l] / spec.mu[k] for k in range(spec.K) if spec.Hc[k][l] is not None), None)
+        if base is None:
+            continue
+        new = hp.nonselfadjoint_variant(kind, base, rng_nsa)
+        new = weight * new if kind != 'lower' else base + weight * (new - base)
+        spec.Hc = [list(row) for row in spec.Hc]
+        for k in ks:
+            if spec.Hc[k][l] is not None:
+                spec.Hc[k][l] = spec.mu[k] * new
+                spec.changed[k, l] = kind
+        tag += ' %s[%s][%d]' % (kind, where, l)
+    return tag
+
+
 def has_absent_control(spec):
     return any(op is None for row in getattr(spec, 'Hc', ()) for op in row)
 
 
-def draw(rng, drop_controls=True, rng_drop=None):
-    """A random ProblemSpec (and a tag that says how it was made).  ``rng_drop``: the generator of ``--drop-any``."""
+def draw(rng, drop_controls=True, rng_drop=None, rng_nsa=None):
+    """A random ProblemSpec (and a tag that says how it was made).  ``rng_drop``: the generator of ``--drop-any``;
+    ``rng_nsa``: that of ``--nonselfadjoint``."""
     kind = rng.choice(['c5', 'c5', 'c5', 'c5', 'c5', 'c4', 'sparse', 'manyK'])
     if kind == 'c4':  # Liouville space, shared operator list, one control (cooperative / generic kernels)
         d = int(rng.choice([3, 4, 5, 6, 8, 9]))
@@ -79,6 +113,8 @@ def draw(rng, drop_controls=True, rng_drop=None):
         tag = 'c5(K=%d, N=%d, nt=%d, L=%d%s)' % (K, N, nt, L, ', distinct' if distinct else '')
         if rng_drop is not None:
             tag = drop_any_control(rng_drop, spec, tag)
+        if rng_nsa is not None:
+            tag = nonselfadjoint_controls(rng_nsa, spec, tag)
         return spec, tag, None
     N = int(rng.choice(N_CHOICES))
     L = int(rng.choice(L_CHOICES))
@@ -95,10 +131,14 @@ def draw(rng, drop_controls=True, rng_drop=None):
         tag += ' -Hc[%d][%d]' % (k, l)
     if rng_drop is not None:
         tag = drop_any_control(rng_drop, spec, tag)
+    if rng_nsa is not None:
+        tag = nonselfadjoint_controls(rng_nsa, spec, tag)
     if rng.random() < 0.15:  # all objectives share ONE operator list (what gate_objectives builds)
         for k in range(1, K):
             spec.H0[k] = spec.H0[0]
             spec.Hc[k] = spec.Hc[0]
+        if rng_nsa is not None:  # (objective 0's controls are everybody's now)
+            spec.changed = {(k, l): kind for (k0, l), kind in spec.changed.items() if k0 == 0 for k in range(K)}
         tag += ' shared'
     return spec, tag, None
 
@@ -247,14 +287,18 @@ def run_optimize_case(spec, fmt, rng):
     return '%s chis_%s%s' % (engine_mod.LAST_ENGINE().kernel, spec.chi, ' 2nd' if second else ''), dev
 
 
-def fuzz(seed, seconds=None, cases=None, verbose=True, level='sweeps', regimes=False, drop_any=False, stats=None):
+def fuzz(seed, seconds=None, cases=None, verbose=True, level='sweeps', regimes=False, drop_any=False, stats=None,
+         nonselfadjoint=False):
     """Run random cases until `seconds` have passed or `cases` are done; returns (number run, list of failures).
     ``stats``: a dict that receives how many cases had an absent control (``'absent'``) and how many of those had one
-    control (``'absent_L1'``)."""
+    control (``'absent_L1'``), and how many a control that is not self-adjoint (``'nonselfadjoint'``)."""
     rng = np.random.default_rng(seed)
     rng_regimes = np.random.default_rng([int(seed), 0x7e91]) if regimes else None  # (the default stream stays untouched)
     rng_drop = np.random.default_rng([int(seed), 0xd709]) if drop_any and level == 'sweeps' else None  # (likewise)
+    rng_nsa = np.random.default_rng([int(seed), 0x5ad1]) if nonselfadjoint and level == 'sweeps' else None  # (likewise)
     counts = {'absent': 0, 'absent_L1': 0}
+    if rng_nsa is not None:  # (the key only where it was asked for: the older tests compare the whole dict)
+        counts['nonselfadjoint'] = 0
     t0 = time.time()
     done, failures, by_kernel = 0, [], {}
     while True:
@@ -263,7 +307,9 @@ def fuzz(seed, seconds=None, cases=None, verbose=True, level='sweeps', regimes=F
         if seconds is not None and time.time() - t0 > seconds:
             break
         # (optimize level: every Objective lists every control -- configs.spec_to_objectives has no form for a missing one)
-        spec, tag, fmt = draw(rng, drop_controls=level != 'optimize', rng_drop=rng_drop)
+        spec, tag, fmt = draw(rng, drop_controls=level != 'optimize', rng_drop=rng_drop, rng_nsa=rng_nsa)
+        if rng_nsa is not None:
+            counts['nonselfadjoint'] += 1 if getattr(spec, 'changed', None) else 0
         if has_absent_control(spec):  # (counted on the problem itself: a shared operator list may have taken the entry back)
             counts['absent'] += 1
             counts['absent_L1'] += 1 if spec.L == 1 else 0
@@ -316,7 +362,10 @@ if __name__ == '__main__':
     ap.add_argument('--drop-any', action='store_true',
                     help="drawn config_c5 problems lose a control more often, also with one control or one objective and from "
                          "objective 0, a middle or the last objective; decided by a separate generator (sweeps level)")
+    ap.add_argument('--nonselfadjoint', action='store_true',
+                    help="a random subset of the controls of the drawn config_c5 problems becomes lower / ladder / anti variants "
+                         "(not Hermitian); decided by a separate generator (sweeps level)")
     a = ap.parse_args()
     n, bad = fuzz(a.seed, seconds=None if a.cases else a.seconds, cases=a.cases or None, level=a.level, regimes=a.regimes,
-                  drop_any=a.drop_any)
+                  drop_any=a.drop_any, nonselfadjoint=a.nonselfadjoint)
     sys.exit(1 if bad else 0)

@@ -372,6 +372,35 @@ def series_degree_tables(theta_cap=2.0, defect=3e-3):
     return out
 
 
+def series_coefficients(theta_cap=2.0):
+    """(theta_b[m], c[m][j]) of the real-spectrum (Chebyshev-form) series with the cap ``theta_cap`` from the library's
+    exported host code: the polynomial of degree m is sum_j c[m][j] Z^j with Z = f A dt (``ratios``: c_0, c_1, c_j / c_{j-1})."""
+    import ctypes
+
+    from krotov_amd import _lib
+
+    lib = _lib.load()
+    th, ra = (ctypes.c_double * 65)(), (ctypes.c_double * (65 * 65))()
+    assert lib.kh_series_tables_defect(0.0, theta_cap, 0.0, th, ra) == 0
+    ratios = np.array(ra).reshape(65, 65)
+    coeff = np.zeros((65, 65))
+    coeff[:, :2] = ratios[:, :2]
+    for j in range(2, 65):
+        coeff[:, j] = coeff[:, j - 1] * ratios[:, j]
+    return np.array(th), coeff
+
+
+def series_polynomial(c, Z):
+    """sum_j c[j] Z^j (Horner) for a matrix or an array of scalars ``Z``."""
+    Z = np.asarray(Z, dtype=np.complex128)
+    one = np.eye(Z.shape[0], dtype=np.complex128) if Z.ndim == 2 else np.ones_like(Z)
+    mul = (lambda a, b: a @ b) if Z.ndim == 2 else (lambda a, b: a * b)
+    out = c[-1] * one
+    for cj in c[-2::-1]:
+        out = mul(Z, out) + cj * one
+    return out
+
+
 def series_plan(theta, theta_max, tab):
     """(nsub_n, degree_n) of a sequence theta_n: ``kh_degree_lookup`` restated (sub-steps beyond theta_max; the smallest
     degree m >= 1 whose threshold tab[m] serves theta_n / nsub_n)."""
@@ -484,3 +513,31 @@ class MemoExpm:
     def __exit__(self, *exc):
         ko.expm_dense = self._orig
         return False
+
+
+# ---------------------------------------------------------------------------
+# Controls that are not self-adjoint (tests/test_nonselfadjoint_controls.py, tests/fuzz_parity.py --nonselfadjoint)
+# ---------------------------------------------------------------------------
+def _ladder_control(rng, N, scale, row_cols=None):
+    """Entries on the super-diagonals 1 and 20 and one dense row (``row_cols`` entries of row N // 2): the non-zero 16 x 16
+    blocks are (g, g), (g, g + 1), (g, g + 2) and a block row, those of the adjoint lie on the other side."""
+    A = np.zeros((N, N), dtype=np.complex128)
+    for off in (1, 20):
+        if off < N:
+            A += np.diag(rng.standard_normal(N - off) + 1j * rng.standard_normal(N - off), off)
+    cols = N if row_cols is None else min(N, row_cols)
+    A[N // 2, :cols] += rng.standard_normal(cols) + 1j * rng.standard_normal(cols)
+    return scale * A / np.linalg.norm(A, 2)
+
+
+def nonselfadjoint_variant(kind, H, rng, row_cols=None):
+    """The control that replaces the Hermitian (or commutator) ``H``; the same spectral norm except ``lower`` (twice)."""
+    N, scale = H.shape[0], np.linalg.norm(H, 2)
+    if kind == 'lower':
+        G = np.tril(rng.standard_normal((N, N)) + 1j * rng.standard_normal((N, N)), -1)
+        return H + G * (scale / np.linalg.norm(G, 2))
+    if kind == 'ladder':
+        return _ladder_control(rng, N, scale, row_cols)
+    if kind == 'anti':
+        return 1j * H
+    raise KeyError(kind)

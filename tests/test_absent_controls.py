@@ -248,13 +248,8 @@ def _mixed_oracle(spec):
     return oracle_adapter(zero)
 
 
-@functools.lru_cache(maxsize=None)
-def problem(name, present=False):
-    """Everything a case's sweeps take (built once; never modified)."""
-    c = CASES[name]
-    spec = c.build()
-    if present:
-        spec = _filled(spec)
+def build_problem(c, spec):
+    """Everything the sweeps of a case ``c`` on ``spec`` take (shared with tests/test_nonselfadjoint_controls.py)."""
     prob = _mixed_oracle(spec) if c.fmt == 'mixed' else spec_to_oracle(spec)
     gp, S, lam = oracle_controls(spec)
     rng = np.random.default_rng(17)
@@ -269,20 +264,34 @@ def problem(name, present=False):
                                  chi_T=chi_T, tol=TOL_LIOUVILLE if prob.is_super else TOL_HILBERT)
 
 
+def compute_sweeps(p, second_order, use_scipy=False):
+    """The oracle's sweeps of a problem of :func:`build_problem`."""
+    out = types.SimpleNamespace(prev=None, so=None)
+    with helpers.MemoExpm():
+        out.fw_T, out.states = ko.forward_propagation(p.prob, p.gp, store=True, use_scipy=use_scipy)
+        out.chi = ko.backward_sweep(p.prob, p.chi_T, p.gp, use_scipy=use_scipy)
+        out.update = ko.forward_update_sweep(p.prob, out.chi, p.norms, p.gp, p.S, p.lam, use_scipy=use_scipy)
+        if second_order:
+            _, out.prev = ko.forward_propagation(p.prob, p.older, store=True, use_scipy=use_scipy)
+            out.so = ko.forward_update_sweep(p.prob, out.chi, p.norms, p.gp, p.S, p.lam, use_scipy=use_scipy,
+                                             sigma_vals=p.sigma_vals, fw_prev=out.prev, store=True)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def problem(name, present=False):
+    """Everything a case's sweeps take (built once; never modified)."""
+    c = CASES[name]
+    spec = c.build()
+    if present:
+        spec = _filled(spec)
+    return build_problem(c, spec)
+
+
 @functools.lru_cache(maxsize=None)
 def oracle_sweeps(name, present=False):
     """The oracle's sweeps of a case, computed once and shared by the GPU test and the witness (never modified)."""
-    p = problem(name, present)
-    out = types.SimpleNamespace(prev=None, so=None)
-    with helpers.MemoExpm():
-        out.fw_T, out.states = ko.forward_propagation(p.prob, p.gp, store=True)
-        out.chi = ko.backward_sweep(p.prob, p.chi_T, p.gp)
-        out.update = ko.forward_update_sweep(p.prob, out.chi, p.norms, p.gp, p.S, p.lam)
-        if CASES[name].so is not None and not present:
-            _, out.prev = ko.forward_propagation(p.prob, p.older, store=True)
-            out.so = ko.forward_update_sweep(p.prob, out.chi, p.norms, p.gp, p.S, p.lam, sigma_vals=p.sigma_vals,
-                                             fw_prev=out.prev, store=True)
-    return out
+    return compute_sweeps(problem(name, present), CASES[name].so is not None and not present)
 
 
 # ---------------------------------------------------------------------------
@@ -405,18 +414,18 @@ def _check(errs, tol, name, what):
         assert err < tol, (name, what, key, err)
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize('name', sorted(CASES))
-def test_absent_control_vs_oracle(name, monkeypatch):
+def check_case(name, c, p, ref, monkeypatch):
+    """The sweeps of case ``c`` (a row of a ``case`` table) on the GPU against the oracle's ``ref`` of problem ``p``: forward
+    with storage, backward, the update sweep in one launch and per interval, second order where ``c.so`` says so; the
+    kernel family and the launched instantiations.  Returns what the single-launch sweeps gave (host arrays), the
+    products the update sweep issued (``matvecs_update``) and the launched instantiations."""
     import torch
 
     from krotov_amd import _lib
     from krotov_amd.engine import HipKrotovEngine
 
-    c = CASES[name]
     for key, value in c.env.items():
         monkeypatch.setenv(key, value)
-    p, ref = problem(name), oracle_sweeps(name)
     spec, init, tol = p.spec, p.prob.init, p.tol
     pulses, Sa, lama = np.array(p.gp), np.array(p.S), np.array(p.lam)
     ref_opt, ref_psi, ref_ga = np.array(ref.update[0]), ref.update[1], ref.update[2]
@@ -434,6 +443,7 @@ def test_absent_control_vs_oracle(name, monkeypatch):
         opt, psi_T, g_a = (x.cpu().numpy() for x in eng.forward_update(chi, p.norms, init, pulses, Sa, lama))
         eng.check()
         launched = list(_lib.kernel_instantiations(launched_only=True))
+        got = types.SimpleNamespace(chi=chi.cpu().numpy(), opt=opt, psi_T=psi_T, g_a=g_a, matvecs_update=eng.stats()['matvecs'])
         _check(dict(states=np.abs(states - ref.states).max(), fw_T=np.abs(fw_T - ref.fw_T).max(),
                     chi=np.abs(chi.cpu().numpy() - ref.chi).max(), opt=np.abs(opt - ref_opt).max() / scale,
                     psi_T=np.abs(psi_T - ref_psi).max(), g_a=np.abs(g_a - ref_ga).max() / ga_scale), tol, name, 'single launch')
@@ -452,7 +462,7 @@ def test_absent_control_vs_oracle(name, monkeypatch):
                         g_a=np.abs(ga3 - ref.so[2]).max() / max(1.0, np.abs(ref.so[2]).max()),
                         fw_store=np.abs(store.cpu().numpy() - ref.so[3]).max()), tol, name, 'second order')
             eng.set_second_order()
-        launched_so = list(_lib.kernel_instantiations(launched_only=True))
+        launched_so = got.launched = list(_lib.kernel_instantiations(launched_only=True))
         print('%s launched: %s' % (name, ', '.join(launched_so)))
         for want in c.expect:
             assert want in launched, (want, launched)
@@ -474,6 +484,13 @@ def test_absent_control_vs_oracle(name, monkeypatch):
                     assert np.array_equal(psi_T, fw_T)
     finally:
         eng.close()
+    return got
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('name', sorted(CASES))
+def test_absent_control_vs_oracle(name, monkeypatch):
+    check_case(name, CASES[name], problem(name), oracle_sweeps(name), monkeypatch)
 
 
 @pytest.mark.gpu
