@@ -415,6 +415,16 @@ int kh_series_tables(int32_t real_spectrum, double tol, double *theta /* [65] */
 int kh_series_tables_defect(double tol, double theta_cap, double defect, double *theta /* [65] */,
                             double *ratios /* [65*65] */);
 
+/* The exactly-Hermitian Chebyshev-form tables (real_spectrum = 1, theta <= 2) with odd degrees too, as an engine
+ * hands them to the workgroup-per-objective two-terms-per-phase kernels (KH_ODD_DEGREES=0: not at all): theta[m] of
+ * an odd m is the largest theta the degree-m truncation serves by the same bound at the same `tol`; even entries equal
+ * kh_series_tables(1, ...) bit for bit; odd m in the Taylor tail repeat m - 1.  Those kernels evaluate degree m as
+ *   T_0 = c_0 v,  T_{2p+2} = r2_p (f h A)^2 T_{2p},  s = h (r1_0 v + sum_{p>=1} r1_p T_{2p}),
+ *   result = sum_p T_{2p} + f A s
+ * with c0[m] = c_0 and rows[(m*32 + p)*2 + {0, 1}] = {r1_p, r2_p}: P = (m + 1) / 2 terms T_0 .. T_{2P-2} and, for an
+ * even m, T_m besides; for an odd m = 2P - 1 the row P - 1 is {r1_{P-1}, 0}.  Host only. */
+int kh_series_tables_odd(double tol, double *theta /* [65] */, double *c0 /* [65] */, double *rows /* [65*32*2] */);
+
 /* The padded row form the sparse kernels keep in registers (host only, no GPU needed; for inspection and tests): the
  * union of the patterns of an operator list (drift + controls; data == NULL: absent; HOST arrays here), entries some
  * control touches in the first Ec slots of every row, every row padded to E entries (multiples of four).

@@ -235,6 +235,11 @@ __host__ inline void kh_bessel_j(double theta, int kmax, long double *J) {
 // tab[m]: largest theta <= 2 the degree-m Chebyshev truncation serves at `tol` (even m; odd m repeat m-1 so
 // that the smallest-degree search never lands on them); c0, rows as above
 //
+// odd_degrees (delta = 0 only; the two-terms-per-phase kernels, which end an odd degree m = 2P - 1 with the A product
+// alone): odd m get an entry of their own by the same error functional at the same tolerance, and the rows
+// {r1_p, r2_p} for p < P - 1, {r1_{P-1}, 0}.  Even entries and rows are those of the even-only table bit for bit (the
+// thresholds increase with m).  Odd m in the Taylor tail beyond theta_cap keep repeating m - 1.
+//
 // theta_cap: largest theta served by the Chebyshev form (2 for the register-tile kernels, which sub-step at theta <= 1
 // anyway; 4 for the cooperative kernels, where a term costs a cross-workgroup round -- measured on the 400-dim
 // Liouvillian of config 4: the power form still reaches 2e-15 at theta = 4, like Taylor's, with degree 22 instead of 30).
@@ -258,7 +263,8 @@ __host__ inline long double kh_bernstein_eta(long double d) {
     return logl(p > q ? p : q);
 }
 __host__ inline void kh_build_real_spectrum_rows(double tol, double *tab /*[KH_MAX_DEGREE+1]*/, double *c0, double *rows,
-                                                 double *ratios, double theta_cap = 2.0, double delta = 0.0) {
+                                                 double *ratios, double theta_cap = 2.0, double delta = 0.0,
+                                                 bool odd_degrees = false) {
     const int TAIL = 40;
     long double J[KH_MAX_DEGREE + TAIL + 2];
     auto err = [&](double theta, int m) {
@@ -278,7 +284,7 @@ __host__ inline void kh_build_real_spectrum_rows(double tol, double *tab /*[KH_M
     kh_build_degree_table(tol, taylor_tab);
     tab[0] = 0.0;
     for (int m = 1; m <= KH_MAX_DEGREE; ++m) {
-        if (m & 1) {
+        if ((m & 1) && (!odd_degrees || delta > 0.0 || taylor_tab[m] >= theta_cap)) {
             tab[m] = tab[m - 1];
             continue;
         }
@@ -322,6 +328,11 @@ __host__ inline void kh_build_real_spectrum_rows(double tol, double *tab /*[KH_M
             const long double den = p == 0 ? 1.0L : c[2 * p];
             rows[((size_t)m * KH_Q2_ROWS + p) * 2 + 0] = (double)(c[2 * p + 1] / den);
             rows[((size_t)m * KH_Q2_ROWS + p) * 2 + 1] = (double)(c[2 * p + 2] / den);
+        }
+        if (m & 1) {  // the last phase of an odd degree: the A product on s alone
+            const int p = m / 2;
+            rows[((size_t)m * KH_Q2_ROWS + p) * 2 + 0] = (double)(c[m] / (p == 0 ? 1.0L : c[m - 1]));
+            rows[((size_t)m * KH_Q2_ROWS + p) * 2 + 1] = 0.0;
         }
     }
 }

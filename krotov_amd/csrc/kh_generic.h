@@ -33,6 +33,7 @@ struct KhSweepArgs {
     const double *q2_theta;   // [KH_MAX_DEGREE+1]
     const double *q2_c0;      // [KH_MAX_DEGREE+1]
     const double *q2_rows;    // [KH_MAX_DEGREE+1][KH_Q2_ROWS][2]   (two-terms-per-phase kernels)
+    int q2_odd;               // the three q2_* tables serve odd degrees (kh_tile64q2.h only; 0 for every other kernel)
     const double *ratios;     // [KH_MAX_DEGREE+1][KH_RATIO_STRIDE]  (one-term-per-phase kernels)
     double *stats;            // [0] += matvecs issued (per objective, summed)
     // generic kernels, dense operators too large for an LDS-resident generator: one N x N scratch matrix per workgroup

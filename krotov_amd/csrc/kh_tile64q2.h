@@ -161,6 +161,10 @@ __device__ __forceinline__ void kh_q2_advance(const KhQ2Lds &s, int tid, double 
 // LAST phase does the one A product (on s) next to its B product: P + 1
 // matrix-vector products per step instead of 2 P, on the same critical path of
 // P phases.  (With m = 14: 8 products instead of 14.)
+// Odd degrees (`odd`: the engine handed this launch the table that serves them, KhSweepArgs::q2_odd).  m = 2P - 1 runs
+// the same P phases; s is complete after t_{m-1} as before, and the last phase does the A product on s alone: no read
+// of the term vector, no B product, no row sums for a term t_{m+1} the degree does not ask for.  P products instead
+// of P + 1.  Without `odd` an odd m evaluates degree m + 1 (Taylor's table has odd entries).
 // `epilogue()` runs once, when the new state is complete in `state` and before the last barrier: work that
 // depends on the new state and must be visible after that barrier rides on it instead of a barrier of its own.
 // Returns the number of matrix-vector products issued.
@@ -168,13 +172,14 @@ template <class Epilogue>
 __device__ __forceinline__ int kh_q2_expm_action(const cplx (&a)[8], const cplx (&b)[8], cplx &state,
                                                  cplx (*buf)[KH_TILE_N], cplx *sbuf, const double2 *inv2, int &cur,
                                                  cplx *store_in, int N, double fre, double fim,
-                                                 double dt, int nsub, int m, int wave, int lane,
+                                                 double dt, int nsub, int m, bool odd, int wave, int lane,
                                                  Epilogue epilogue) {
     const int cg = KhQ2Lanes::cg(lane), row = wave * 8 + KhQ2Lanes::row_out(lane);
     const bool writer = (lane & 7) == 0;
     const double h = nsub == 1 ? dt : dt / nsub;
     const double f2h2 = (fre * fre - fim * fim) * h * h;  // f is purely real or purely imaginary
     const int phases = (m + 1) >> 1;
+    const bool no_last_b = odd && (m & 1);  // (workgroup-uniform)
     if (store_in != nullptr && wave == 0 && lane < N) {
         // the interval's incoming state goes to HBM from here (one LDS read + one fire-and-forget
         // coalesced store, outside the phase loop so the loop carries no exec-mask juggling for it)
@@ -190,26 +195,29 @@ __device__ __forceinline__ int kh_q2_expm_action(const cplx (&a)[8], const cplx 
             __syncthreads();
         }
         for (int ph = 0; ph < phases; ++ph) {
-            const double c2 = f2h2 * inv2[ph].y;  // inv2[p] = {r1_p, r2_p}
-            cplx xv[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) xv[j] = buf[cur][cg + 8 * j];
             const bool last = (ph + 1 == phases);
-            cplx yb = c_make(0.0, 0.0);
+            if (!(last && no_last_b)) {
+                const double c2 = f2h2 * inv2[ph].y;  // inv2[p] = {r1_p, r2_p}
+                cplx xv[8];
 #pragma unroll
-            for (int j = 0; j < 8; ++j) c_fma(yb, b[j], xv[j]);
-            const double t2x = KhQ2Lanes::rowsum(yb.x, c2), t2y = KhQ2Lanes::rowsum(yb.y, c2);
-            state.x += t2x;
-            state.y += t2y;
-            if (!last) {
-                const double hn = h * inv2[ph + 1].x;
-                sacc.x = fma(hn, t2x, sacc.x);
-                sacc.y = fma(hn, t2y, sacc.y);
-                if (writer) {
-                    buf[cur ^ 1][row] = c_make(t2x, t2y);
-                    if (ph + 2 == phases) sbuf[row] = sacc;  // s is complete: next phase multiplies it by A
+                for (int j = 0; j < 8; ++j) xv[j] = buf[cur][cg + 8 * j];
+                cplx yb = c_make(0.0, 0.0);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) c_fma(yb, b[j], xv[j]);
+                const double t2x = KhQ2Lanes::rowsum(yb.x, c2), t2y = KhQ2Lanes::rowsum(yb.y, c2);
+                state.x += t2x;
+                state.y += t2y;
+                if (!last) {
+                    const double hn = h * inv2[ph + 1].x;
+                    sacc.x = fma(hn, t2x, sacc.x);
+                    sacc.y = fma(hn, t2y, sacc.y);
+                    if (writer) {
+                        buf[cur ^ 1][row] = c_make(t2x, t2y);
+                        if (ph + 2 == phases) sbuf[row] = sacc;  // s is complete: next phase multiplies it by A
+                    }
                 }
-            } else {
+            }
+            if (last) {
                 // (the B product is finished before s is fetched: both vectors at once do not fit next to the tiles)
                 __builtin_amdgcn_sched_barrier(0);
                 cplx sv[8];
@@ -218,9 +226,9 @@ __device__ __forceinline__ int kh_q2_expm_action(const cplx (&a)[8], const cplx 
                 cplx ya = c_make(0.0, 0.0);
 #pragma unroll
                 for (int j = 0; j < 8; ++j) c_fma(ya, a[j], sv[j]);
-                const cplx odd = c_mul(c_make(fre, fim), c_make(KhQ2Lanes::rowsum(ya.x, 1.0), KhQ2Lanes::rowsum(ya.y, 1.0)));
-                state.x += odd.x;
-                state.y += odd.y;
+                const cplx odd_sum = c_mul(c_make(fre, fim), c_make(KhQ2Lanes::rowsum(ya.x, 1.0), KhQ2Lanes::rowsum(ya.y, 1.0)));
+                state.x += odd_sum.x;
+                state.y += odd_sum.y;
                 if (writer) buf[cur ^ 1][row] = c_make(state.x, state.y);
                 if (sub + 1 == nsub) epilogue();
             }
@@ -228,7 +236,7 @@ __device__ __forceinline__ int kh_q2_expm_action(const cplx (&a)[8], const cplx 
             cur ^= 1;
         }
     }
-    return nsub * (phases + 1);
+    return nsub * (phases + (no_last_b ? 0 : 1));
 }
 
 // ---------------------------------------------------------------------------
@@ -308,7 +316,7 @@ kh_q2_sweep_store(KhSweepArgs p, const cplx *const *__restrict__ sq, const doubl
             t_build += tq1 - tq0;
 #endif
             matvecs += kh_q2_expm_action(a, b, state, s.buf, s.sbuf, s.inv2, cur, store_in, N, p.fre, p.fim, dt, nsub, m,
-                                         wave, lane, [] {});
+                                         p.q2_odd != 0, wave, lane, [] {});
 #ifdef KH_TIMING
             t_phases += clock64() - tq1;
 #endif
@@ -586,12 +594,12 @@ kh_q2_forward_update(KhSweepArgs p, const cplx *const *__restrict__ sq, KhUpdate
             epilogue();
             __syncthreads();
 #else
-            matvecs += kh_q2_expm_action(a, b, state, s.buf, s.sbuf, s.inv2, cur, fw_out, N, p.fre, p.fim, dt, nsub, m, wave,
-                                         lane, epilogue);
+            matvecs += kh_q2_expm_action(a, b, state, s.buf, s.sbuf, s.inv2, cur, fw_out, N, p.fre, p.fim, dt, nsub, m,
+                                         p.q2_odd != 0, wave, lane, epilogue);
 #endif
         } else {
-            matvecs += kh_q2_expm_action(a, b, state, s.buf, s.sbuf, s.inv2, cur, fw_out, N, p.fre, p.fim, dt, nsub, m, wave,
-                                         lane, [] {});
+            matvecs += kh_q2_expm_action(a, b, state, s.buf, s.sbuf, s.inv2, cur, fw_out, N, p.fre, p.fim, dt, nsub, m,
+                                         p.q2_odd != 0, wave, lane, [] {});
         }
 #ifdef KH_TIMING
         const long long tq2 = clock64();

@@ -82,7 +82,7 @@ struct KhSwitches {
     std::string kernel;  // KH_KERNEL (testing): "generic" | "tile256" | "tile512" | "q2" | "mini" | "coop" | "tilen" | "tilex" | "ellstream" | "ellglobal" | "ellsplit"
     bool kernel_set = false;
     bool kernel_is(const char *name) const { return kernel_set && kernel == name; }
-    bool taylor, no_adj, near_imag, ellstream, stepwise, stream, coop_xcd, coop_sq, coop_adj, tn_h1reg, tx, q2_store, ens2, gen_adj;
+    bool taylor, odd_degrees, no_adj, near_imag, ellstream, stepwise, stream, coop_xcd, coop_sq, coop_adj, tn_h1reg, tx, q2_store, ens2, gen_adj;
     double ell_cap;
     int ell_split, ell_groups;  // KH_ELL_SPLIT (0: 'auto'), KH_ELL_GROUPS (0: no cap)
     int stream_G, coop_cols, ens, ens_min_k, ens_ncg;
@@ -100,6 +100,7 @@ static KhSwitches read_switches() {
     KhSwitches s;
     if (const char *d = getenv("KH_KERNEL")) s.kernel = d, s.kernel_set = true;
     s.taylor = on("KH_TAYLOR");                // plain Taylor coefficients everywhere (A/B)
+    s.odd_degrees = !off("KH_ODD_DEGREES");    // =0: the two-terms-per-phase kernels get the even-only table too (A/B)
     s.no_adj = on("KH_NO_ADJ");                // <chi|H phi> on the forward side (A/B; dense operators)
     s.near_imag = !off("KH_NEAR_IMAG");        // =0: Taylor instead of the near-imaginary form's coefficients (A/B)
     s.ell_cap = 0.0;                           // KH_ELL_CAP (> 0): another theta cap of the padded-row kernels' Chebyshev form
@@ -189,6 +190,9 @@ struct KhPlan {
     double theta_max = 1.0;
     bool series_rows = false;              // series tables: the Chebyshev form's rows (theta cap, Hermitian defect), else Taylor's
     double series_cap = 2.0, series_defect = 0.0;
+    // kh_q2_sweep_store / kh_q2_forward_update launches get the table that also serves odd degrees (sweep_args_q2);
+    // every other kernel the engine launches keeps the even-only one
+    bool q2_odd = false;
 
     // kh_forward_update runs kh_update_begin / _step / _end (no single launch)
     bool per_interval() const { return stepwise_only && !stream && !ens; }
@@ -262,6 +266,7 @@ struct kh_engine {
     const cplx *ens_H0 = nullptr, *ens_H1 = nullptr;
     double *d_ens_scale = nullptr;    // [K]
     double *d_q2_theta = nullptr, *d_q2_c0 = nullptr, *d_q2_rows = nullptr, *d_ratios = nullptr;  // series tables of the register-tile kernels
+    double *d_q2o_theta = nullptr, *d_q2o_c0 = nullptr, *d_q2o_rows = nullptr;  // plan.q2_odd: the tables with odd degrees
     // workspaces
     cplx *d_phi = nullptr;            // [K][N]
     kh_u64 *d_slots = nullptr;        // [2][G][L][2]
@@ -501,10 +506,23 @@ static KhSweepArgs sweep_args(const kh_engine *e, bool backward) {
     p.q2_theta = e->d_q2_theta;
     p.q2_c0 = e->d_q2_c0;
     p.q2_rows = e->d_q2_rows;
+    p.q2_odd = 0;
     p.ratios = e->d_ratios;
     p.stats = e->d_stats;
     p.gen_scratch = e->d_gen_scratch;
     p.gen_scratch_wgs = e->gen_scratch_wgs;
+    return p;
+}
+
+// The arguments of a kh_q2_sweep_store / kh_q2_forward_update launch: the tables that serve odd degrees where the plan
+// has them (exactly Hermitian series).  No other kernel is launched with these.
+static KhSweepArgs sweep_args_q2(const kh_engine *e, KhSweepArgs p) {
+    if (e->plan.q2_odd) {
+        p.q2_theta = e->d_q2o_theta;
+        p.q2_c0 = e->d_q2o_c0;
+        p.q2_rows = e->d_q2o_rows;
+        p.q2_odd = 1;
+    }
     return p;
 }
 
@@ -918,6 +936,10 @@ static KhPlan plan_families(const KhFacts &f, const KhSwitches &sw) {
         p.series_cap = ell_cap, p.series_defect = f.real_spectrum ? 0.0 : f.imag_defect;
     } else if (f.real_spectrum) {
         p.series_cap = 2.0, p.series_defect = 0.0;
+        // the workgroup-per-objective two-terms-per-phase kernels end an odd degree with the A product alone (one
+        // product fewer than the next even degree): their launches, and only theirs, get a table with odd degrees.
+        // Only for this exactly Hermitian form.  KH_ODD_DEGREES=0: the even-only table for them too (A/B switch)
+        p.q2_odd = (p.kind == KIND_TILE_Q2 || p.kind_store == KIND_TILE_Q2) && !p.mini && sw.odd_degrees;
     } else if (f.imag_defect > 0.0 && f.imag_defect <= 0.05 && sw.near_imag) {
         // the same form, with the margin for the Hermitian defect, for the other kernel families (weakly damped
         // Liouvillians, Hamiltonians with a small anti-Hermitian part); KH_NEAR_IMAG=0: Taylor (A/B switch)
@@ -1282,6 +1304,12 @@ static int stage_coop(kh_engine *e, const std::vector<const cplx *> &fw, const s
 static int stage_series(kh_engine *e) {
     std::vector<double> tab(KH_MAX_DEGREE + 1), c0(KH_MAX_DEGREE + 1), rows((size_t)(KH_MAX_DEGREE + 1) * KH_Q2_ROWS * 2),
         ratios((size_t)(KH_MAX_DEGREE + 1) * KH_RATIO_STRIDE);
+    if (e->plan.q2_odd) {  // (before the even-only tables: the vectors are reused)
+        kh_build_real_spectrum_rows(e->tol, tab.data(), c0.data(), rows.data(), ratios.data(), e->plan.series_cap, 0.0, true);
+        KH_TRY(dev_upload(e, &e->d_q2o_theta, tab.data(), sizeof(double) * tab.size()));
+        KH_TRY(dev_upload(e, &e->d_q2o_c0, c0.data(), sizeof(double) * c0.size()));
+        KH_TRY(dev_upload(e, &e->d_q2o_rows, rows.data(), sizeof(double) * rows.size()));
+    }
     if (e->plan.series_rows) {
         kh_build_real_spectrum_rows(e->tol, tab.data(), c0.data(), rows.data(), ratios.data(), e->plan.series_cap,
                                     e->plan.series_defect);
@@ -2095,7 +2123,7 @@ static int sweep_store(kh_engine *e, bool backward, const double *pulses, const 
             else if (pl.mini)
                 launch_plain<kh_mini_sweep_store>(dim3(e->K), dim3(64), 0, st, p, sq, pulses, in, store, out, direction);
             else
-                launch_plain<kh_q2_sweep_store>(dim3(e->K), dim3(KH_Q2_THREADS), kh_q2_lds_bytes(), st, p, sq, pulses, in, store, out, direction);
+                launch_plain<kh_q2_sweep_store>(dim3(e->K), dim3(KH_Q2_THREADS), kh_q2_lds_bytes(), st, sweep_args_q2(e, p), sq, pulses, in, store, out, direction);
             break;
         case KIND_TILEN: {
             const cplx *const *tabs = backward ? e->d_tn_bw : e->d_tn_fw;
@@ -2317,7 +2345,8 @@ static int update_mini(kh_engine *e, const KhSweepArgs &p, const KhUpdateArgs &u
     });
 }
 
-static int update_q2(kh_engine *e, const KhSweepArgs &p, const KhUpdateArgs &u, const KhExchange &ex, hipStream_t st) {
+static int update_q2(kh_engine *e, const KhSweepArgs &p_in, const KhUpdateArgs &u, const KhExchange &ex, hipStream_t st) {
+    const KhSweepArgs p = sweep_args_q2(e, p_in);
     const dim3 g(e->K), b(KH_Q2_THREADS);
     const size_t lds = kh_q2_lds_bytes();
     // (KH_Q2_SINGLE=0: the instantiations with the cross-GPU stage on one GPU too -- A/B switch)
@@ -3043,6 +3072,14 @@ extern "C" int kh_series_tables(int32_t real_spectrum, double tol, double *theta
         kh_build_degree_table(tol, theta);
         kh_build_taylor_rows(c0.data(), rows.data(), ratios);
     }
+    return KH_OK;
+}
+
+extern "C" int kh_series_tables_odd(double tol, double *theta, double *c0, double *rows) {
+    if (theta == nullptr || c0 == nullptr || rows == nullptr) return kh_fail(KH_ERR_INVALID, "null argument");
+    if (!(tol > 0.0)) tol = ldexp(1.0, -53);
+    std::vector<double> ratios((size_t)(KH_MAX_DEGREE + 1) * KH_RATIO_STRIDE);
+    kh_build_real_spectrum_rows(tol, theta, c0, rows, ratios.data(), 2.0, 0.0, true);
     return KH_OK;
 }
 
