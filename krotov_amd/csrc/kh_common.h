@@ -461,6 +461,20 @@ __device__ __forceinline__ bool kh_poll_gave_up(const KhExchange &ex, int lane, 
     return wave_gave_up;
 }
 
+// A slot's two granules in ONE 16-byte load (buffer form: the builtin takes the cache policy; bytes past the buffer read
+// as 0).  Each granule carries its own tag, so only 8-byte atomicity is used.  Not volatile -- the compiler turns that
+// into system scope, sc0 sc1, a slower path --: a polling loop puts kh_compiler_fence() in front of every round instead.
+typedef unsigned int kh_u32x4 __attribute__((ext_vector_type(4)));
+#define KH_CPOL_SC0 1           // workgroup scope (may be served by the L1 / a stale L2 line)
+#define KH_CPOL_SC1 16          // agent scope
+__device__ __forceinline__ void kh_compiler_fence() { asm volatile("" ::: "memory"); }
+template <int CPOL>
+__device__ __forceinline__ void kh_load_granules(__amdgpu_buffer_rsrc_t rsrc, unsigned int byte_off, kh_u64 &a, kh_u64 &b) {
+    const kh_u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)byte_off, 0, CPOL);
+    a = (kh_u64)v.x | ((kh_u64)v.y << 32);
+    b = (kh_u64)v.z | ((kh_u64)v.w << 32);
+}
+
 #define KH_GATHER_CHUNKS 4  // workgroups per lane (default): the exchange handles up to 256 workgroups
 #define KH_GATHER_CHUNKS_WIDE 8  // two 256-thread workgroups per CU: up to 512
 
@@ -472,20 +486,28 @@ __device__ __forceinline__ bool kh_poll_gave_up(const KhExchange &ex, int lane, 
 // every workgroup derives bit-identical pulse values.
 // kh_gather_range: the controls l0 ... l0 + MAXL - 1 of L (the generic kernels gather more than KH_MAX_L controls in
 // groups of KH_MAX_L: a round's granules must fit the registers).
-template <int MAXL, int CH>
+// WIDE: a polling round reads every slot with one 16-byte load instead of two 8-byte ones -- half the load instructions
+// per round, the same lines: scripts/ubench_exchange.hip, 256 workgroups, 1.27 -> 1.20 us per exchange at the best head
+// start of either form (profiles/exchange_layout_ubench.txt).  The poll is out sooner, so the head start that suits it
+// is longer (krotov_hip.hip, KH_ADJ_DELAY).  The values and their order are the same, so are the sums.
+template <int MAXL, int CH, bool WIDE = false>
 __device__ __forceinline__ bool kh_gather_range(const KhExchange &ex, int parity, int L, int l0, unsigned int epoch, int lane,
                                                 double (&out)[MAXL]);
-template <int MAXL, int CH = KH_GATHER_CHUNKS>
+template <int MAXL, int CH = KH_GATHER_CHUNKS, bool WIDE = false>
 __device__ __forceinline__ bool kh_gather(const KhExchange &ex, int parity, int L, unsigned int epoch, int lane,
                                           double (&out)[MAXL]) {
-    return kh_gather_range<MAXL, CH>(ex, parity, L, 0, epoch, lane, out);
+    return kh_gather_range<MAXL, CH, WIDE>(ex, parity, L, 0, epoch, lane, out);
 }
-template <int MAXL, int CH>
+template <int MAXL, int CH, bool WIDE>
 __device__ __forceinline__ bool kh_gather_range(const KhExchange &ex, int parity, int L, int l0, unsigned int epoch, int lane,
                                                 double (&out)[MAXL]) {
     const kh_u64 *base = ex.slots + ((size_t)parity * ex.G * L + l0) * 2;
     L -= l0;  // (controls left from l0 on; the slot stride below keeps the full count)
     const int Lfull = L + l0;
+    // (WIDE: this parity's slots from `base` on as a buffer -- a load past its end returns 0, a stale tag)
+    __amdgpu_buffer_rsrc_t rsrc;
+    if constexpr (WIDE)
+        rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)base, 0, (int)(((size_t)ex.G * Lfull - l0) * 16), 0x00020000);
     kh_u64 a[MAXL][CH], b[MAXL][CH];
     long long t0 = 0;
     unsigned int spins = 0;
@@ -494,12 +516,19 @@ __device__ __forceinline__ bool kh_gather_range(const KhExchange &ex, int parity
     for (int d = 0; d < ex.first_poll_delay; ++d) __builtin_amdgcn_s_sleep(1);
     for (;;) {
         bool ok = true;
+        if constexpr (WIDE) kh_compiler_fence();
 #pragma unroll
         for (int l = 0; l < MAXL; ++l) {
 #pragma unroll
             for (int c = 0; c < CH; ++c) {
                 const int wg = lane + 64 * c;
-                if (l < L && wg < ex.G) {
+                if constexpr (WIDE) {
+                    // (no branch around a load: a lane without a slot reads slot 0 and drops it, so that the round's
+                    // loads issue back to back -- under a branch each the compiler waits for one before the next)
+                    const bool mine = l < L && wg < ex.G;
+                    kh_load_granules<KH_CPOL_SC1>(rsrc, mine ? (unsigned int)(wg * Lfull + l) * 16u : 0u, a[l][c], b[l][c]);
+                    if (!mine) a[l][c] = b[l][c] = (kh_u64)epoch << 32;
+                } else if (l < L && wg < ex.G) {
                     const kh_u64 *g = base + ((size_t)wg * Lfull + l) * 2;
                     a[l][c] = __hip_atomic_load(g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     b[l][c] = __hip_atomic_load(g + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -640,7 +669,7 @@ __device__ __forceinline__ void kh_exchange_publish(const KhExchange &ex, int n,
 // P2P = false: an instantiation for a single GPU (ex.world == 1 by the caller's word) without the cross-GPU stage -- the
 // stage is a run-time branch otherwise, and its code, inlined into a kernel that sits at the register limit, costs the
 // single-GPU path registers it does not use (cooperative update kernel: 236 -> 230 VGPRs, 20.0 -> 19.3 ms on config 4)
-template <int MAXL, int CH = KH_GATHER_CHUNKS, bool P2P = true>
+template <int MAXL, int CH = KH_GATHER_CHUNKS, bool P2P = true, bool WIDE = false>
 __device__ __forceinline__ bool kh_exchange_collect(const KhExchange &ex, int n, int wg, int L, int lane,
                                                     const double *part, double (&out)[MAXL]) {
     if (ex.G == 1 && ex.world == 1) {
@@ -652,7 +681,7 @@ __device__ __forceinline__ bool kh_exchange_collect(const KhExchange &ex, int n,
     const bool timed = P2P && ex.world > 1 && wg == 0 && ex.wait_ticks != nullptr;  // (uniform; scalar clock reads)
     long long t0 = 0;
     if (timed) t0 = wall_clock64();
-    if (!kh_gather<MAXL, CH>(ex, parity, L, (unsigned)(n + 1), lane, out)) return false;
+    if (!kh_gather<MAXL, CH, WIDE>(ex, parity, L, (unsigned)(n + 1), lane, out)) return false;
     if (P2P && ex.world > 1) {
         long long t1 = 0;
         if (timed) t1 = wall_clock64();

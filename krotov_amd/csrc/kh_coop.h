@@ -68,7 +68,6 @@ __device__ __forceinline__ void kh_coop_owner_element(int tid, int &r, int &col)
     }
 }
 
-typedef unsigned int kh_u32x4 __attribute__((ext_vector_type(4)));
 template <class T>
 __device__ __forceinline__ T *kh_uniform_ptr(T *p) {
     const unsigned long long v = (unsigned long long)p;
@@ -379,18 +378,8 @@ __device__ __forceinline__ size_t kh_coop_group4(const KhCoopArgs &c, unsigned i
 __device__ __forceinline__ kh_u64 *kh_coop_slot4(const KhCoopArgs &c, unsigned int rid, int y, int group) {
     return c.vbuf + kh_coop_group4(c, rid, y, group);
 }
-#define KH_CPOL_SC0 1           // workgroup scope (may be served by the L1 / a stale L2 line)
-#define KH_CPOL_SC1 16          // agent scope
-// two granules (16 bytes) of the lane's element; each granule carries its own tag, so only 8-byte atomicity is used.
-// (Not marked volatile: the compiler turns that into system scope, sc0 sc1 -- a slower path.  A polling loop puts a
-// compiler barrier, kh_compiler_fence, before every pass instead.)
-__device__ __forceinline__ void kh_compiler_fence() { asm volatile("" ::: "memory"); }
-template <int CPOL>
-__device__ __forceinline__ void kh_coop_load2(__amdgpu_buffer_rsrc_t rsrc, unsigned int byte_off, kh_u64 &a, kh_u64 &b) {
-    const kh_u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)byte_off, 0, CPOL);
-    a = (kh_u64)v.x | ((kh_u64)v.y << 32);
-    b = (kh_u64)v.z | ((kh_u64)v.w << 32);
-}
+// two granules (16 bytes) of the lane's element: kh_load_granules (kh_common.h; KH_CPOL_SC0 / KH_CPOL_SC1, and
+// kh_compiler_fence before every polling pass)
 
 // owner thread: element (row, col) of round `rid`
 template <int COLS>
@@ -683,15 +672,15 @@ __device__ __forceinline__ void kh_coop_round4(const KhCoopArgs &c, const KhExch
 #pragma unroll
         for (int j = 0; j < MAXG; ++j) {
             const unsigned int off = j < jv ? ring_off + GB * (start + j) : 0xffffff00u;
-            kh_coop_load2<KH_CPOL_SC1>(rsrc, off, g[j][0], g[j][1]);
-            if constexpr (COLS == 4) kh_coop_load2<KH_CPOL_SC1>(rsrc, off + (j < jv ? 1024u : 0u), g[j][2], g[j][3]);
+            kh_load_granules<KH_CPOL_SC1>(rsrc, off, g[j][0], g[j][1]);
+            if constexpr (COLS == 4) kh_load_granules<KH_CPOL_SC1>(rsrc, off + (j < jv ? 1024u : 0u), g[j][2], g[j][3]);
         }
     } else {
 #pragma unroll
         for (int j = 0; j < MAXG; ++j) {
             const unsigned int off = j < jv ? ring_off + GB * (start + j) : 0xffffff00u;
-            kh_coop_load2<KH_CPOL_SC0>(rsrc, off, g[j][0], g[j][1]);
-            if constexpr (COLS == 4) kh_coop_load2<KH_CPOL_SC0>(rsrc, off + (j < jv ? 1024u : 0u), g[j][2], g[j][3]);
+            kh_load_granules<KH_CPOL_SC0>(rsrc, off, g[j][0], g[j][1]);
+            if constexpr (COLS == 4) kh_load_granules<KH_CPOL_SC0>(rsrc, off + (j < jv ? 1024u : 0u), g[j][2], g[j][3]);
         }
     }
 #else
@@ -734,10 +723,10 @@ __device__ __forceinline__ void kh_coop_round4(const KhCoopArgs &c, const KhExch
             if (j < jv) {
                 const unsigned int off = ring_off + GB * (start + j);
                 if ((unsigned int)(g[j][0] >> 32) != epoch || (unsigned int)(g[j][1] >> 32) != epoch)
-                    kh_coop_load2<KH_CPOL_SC1>(rsrc, off, g[j][0], g[j][1]);
+                    kh_load_granules<KH_CPOL_SC1>(rsrc, off, g[j][0], g[j][1]);
                 if constexpr (COLS == 4) {
                     if ((unsigned int)(g[j][2] >> 32) != epoch || (unsigned int)(g[j][3] >> 32) != epoch)
-                        kh_coop_load2<KH_CPOL_SC1>(rsrc, off + 1024u, g[j][2], g[j][3]);
+                        kh_load_granules<KH_CPOL_SC1>(rsrc, off + 1024u, g[j][2], g[j][3]);
                 }
             }
         }

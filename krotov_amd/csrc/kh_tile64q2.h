@@ -359,6 +359,11 @@ kh_q2_forward_update(KhSweepArgs p, const cplx *const *__restrict__ sq, KhUpdate
 #else
     constexpr bool PREFETCH = !SO;
 #endif
+#ifdef KH_Q2_NARROW_POLL  // (A/B build) the exchange polls with two 8-byte loads per slot
+    constexpr bool WIDE_POLL = false;
+#else
+    constexpr bool WIDE_POLL = true;  // one 16-byte load per slot (kh_common.h, kh_gather_range)
+#endif
     if (u.n_dev != nullptr) {  // graph-replayed stepwise mode: interval index from device memory
         u.n_begin = *u.n_dev;
         u.n_end = u.n_begin + 1;
@@ -531,7 +536,7 @@ kh_q2_forward_update(KhSweepArgs p, const cplx *const *__restrict__ sq, KhUpdate
 #ifdef KH_TIMING
                 const long long tc0 = clock64();
 #endif
-                const bool ok = kh_exchange_collect<1, KH_GATHER_CHUNKS, !SINGLE>(ex, n, k, 1, lane, part, D);
+                const bool ok = kh_exchange_collect<1, KH_GATHER_CHUNKS, !SINGLE, WIDE_POLL>(ex, n, k, 1, lane, part, D);
 #ifdef KH_TIMING
                 t_coll += clock64() - tc0;
 #endif

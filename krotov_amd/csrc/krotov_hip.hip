@@ -131,7 +131,11 @@ static KhSwitches read_switches() {
     // controls do not apply their own default
     s.poll_delay_set = getenv("KH_POLL_DELAY") != nullptr;
     s.poll_delay = num("KH_POLL_DELAY", 16);
-    s.adj_poll_delay = num("KH_ADJ_DELAY", 0);  // the same where a matrix-vector product already sits between store and poll
+    // the same where a matrix-vector product already sits between store and poll (kh_q2_forward_update, sums on the
+    // adjoint side).  0 was best while a round polled with two 8-byte loads per slot; the 16-byte polls are out
+    // sooner (the optimum moved by 7 units, ~0.2 us), and a first round that comes back stale costs a second round trip: K = 256, N = 64, update sweep 19.79 ms
+    // at 0, 18.62 at 4, 17.82 at 6 and 7, 17.88 at 8, 18.37 at 12 (18.2 - 18.3 before the change; profiles/exchange_layout.txt)
+    s.adj_poll_delay = num("KH_ADJ_DELAY", 7);
     // the same for the cooperative kernels' block exchange (a polling pass is four 16-byte loads per lane there: an
     // early, stale pass costs little -- measured 0 best)
     s.coop_poll_delay = num("KH_COOP_DELAY", 0);
