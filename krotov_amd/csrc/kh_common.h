@@ -38,8 +38,7 @@ typedef double2 cplx;
 #define KH_TU_TILEX 15
 #define KH_TU_LIND 16
 #define KH_TU_ELLG 17
-#define KH_TU_ELLGS 18
-#define KH_TU_EXPECT 19
+#define KH_TU_EXPECT 18
 #ifndef KH_TU
 #define KH_TU KH_TU_ALL
 #endif

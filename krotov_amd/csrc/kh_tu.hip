@@ -34,8 +34,6 @@
 #include "kh_ell.h"
 #elif KH_TU == KH_TU_ELLG
 #include "kh_ellg.h"
-#elif KH_TU == KH_TU_ELLGS
-#include "kh_ellgs.h"
 #elif KH_TU == KH_TU_EXPECT
 #include "kh_expect.h"
 #else

@@ -38,7 +38,6 @@
 #include "kh_replica.h"
 #include "kh_ell.h"
 #include "kh_ellg.h"
-#include "kh_ellgs.h"
 #include "kh_tilen.h"
 #include "kh_ens.h"
 #include "kh_lind.h"
@@ -248,10 +247,10 @@ struct kh_engine {
     bool gen_fits = true;             // the generic kernels' LDS vectors fit (N <= 2540)
     cplx *d_ell_scratch = nullptr;    // the streamed padded-row form's per-workgroup scratch planes [workgroups][stride]
     long long ell_scratch_stride = 0;
-    cplx *d_ellg_ws = nullptr;        // kh_ellg.h: per-workgroup workspaces [ellg_wgs][stride] (term planes, running sum, values)
+    cplx *d_ellg_ws = nullptr;        // kh_ellg.h: per-group workspaces [ellg_wgs][stride] (term planes, running sum, values)
     long long ellg_ws_stride = 0;
     int ellg_wgs = 0;
-    // kh_ellgs.h (kh_set_row_split): S workgroups per objective on `groups` groups; 1: the kernels of kh_ellg.h
+    // kh_ellg.h's split form (kh_set_row_split): S workgroups per objective on `groups` groups; 1: its plain form
     int row_split = 1, split_groups = 0;
     unsigned int *d_split_counters = nullptr;  // [groups] barrier counters, a memory line each: one block, zeroed per launch
     size_t split_counters_bytes = 0;
@@ -2148,21 +2147,24 @@ static int sweep_store(kh_engine *e, bool backward, const double *pulses, const 
         }
         case KIND_ELL: {
             const KhEll *ells = backward ? e->d_ell_bw : e->d_ell_fw;
-            if (pl.ell_global && e->row_split > 1) {
-                // all S x groups workgroups wait for each other at every term: resident at once, as an update sweep's
-                KH_HIP(hipMemsetAsync(e->d_split_counters, 0, e->split_counters_bytes, st));
-                KhExchange ex = exchange_args(e, false);
-                ex.G = e->split_groups * e->row_split;
-                rc = launch_persistent<kh_ellgs_sweep_store<KH_ELLGS_THREADS>>(
-                    e, dim3(e->split_groups * e->row_split), dim3(KH_ELLGS_THREADS), kh_ellgs_lds_bytes(), st, p, ells,
-                    (const int *)e->d_ell_off, (const cplx *)e->d_ell_vals, pulses, in, store, out, direction, e->d_ellg_ws,
-                    e->ellg_ws_stride, ex, e->row_split, e->d_split_counters);
-                break;
-            }
             if (pl.ell_global) {
-                launch_plain<kh_ellg_sweep_store<KH_ELLG_THREADS>>(dim3(e->ellg_wgs), dim3(KH_ELLG_THREADS), kh_ellg_lds_bytes(), st, p, ells,
-                                                                   (const int *)e->d_ell_off, (const cplx *)e->d_ell_vals, pulses, in, store, out,
-                                                                   direction, e->d_ellg_ws, e->ellg_ws_stride);
+                const bool split = e->row_split > 1;
+                const int G = split ? e->split_groups * e->row_split : e->ellg_wgs;
+                auto shared = [&](auto launch) {  // what both forms are launched with
+                    return launch(dim3(G), dim3(KH_ELLG_THREADS), kh_ellg_lds_bytes(split), st, p, ells, (const int *)e->d_ell_off,
+                                  (const cplx *)e->d_ell_vals, pulses, in, store, out, direction, e->d_ellg_ws, e->ellg_ws_stride);
+                };
+                if (split) {
+                    // all S x groups workgroups wait for each other at every term: resident at once, as an update sweep's
+                    KH_HIP(hipMemsetAsync(e->d_split_counters, 0, e->split_counters_bytes, st));
+                    KhExchange ex = exchange_args(e, false);
+                    ex.G = G;
+                    rc = shared([&](auto... a) {
+                        return launch_persistent<kh_ellgs_sweep_store<KH_ELLG_THREADS>>(e, a..., ex, e->row_split, e->d_split_counters);
+                    });
+                } else {
+                    shared([](auto... a) { launch_plain<kh_ellg_sweep_store<KH_ELLG_THREADS>>(a...); });
+                }
                 break;
             }
             const int grid = pl.ell_stream ? grid_cus : (e->K < 4 * e->num_cus ? e->K : 4 * e->num_cus);
@@ -2394,27 +2396,27 @@ static int update_tilen(kh_engine *e, const KhSweepArgs &p, const KhUpdateArgs &
 // the padded-row form with its vectors in global memory (kh_ellg.h): a workgroup takes its objectives in turns, so the
 // grid is min(K, #CUs) or what kh_set_update_workgroups allows
 static int update_ellg(kh_engine *e, const KhSweepArgs &p, const KhUpdateArgs &u, const KhExchange &ex, hipStream_t st) {
-    if (e->row_split > 1) {  // kh_ellgs.h: every workgroup of every group takes part in the exchange
-        const int S = e->row_split, G = e->split_groups * S;
+    const int S = e->row_split;
+    const bool split = S > 1;  // the split form: every workgroup of every group takes part in the exchange
+    int G = split ? e->split_groups * S : e->plan.grid_update;
+    if (!split && e->reduced_G > 0 && e->reduced_G < G) G = e->reduced_G;
+    if (split) {
         KH_HIP(hipMemsetAsync(e->d_split_counters, 0, e->split_counters_bytes, st));
-        KhExchange exs = ex;
-        exs.G = G;
-        e->last_update_grid = G;
-        return with_bool(u.sigma != nullptr, [&](auto so) {
-            return launch_persistent<kh_ellgs_forward_update<KH_ELLGS_THREADS, decltype(so)::value>>(
-                e, dim3(G), dim3(KH_ELLGS_THREADS), kh_ellgs_lds_bytes(), st, p, (const KhEll *)e->d_ell_fw, (const int *)e->d_ell_off,
-                (const cplx *)e->d_ell_vals, u, exs, e->d_ellg_ws, e->ellg_ws_stride, S, e->d_split_counters);
-        });
     }
-    int G = e->plan.grid_update;
-    if (e->reduced_G > 0 && e->reduced_G < G) G = e->reduced_G;
     KhExchange exg = ex;
     exg.G = G;
     e->last_update_grid = G;
     return with_bool(u.sigma != nullptr, [&](auto so) {
-        return launch_persistent<kh_ellg_forward_update<KH_ELLG_THREADS, decltype(so)::value>>(
-            e, dim3(G), dim3(KH_ELLG_THREADS), kh_ellg_lds_bytes(), st, p, (const KhEll *)e->d_ell_fw, (const int *)e->d_ell_off,
-            (const cplx *)e->d_ell_vals, u, exg, e->d_ellg_ws, e->ellg_ws_stride);
+        constexpr bool SO = decltype(so)::value;
+        auto shared = [&](auto launch) {  // what both forms are launched with
+            return launch(e, dim3(G), dim3(KH_ELLG_THREADS), kh_ellg_lds_bytes(split), st, p, (const KhEll *)e->d_ell_fw,
+                          (const int *)e->d_ell_off, (const cplx *)e->d_ell_vals, u, exg, e->d_ellg_ws, e->ellg_ws_stride);
+        };
+        if (split)
+            return shared([&](auto... a) {
+                return launch_persistent<kh_ellgs_forward_update<KH_ELLG_THREADS, SO>>(a..., S, e->d_split_counters);
+            });
+        return shared([](auto... a) { return launch_persistent<kh_ellg_forward_update<KH_ELLG_THREADS, SO>>(a...); });
     });
 }
 
@@ -2723,7 +2725,7 @@ extern "C" int kh_ellsplit_rows(int32_t N, int32_t S, int32_t part, int32_t *fir
     return KH_OK;
 }
 
-// S workgroups per objective for both sweeps of a CSR engine in the global form (kh_ellgs.h); 1: the kernels of kh_ellg.h
+// S workgroups per objective for both sweeps of a CSR engine in the global form (kh_ellg.h's split form); 1: its plain form
 extern "C" int kh_set_row_split(kh_engine *e, int workgroups_per_objective) {
     if (e == nullptr) return kh_fail(KH_ERR_INVALID, "null engine");
     const int S = workgroups_per_objective;

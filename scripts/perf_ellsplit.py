@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""One sparse objective on S workgroups ("ellsplit/csr", kh_ellgs.h) against one workgroup per objective ("ellglobal/csr",
-kh_ellg.h: S = 1, the baseline) on spin chains beyond N = 4096 (dev tool, GPU only; writes profiles/ellsplit.txt).
+"""One sparse objective on S workgroups ("ellsplit/csr", kh_ellg.h's split form) against one workgroup per objective
+("ellglobal/csr", its plain form: S = 1, the baseline) on spin chains beyond N = 4096 (dev tool, GPU only; writes
+profiles/ellsplit.txt).
 
     python scripts/perf_ellsplit.py [nt] [output file]
 

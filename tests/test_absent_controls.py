@@ -212,7 +212,7 @@ for _name, _k in (('ens_middle', 150), ('ens_first', 0)):
     case(_name, lambda k=_k: _drop(_c5(300, 16, nt=6, distinct=False), [(k, 0)]), 'tile64/256',
          ['kh_q2_sweep_store', 'kh_tile_forward_update<2, 1, false, true>'], forbid=('kh_ens',))
 
-# ---- sparse operators (kh_ell.h, kh_ellg.h, kh_ellgs.h, the generic CSR kernels)
+# ---- sparse operators (kh_ell.h, kh_ellg.h in both forms, the generic CSR kernels)
 case('ell_lindblad', _lindblad5, 'ell/csr', ['kh_ell_sweep_store<512, 1, 8, false>', 'kh_ell_forward_update<512, 1, 8, false, false>'],
      so=['kh_ell_forward_update<512, 1, 8, true, false>'], fmt='csr')
 case('ell_banded', lambda: _drop_ends(_banded(40, 11, 9, 3)), 'ell/csr',

@@ -243,7 +243,7 @@ case('coop_c4_L2', lambda: _nsa(_shared(2), 'ladder'), 'coop16/mfma',
      ['kh_coop_forward_update<8, 4, false, false, false, true>', 'kh_coop_sweep_store<8, 4, false>'],
      so=['kh_coop_forward_update<8, 4, true, false, false, true>'], env={'KH_COOP_COLS': '4'}, ladder=True)
 
-# ---- sparse operators (kh_ell.h, kh_ellg.h, kh_ellgs.h, the generic CSR kernels): ``ladder`` on the banded problem
+# ---- sparse operators (kh_ell.h, kh_ellg.h in both forms, the generic CSR kernels): ``ladder`` on the banded problem
 # (forward rows 28 wide, backward rows 12: the 32-slot instantiation runs both pools) and ``liouv`` on the d = 5 Lindbladian
 case('ell_banded_ladder', _banded_ladder, 'ell/csr',
      ['kh_ell_sweep_store<512, 1, 32, false>', 'kh_ell_forward_update<512, 1, 32, false, false>'],

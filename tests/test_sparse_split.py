@@ -1,5 +1,5 @@
 """One sparse objective on several workgroups: the padded-row family's fourth form, ``"ellsplit/csr"``
-(krotov_amd/csrc/kh_ellgs.h: the global form with S workgroups per objective, a barrier among them per term).
+(krotov_amd/csrc/kh_ellg.h, SPLIT: the global form with S workgroups per objective, a barrier among them per term).
 
 1. forced (``KH_KERNEL=ellsplit``, ``KH_ELL_SPLIT=S``) at small N against the oracle, at the project's bounds:
    1e-12 in Hilbert space, 1e-11 in Liouville space -- the cases tests/test_sparse_large.py holds at those bounds on the
@@ -148,8 +148,8 @@ def _plain_sweeps(eng, spec, pulses, chi_T):
 @pytest.mark.no_oracle
 def test_plain_sweeps_do_not_depend_on_the_split(monkeypatch):
     """``banded_n600_e21``: the stored forward and backward trajectories for S = 2 and S = 4 are bitwise equal (the same
-    instantiation, the same per-row code: any difference is a stale or an early read); against S = 1 (the kernels of
-    kh_ellg.h: other code generation) they deviate by at most 1e-13.  The product count does not depend on S either."""
+    instantiation, the same per-row code: any difference is a stale or an early read); against S = 1 (the plain
+    instantiations: other code generation) they deviate by at most 1e-13.  The product count does not depend on S either."""
     import torch
 
     monkeypatch.setenv('KH_KERNEL', 'ellsplit')
