@@ -180,12 +180,13 @@ int kh_engine_create_lindblad(const kh_problem_lindblad *problem, kh_engine **ou
  * replica's results depend neither on B nor on where in the batch it sits.
  *   dt_replicas  host [B][nt-1] time steps of every replica, or NULL: problem->dt for all of them (problem->dt may be
  *                NULL when dt_replicas is given)
- * Limits: dense operators, N <= 16, K_r <= 8, 1 <= L <= 4, first-order update, one GPU (KH_ERR_UNSUPPORTED beyond;
+ * Limits: dense operators, N <= 16, K_r <= 8, 1 <= L <= 4, one GPU (KH_ERR_UNSUPPORTED beyond;
  * NULL or non-divisible arguments: KH_ERR_INVALID; both decided before the first HIP call).  The coefficient set of
  * the series (Taylor, real spectrum, defect) is chosen from ALL operators of the batch.
  * kh_forward_store / kh_backward_store / kh_forward_update keep their signatures and their state shapes at K total;
  * their pulse-like arguments are per replica (see there).  kh_tau, kh_chi_boundary and kh_expect are per objective and
- * work unchanged.  kh_set_second_order (non-NULL arguments), kh_set_update_workgroups (> 0), kh_set_row_split,
+ * work unchanged.  The second-order update takes one sigma row per replica: kh_set_second_order_replicas.
+ * kh_set_second_order (non-NULL arguments: its sigma_dev is ONE row), kh_set_update_workgroups (> 0), kh_set_row_split,
  * kh_p2p_create_window and kh_update_begin / _step / _step_dev / _end answer KH_ERR_UNSUPPORTED.
  * kh_last_stats counts products per objective, summed. */
 int kh_engine_create_replicas(const kh_problem *problem, int32_t replicas, const double *dt_replicas, kh_engine **out);
@@ -197,7 +198,9 @@ int kh_engine_create_replicas(const kh_problem *problem, int32_t replicas, const
 int kh_set_active_replicas(kh_engine *engine, const int32_t *active_host);
 
 /* Workgroups of the replica update kernel (64 K_r threads) that one compute unit holds at once, as built
- * (hipOccupancyMaxActiveBlocksPerMultiprocessor).  Batches up to that x the number of compute units run in one turn. */
+ * (hipOccupancyMaxActiveBlocksPerMultiprocessor) -- of the instantiation the next update sweep launches: the
+ * second-order one after kh_set_second_order_replicas.  Batches up to that x the number of compute units run in one
+ * turn. */
 int kh_replica_occupancy(kh_engine *engine, int32_t *workgroups_per_cu);
 
 /* Which kernel family the engine selected: "lindblad/matrix" (kh_engine_create_lindblad), "tile64q2/512", "tile64/512", "tile64/256", "tile64/stream" (more objectives
@@ -275,6 +278,16 @@ int kh_set_update_workgroups(kh_engine *engine, int32_t max_workgroups, int32_t 
  * Pass three NULLs to return to the first-order update. */
 int kh_set_second_order(kh_engine *engine, const kh_cdouble *fw_prev_dev,
                         kh_cdouble *fw_store_dev, const double *sigma_dev);
+
+/* The second-order update of a replica engine (kh_engine_create_replicas): as kh_set_second_order, with every replica
+ * under its own sigma(t).
+ *   fw_prev_dev  [K][nt][N] (K = B K_r) states under the guess pulses (iteration 0: kh_forward_store's states)
+ *   fw_store_dev [K][nt][N] OUT states under the optimized pulses; an inactive replica's slices keep what they held
+ *   sigma_dev    [B][nt-1] sigma_b(t) at replica b's own interval mid-points
+ * Three NULLs return the engine to the first-order update; NULL and non-NULL mixed, or fw_store_dev == fw_prev_dev:
+ * KH_ERR_INVALID.  KH_ERR_UNSUPPORTED on any engine that is not a replica engine. */
+int kh_set_second_order_replicas(kh_engine *engine, const kh_cdouble *fw_prev_dev, kh_cdouble *fw_store_dev,
+                                 const double *sigma_dev);
 
 /* The same sweep cut at the cross-objective sum, for objectives sharded over
  * several GPUs: the caller all-reduces `partial` (L doubles, Im parts) across

@@ -6,8 +6,9 @@ controls, grid length, kind) run on ONE replica engine (``kh_engine_create_repli
 ``"replica16/wave"``): per Krotov iteration of the whole batch one ``kh_tau``, one ``kh_chi_boundary``, one backward
 sweep and one update sweep, where a Python loop over ``optimize_pulses`` creates B engines and pays three launches per
 replica and iteration.  Replicas stop on their own (``check_convergence``, ``iter_stop``): a finished one is frozen
-through the engine's active mask.  Whatever does not fit one batch runs the replicas one after another through
-``optimize_pulses``, with the same results.
+through the engine's active mask.  With ``sigma`` (one ``Sigma`` per problem) the update sweep is the second-order
+one, every replica under its own sigma(t) (``kh_set_second_order_replicas``).  Whatever does not fit one batch runs
+the replicas one after another through ``optimize_pulses``, with the same results.
 """
 import copy
 import logging
@@ -42,7 +43,7 @@ def _free_device_bytes():
 class _Replica:
     """One problem of the batch: what ``optimize_pulses`` keeps in local variables, per replica."""
 
-    def __init__(self, problem, propagator, chi_constructor, iter_stop, store_all_pulses, continue_from):
+    def __init__(self, problem, propagator, chi_constructor, iter_stop, store_all_pulses, continue_from, sigma=None):
         self.objectives = problem['objectives']
         self.pulse_options = problem['pulse_options']
         self.tlist = problem['tlist']
@@ -65,11 +66,14 @@ class _Replica:
         self.static_args = dict(
             objectives=self.objectives, adjoint_objectives=self.adjoint_objectives, lambda_vals=self.lambda_vals,
             shape_arrays=self.shape_arrays, tlist=self.tlist, propagator=propagator, chi_constructor=chi_constructor,
-            mu=derivative_wrt_pulse, sigma=None, iter_start=0, iter_stop=iter_stop,
+            mu=derivative_wrt_pulse, sigma=sigma, iter_start=0, iter_stop=iter_stop,
         )
+        self.sigma = sigma
+        self.midpoints = None  # (second order: the interval mid-points sigma is evaluated at)
         self.optimized_pulses = copy.deepcopy(self.guess_pulses)
         self.tau_vals = None
         self.fw_states_T = None
+        self.forward_states0 = None  # second order: this replica's view of the trajectory under its guess pulses
         self.active = True
         self.iteration = 0
 
@@ -111,7 +115,7 @@ class _ReplicaBackend:
     """The B replicas of one (sub-)batch resident on one replica engine; every buffer a sweep writes is persistent, so
     that a frozen replica's slices keep their last values."""
 
-    def __init__(self, reps, propagator):
+    def __init__(self, reps, propagator, second_order=False):
         import torch
 
         from .engine import HipKrotovEngine
@@ -146,6 +150,15 @@ class _ReplicaBackend:
         self.chi_store = t.zeros((self.K, self.nt, self.N), dtype=c128, device=dev)
         self.opt = t.zeros((self.B, self.L, self.nt - 1), dtype=f64, device=dev)
         self.g_a = t.zeros((self.B, self.L), dtype=f64, device=dev)
+        # second order: phi(t_n) of the last / the running iteration, swapped once per pass for the whole batch (a
+        # frozen replica's slices of either are never read again)
+        self.second_order = second_order
+        self.fw_prev = self.fw_next = None
+        if second_order:
+            self.fw_prev = t.zeros((self.K, self.nt, self.N), dtype=c128, device=dev)
+            self.fw_next = t.zeros((self.K, self.nt, self.N), dtype=c128, device=dev)
+            self.sigma_host = np.zeros((self.B, self.nt - 1))
+        self.last_chi = None
         self._uploads = {}
         self._mask = None
 
@@ -168,8 +181,30 @@ class _ReplicaBackend:
             self._mask = mask
 
     def initial_forward(self):
-        self.engine.forward(self._pulses('pulses', 'guess_pulses'), self.init, out=self.psi_T)
+        pulses = self._pulses('pulses', 'guess_pulses')
+        if self.second_order:  # (the trajectory under the guess: forward_states0 of iteration 1)
+            self.engine.forward(pulses, self.init, store=True, out=(self.psi_T, self.fw_prev))
+        else:
+            self.engine.forward(pulses, self.init, out=self.psi_T)
         return self.psi_T.cpu().numpy()
+
+    def trajectories(self, store, b, likes, final):
+        """Replica b's slices of a (K, nt, N) store, for ``info_hook`` and ``sigma.refresh`` (views: they follow the
+        buffer through ``advance_second_order``).  ``final``: the states at T of all objectives on the host -- what
+        ``numerical_estimate_A`` reads, B K_r times per pass, without a device copy each (a copy of the rows: the
+        sweeps write ``psi_T`` in place)."""
+        rows = slice(b * self.Kr, (b + 1) * self.Kr)
+        return _opt._DeviceTrajectories(store[rows], likes, final=np.array(final[rows]))
+
+    def chi_host(self):
+        """Normalised chi_k(T) and their norms of the last iteration, (K, N) and (K,), on the host."""
+        chi, norms = self.last_chi
+        return chi.cpu().numpy(), norms.cpu().numpy()
+
+    def advance_second_order(self):
+        """The trajectory of the finished iteration becomes ``forward_states0`` of the next one (optimize.py:577): one
+        swap for the whole batch."""
+        self.fw_prev, self.fw_next = self.fw_next, self.fw_prev
 
     def tau_vals(self):
         """(B, K_r) on the host from one kh_tau over all objectives, or None without state targets."""
@@ -191,6 +226,17 @@ class _ReplicaBackend:
         else:
             chi_loc = eng.dev(chi_T, t.complex128)
             norms_loc = eng.dev(np.asarray(chi_norms, dtype=np.float64), t.float64)
+        if self.second_order:
+            # sigma_b at replica b's own interval mid-points (optimize.py:451-452), the active replicas, one upload
+            # (the mid-points once per replica, as an array: the same values as the scalar expression, element by element)
+            for b, r in enumerate(self.reps):
+                if r.active:
+                    if r.midpoints is None:
+                        tl = np.asarray(r.tlist)
+                        r.midpoints = tl[:-1] + 0.5 * (tl[1:] - tl[:-1])
+                    self.sigma_host[b] = [r.sigma(t) for t in r.midpoints]
+            eng.set_second_order_replicas(self.fw_prev, self.fw_next, self.sigma_host)
+        self.last_chi = (chi_loc, norms_loc)
         self.set_active()
         eng.backward(chi_loc, guess, out=self.chi_store)
         # (the update sweep reads init and the boundary states' buffer is its own: psi_T may be written in place)
@@ -203,7 +249,8 @@ class _ReplicaBackend:
 
 def _run_batch(reps, propagator, chi_constructor, check_convergence, info_hook, store_all_pulses):
     logger = logging.getLogger('krotov')
-    backend = _ReplicaBackend(reps, propagator)
+    second_order = reps[0].sigma is not None
+    backend = _ReplicaBackend(reps, propagator, second_order=second_order)
     Kr = backend.Kr
 
     def states_of(psi_host, b):
@@ -220,10 +267,13 @@ def _run_batch(reps, propagator, chi_constructor, check_convergence, info_hook, 
     for b, r in enumerate(reps):
         r.fw_states_T = states_of(psi_host, b)
         r.tau_vals = taus_of(tau, b)
+        if second_order:  # (in iteration 0 the states under "optimized" and guess pulses coincide)
+            r.forward_states0 = backend.trajectories(backend.fw_prev, b, r.likes, psi_host)
         info = None
         if info_hook is not None:
             info = info_hook(
-                backward_states=None, forward_states=None, forward_states0=None, guess_pulses=r.guess_pulses,
+                backward_states=None, forward_states=r.forward_states0, forward_states0=r.forward_states0,
+                guess_pulses=r.guess_pulses,
                 optimized_pulses=r.optimized_pulses, g_a_integrals=r.g_a_integrals, fw_states_T=r.fw_states_T,
                 tau_vals=r.tau_vals, start_time=tic, stop_time=toc, iteration=0, info_vals=[], shared_data={},
                 **r.static_args,
@@ -251,6 +301,7 @@ def _run_batch(reps, propagator, chi_constructor, check_convergence, info_hook, 
         if r.iteration + 1 > r.range_stop:  # (an empty loop: optimize.py's for-else)
             res.message = "Reached %d iterations" % max(r.iter_start, r.range_stop)
             r.finish()
+            r.forward_states0 = None
 
     # ---- main loop (optimize.py:392-581): one iteration of every active replica per pass
     while any(r.active for r in reps):
@@ -261,6 +312,7 @@ def _run_batch(reps, propagator, chi_constructor, check_convergence, info_hook, 
             if any(c is None for c in coefs):
                 coefs = None
         chi_T = chi_norms = chi_coef = None
+        host_chis = {}  # (second order, a user's chi_constructor: what sigma.refresh gets, per replica)
         if coefs is not None:
             chi_coef = (np.concatenate([c[0] for c in coefs]), np.concatenate([c[1] for c in coefs]))
         else:  # a user's chi_constructor: on the host, per replica, as optimize_pulses does
@@ -277,9 +329,11 @@ def _run_batch(reps, propagator, chi_constructor, check_convergence, info_hook, 
                     raise ValueError("chi_constructor returned states that do not match the state dimension")
                 chi_T[b * Kr:(b + 1) * Kr] = np.array(vecs)
                 chi_norms[b * Kr:(b + 1) * Kr] = norms
+                host_chis[b] = ([chi / nrm for chi, nrm in zip(chis, norms)], norms)
         opt_host, psi_host, g_a = backend.iterate(chi_T, chi_norms, chi_coef)
         tau = backend.tau_vals()
         toc = time.time()
+        chi_fetched = None
 
         for b, r in enumerate(reps):
             if not r.active:
@@ -291,11 +345,15 @@ def _run_batch(reps, propagator, chi_constructor, check_convergence, info_hook, 
             r.g_a_integrals[:] = g_a[b]
             r.tau_vals = taus_of(tau, b)
             res = r.result
+            forward_states = None
+            if second_order:
+                forward_states = backend.trajectories(backend.fw_next, b, r.likes, psi_host)
             info = None
             if info_hook is not None:
                 info = info_hook(
                     backward_states=_opt._DeviceTrajectories(backend.chi_store[b * Kr:(b + 1) * Kr], r.likes),
-                    forward_states=None, forward_states0=None, fw_states_T=r.fw_states_T, guess_pulses=r.guess_pulses,
+                    forward_states=forward_states, forward_states0=r.forward_states0, fw_states_T=r.fw_states_T,
+                    guess_pulses=r.guess_pulses,
                     optimized_pulses=r.optimized_pulses, g_a_integrals=r.g_a_integrals, tau_vals=r.tau_vals,
                     start_time=tic, stop_time=toc, info_vals=res.info_vals, shared_data={}, iteration=r.iteration,
                     **r.static_args,
@@ -326,11 +384,30 @@ def _run_batch(reps, propagator, chi_constructor, check_convergence, info_hook, 
                 r.finish()
             else:
                 r.guess_pulses = r.optimized_pulses
+                if second_order:  # (optimize.py:566-577, for the replicas that go on)
+                    if b in host_chis:
+                        chi_states, norms = host_chis[b]
+                    else:  # co-states formed on the device, in the caller's state type
+                        if chi_fetched is None:
+                            chi_fetched = backend.chi_host()
+                        rows = slice(b * Kr, (b + 1) * Kr)
+                        chi_states, norms = _opt._LazyStates(chi_fetched[0][rows], r.likes), chi_fetched[1][rows]
+                    r.sigma.refresh(
+                        forward_states=forward_states, forward_states0=r.forward_states0, chi_states=chi_states,
+                        chi_norms=norms, optimized_pulses=r.optimized_pulses, guess_pulses=r.guess_pulses,
+                        objectives=r.objectives, result=res,
+                    )
+                    r.forward_states0 = forward_states
+            if not r.active:
+                r.forward_states0 = None  # (a finished replica holds no device reference)
+        if second_order:
+            backend.advance_second_order()
     backend.engine.close()
 
 
 def optimize_pulses_batch(problems, *, propagator, chi_constructor, iter_stop=5000, check_convergence=None,
-                          info_hook=None, modify_params_after_iter=None, store_all_pulses=False, continue_from=None):
+                          info_hook=None, modify_params_after_iter=None, store_all_pulses=False, continue_from=None,
+                          sigma=None):
     """Optimise B independent problems (*replicas*) as one batch on the device.
 
     ``problems``: a sequence of B mappings with the keys ``objectives``, ``pulse_options`` and ``tlist`` -- the first
@@ -347,16 +424,25 @@ def optimize_pulses_batch(problems, *, propagator, chi_constructor, iter_stop=50
     :class:`~krotov_amd.propagators.HipExpm` -- run on one replica engine (``"replica16/wave"``): one ``kh_tau``, one
     ``kh_chi_boundary``, one backward and one update sweep per iteration of the whole batch.  ``check_convergence`` and
     each replica's ``iter_stop`` decide per replica; a finished replica is frozen (the engine's active mask) and its
-    ``Result`` is not touched again; the batch ends when no replica is active.  A batch whose co-state store
-    (B K_r nt N 16 bytes) exceeds a quarter of the free device memory is split into consecutive sub-batches of equal
-    size.  Everything else runs the replicas one after another through ``optimize_pulses`` (logged once as
-    ``"optimize_pulses_batch: sequential (<reason>)"`` on the ``krotov`` logger)."""
+    ``Result`` is not touched again; the batch ends when no replica is active.  ``sigma``: None, or a sequence of B
+    :class:`~krotov_amd.second_order.Sigma` objects -- the second-order update, replica b under ``sigma[b]``
+    (``static_args['sigma']`` of its hooks), which is refreshed after every iteration that replica goes on from;
+    ``info_hook`` then gets ``forward_states`` / ``forward_states0`` of its replica.  A batch whose co-state store
+    (B K_r nt N 16 bytes; with ``sigma`` three such stores: chi and the two forward trajectories) exceeds a quarter of
+    the free device memory is split into consecutive sub-batches of equal size.  Everything else runs the replicas one
+    after another through ``optimize_pulses`` (logged once as ``"optimize_pulses_batch: sequential (<reason>)"`` on the
+    ``krotov`` logger)."""
     logger = logging.getLogger('krotov')
     problems = [dict(p) for p in problems]
     B = len(problems)
     if continue_from is not None and len(continue_from) != B:
         raise ValueError("continue_from must be None or a list of one Result per problem")
     previous = [None] * B if continue_from is None else list(continue_from)
+    if sigma is not None:
+        sigma = list(sigma)
+        if len(sigma) != B or any(s is None for s in sigma):
+            raise ValueError("sigma must be None or a sequence of one Sigma per problem")
+    sigmas = [None] * B if sigma is None else sigma
     if B == 0:
         return []
 
@@ -365,13 +451,14 @@ def optimize_pulses_batch(problems, *, propagator, chi_constructor, iter_stop=50
         return [_opt.optimize_pulses(
             p['objectives'], p['pulse_options'], p['tlist'], propagator=propagator, chi_constructor=chi_constructor,
             iter_stop=iter_stop, check_convergence=check_convergence, info_hook=info_hook,
-            modify_params_after_iter=modify_params_after_iter, store_all_pulses=store_all_pulses, continue_from=prev)
-            for p, prev in zip(problems, previous)]
+            modify_params_after_iter=modify_params_after_iter, store_all_pulses=store_all_pulses, continue_from=prev,
+            sigma=sig)
+            for p, prev, sig in zip(problems, previous, sigmas)]
 
     if isinstance(propagator, list) or not (propagator is expm or isinstance(propagator, HipExpm)):
         return sequential("the propagator is not expm / HipExpm")
-    reps = [_Replica(p, propagator, chi_constructor, iter_stop, store_all_pulses, prev)
-            for p, prev in zip(problems, previous)]
+    reps = [_Replica(p, propagator, chi_constructor, iter_stop, store_all_pulses, prev, sigma=sig)
+            for p, prev, sig in zip(problems, previous, sigmas)]
     reason = _batch_obstacle(problems, reps, propagator)
     if reason is not None:
         return sequential(reason)
@@ -379,11 +466,14 @@ def optimize_pulses_batch(problems, *, propagator, chi_constructor, iter_stop=50
         info_hook = modify_params_after_iter if info_hook is None else chain(modify_params_after_iter, info_hook)
     logger.info("optimize_pulses_batch: %d problems of %d objectives in one batch", B, len(reps[0].objectives))
 
-    # the co-state store of the whole batch against a quarter of the free device memory
+    # the co-state store of the whole batch (second order: and the two forward trajectories) against a quarter of the
+    # free device memory
     size = B
     free = _free_device_bytes()
     if free is not None:
         per_replica = len(reps[0].objectives) * len(reps[0].tlist) * layout_of(reps[0].objectives, propagator).stride * 16
+        if sigma is not None:
+            per_replica *= 3  # chi, phi_prev, phi_next
         while size > 1 and (B % size != 0 or size * per_replica > free // 4):
             size -= 1
         if size < B:

@@ -20,6 +20,9 @@
 //
 // `active` ([B], or NULL: all): a workgroup whose replica is inactive returns before its first barrier and before any
 // store; every slice of every output buffer that belongs to that replica keeps what it held.
+//
+// Second order (kh_rep_forward_update_so): sigma is [B][nt-1], one row per replica; the forward trajectories are [K][nt][N]
+// like the co-state store.  See the update kernel below.
 #pragma once
 
 #include "kh_mini.h"
@@ -200,14 +203,21 @@ kh_rep_sweep_store(KhSweepArgs p, const cplx *const *__restrict__ sq, const doub
 
 // ---------------------------------------------------------------------------
 // forward sweep with sequential pulse update (optimize.py:444-508): ONE workgroup per replica, grid B, block 64 K_r,
-// wave w = objective b K_r + w.  First order.  init / psi_T: [K][N] (read and written directly: an inactive replica's
-// rows are never touched); u.guess / u.shape / u.opt: [B][L][nt-1]; u.lambda / u.g_a: [B][L].
+// wave w = objective b K_r + w.  init / psi_T: [K][N] (read and written directly: an inactive replica's rows are never
+// touched); u.guess / u.shape / u.opt: [B][L][nt-1]; u.lambda / u.g_a: [B][L].
+//
+// SO (second order, kh_set_second_order_replicas): u.fw_prev / u.fw_store are [K][nt][N], u.sigma is [B][nt-1] -- every
+// replica its own row.  The bra of interval n is chi + sigma_n / (2 ||chi||) (phi - phi_prev) (optimize.py:468-469;
+// kh_mini_forward_update<true>'s two fused multiply-adds, once per interval: all L controls share it), phi_prev's row
+// and sigma_n come one interval ahead with chi's, and fw_store[k][n] takes the state before interval n is propagated,
+// fw_store[k][nt-1] the final one.  One body serves both orders; the two kernels below differ in SO only, and the
+// first-order one keeps its name (kh_debug_launched) and its code.
 // ---------------------------------------------------------------------------
-template <int LT>
-__global__ void __launch_bounds__(64 * KH_MINI_MAXK)
-kh_rep_forward_update(KhSweepArgs p, const cplx *const *__restrict__ sq, KhUpdateArgs u, const cplx *__restrict__ init,
-                      cplx *__restrict__ psi_T, int Kr, const int *__restrict__ active) {
-    __shared__ KhRepLds<LT> s;
+template <int LT, bool SO>
+__device__ __forceinline__ void kh_rep_update_body(const KhSweepArgs &p, const cplx *const *__restrict__ sq,
+                                                   const KhUpdateArgs &u, const cplx *__restrict__ init,
+                                                   cplx *__restrict__ psi_T, int Kr, const int *__restrict__ active,
+                                                   KhRepLds<LT> &s) {
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, r = lane >> 2, b = blockIdx.x, k = b * Kr + w;
     if (active != nullptr && active[b] == 0) return;  // (uniform over the workgroup: before the first barrier)
     const bool writer = (lane & 3) == 0;
@@ -223,18 +233,31 @@ kh_rep_forward_update(KhSweepArgs p, const cplx *const *__restrict__ sq, KhUpdat
     __syncthreads();  // (the tables)
     double matvecs = 0.0;
 
-    // chi(t_n) of this lane's row, fetched one interval ahead
-    cplx chi = c_make(0.0, 0.0);
+    // chi(t_n) (and, second order, phi_prev(t_n), sigma_n of this replica) of this lane's row, fetched one interval ahead
+    cplx chi = c_make(0.0, 0.0), prev = c_make(0.0, 0.0);
+    double sig = 0.0;
+    const double *sigma_b = SO ? u.sigma + (size_t)b * (nt - 1) : nullptr;
     auto load_bra = [&](int n) {
-        if (writer && r < N) chi = u.chi_store[((size_t)k * nt + n) * N + r];
+        if (writer && r < N) {
+            chi = u.chi_store[((size_t)k * nt + n) * N + r];
+            if constexpr (SO) prev = u.fw_prev[((size_t)k * nt + n) * N + r];
+        }
+        if constexpr (SO) sig = sigma_b[n];
     };
-    // this objective's  ||chi|| Im(mu <chi(t_n)|H_l phi>)  -> part[n & 1][l][w]
+    // this objective's  ||chi|| Im(mu <bra(t_n)|H_l phi>)  -> part[n & 1][l][w]
     auto partial = [&](int n) {
+        cplx bra = chi;
+        if constexpr (SO) {  // bra = chi + sigma / (2 ||chi||) (phi - phi_prev)  (optimize.py:468-469)
+            if (writer && r < N) {
+                const double hs = 0.5 * sig / chi_norm;
+                bra = c_make(fma(hs, state.x - prev.x, chi.x), fma(hs, state.y - prev.y, chi.y));
+            }
+        }
 #pragma unroll
         for (int l = 0; l < LT; ++l) {
             const cplx y = kh_mini_matvec(t.h[1 + l], state, lane);
             cplx ov = c_make(0.0, 0.0);
-            c_fma_conj(ov, chi, y);
+            c_fma_conj(ov, bra, y);
             const double v = sum64(u.mu_re * ov.y + u.mu_im * ov.x);
             if (lane == 0) s.sum(n & 1, l, w) = chi_norm * v;
         }
@@ -283,15 +306,38 @@ kh_rep_forward_update(KhSweepArgs p, const cplx *const *__restrict__ sq, KhUpdat
             g_a_loc[l] += stepw * (d1 * d1) * dt;
             if (tid == 0) opt_b[(size_t)l * (nt - 1) + n] = eps[l];
         }
+        if constexpr (SO) {  // (behind the next interval's loads: kh_mini.h, kh_mini_sweep_store, on the shared counter)
+            if (writer && r < N) u.fw_store[((size_t)k * nt + n) * N + r] = state;
+        }
         // ---- propagate over interval n with the updated pulse (optimize.py:479-491) ----
         matvecs += kh_rep_interval<LT>(p, t, s, ser, eps, dt, state, lane);
         if (n + 1 < nt - 1) partial(n + 1);
         __syncthreads();  // everybody's partial sums of the next interval are in LDS
     }
-    if (writer && r < N) psi_T[(size_t)k * N + r] = state;
+    if (writer && r < N) {
+        psi_T[(size_t)k * N + r] = state;
+        if constexpr (SO) u.fw_store[((size_t)k * nt + nt - 1) * N + r] = state;
+    }
     if (tid == 0) {
 #pragma unroll
         for (int l = 0; l < LT; ++l) u.g_a[(size_t)b * LT + l] = g_a_loc[l];
     }
     if (lane == 0 && p.stats != nullptr) atomicAdd(p.stats, matvecs);
+}
+
+template <int LT>
+__global__ void __launch_bounds__(64 * KH_MINI_MAXK)
+kh_rep_forward_update(KhSweepArgs p, const cplx *const *__restrict__ sq, KhUpdateArgs u, const cplx *__restrict__ init,
+                      cplx *__restrict__ psi_T, int Kr, const int *__restrict__ active) {
+    __shared__ KhRepLds<LT> s;
+    kh_rep_update_body<LT, false>(p, sq, u, init, psi_T, Kr, active, s);
+}
+
+template <int LT>
+__global__ void __launch_bounds__(64 * KH_MINI_MAXK)
+kh_rep_forward_update_so(KhSweepArgs p, const cplx *const *__restrict__ sq, KhUpdateArgs u,
+                         const cplx *__restrict__ init, cplx *__restrict__ psi_T, int Kr,
+                         const int *__restrict__ active) {
+    __shared__ KhRepLds<LT> s;
+    kh_rep_update_body<LT, true>(p, sq, u, init, psi_T, Kr, active, s);
 }

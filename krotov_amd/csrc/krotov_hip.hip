@@ -1871,10 +1871,17 @@ extern "C" int kh_set_active_replicas(kh_engine *e, const int32_t *active_host) 
 extern "C" int kh_replica_occupancy(kh_engine *e, int32_t *workgroups_per_cu) {
     if (e == nullptr || workgroups_per_cu == nullptr) return kh_fail(KH_ERR_INVALID, "null argument");
     if (e->replicas < 1) return kh_fail(KH_ERR_UNSUPPORTED, "not a replica engine");
-    const void *fn = e->L == 1   ? (const void *)kh_rep_forward_update<1>
-                     : e->L == 2 ? (const void *)kh_rep_forward_update<2>
-                     : e->L == 3 ? (const void *)kh_rep_forward_update<3>
-                                 : (const void *)kh_rep_forward_update<4>;
+    const void *fn = nullptr;  // (the instantiation the next update sweep launches: kh_set_second_order_replicas)
+    if (e->so_sigma != nullptr)
+        fn = e->L == 1   ? (const void *)kh_rep_forward_update_so<1>
+             : e->L == 2 ? (const void *)kh_rep_forward_update_so<2>
+             : e->L == 3 ? (const void *)kh_rep_forward_update_so<3>
+                         : (const void *)kh_rep_forward_update_so<4>;
+    else
+        fn = e->L == 1   ? (const void *)kh_rep_forward_update<1>
+             : e->L == 2 ? (const void *)kh_rep_forward_update<2>
+             : e->L == 3 ? (const void *)kh_rep_forward_update<3>
+                         : (const void *)kh_rep_forward_update<4>;
     int per_cu = 0;
     KH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64 * e->Kr, 0));
     *workgroups_per_cu = per_cu;
@@ -2619,8 +2626,13 @@ extern "C" int kh_forward_update(kh_engine *e, const kh_cdouble *chi_store_dev, 
         const KhUpdateArgs u = update_args(e, chi_store_dev, chi_norms_dev, guess_dev, shape_dev, lambda_dev, opt_dev, g_a_dev);
         const KhSweepArgs p = sweep_args(e, false);
         KH_TRY(with_tile_L(e->L, [&](auto lt) {
-            launch_plain<kh_rep_forward_update<decltype(lt)::value>>(dim3(e->replicas), dim3(64 * e->Kr), 0, st, p, e->d_sq_fw, u,
-                                                                     (const cplx *)init_dev, (cplx *)psi_T_dev, e->Kr, e->active_mask());
+            constexpr int LT = decltype(lt)::value;
+            if (u.sigma != nullptr)  // second order: kh_set_second_order_replicas
+                launch_plain<kh_rep_forward_update_so<LT>>(dim3(e->replicas), dim3(64 * e->Kr), 0, st, p, e->d_sq_fw, u,
+                                                           (const cplx *)init_dev, (cplx *)psi_T_dev, e->Kr, e->active_mask());
+            else
+                launch_plain<kh_rep_forward_update<LT>>(dim3(e->replicas), dim3(64 * e->Kr), 0, st, p, e->d_sq_fw, u,
+                                                        (const cplx *)init_dev, (cplx *)psi_T_dev, e->Kr, e->active_mask());
             return KH_OK;
         }));
         KH_HIP(hipGetLastError());
@@ -2773,6 +2785,22 @@ extern "C" int kh_set_second_order(kh_engine *e, const kh_cdouble *fw_prev_dev, 
         return kh_fail(KH_ERR_INVALID, "fw_prev, fw_store and sigma must be given together (or all NULL)");
     if (e->lind && given != 0) return kh_fail(KH_ERR_UNSUPPORTED, "Lindblad-form engines (kh_engine_create_lindblad) run the first-order update only");
     if (e->replicas > 0 && given != 0) return kh_fail(KH_ERR_UNSUPPORTED, "replica engines (kh_engine_create_replicas) run the first-order update only");
+    if (fw_prev_dev != nullptr && (const void *)fw_prev_dev == (const void *)fw_store_dev)
+        return kh_fail(KH_ERR_INVALID, "fw_store must not alias fw_prev");
+    e->so_fw_prev = (const cplx *)fw_prev_dev;
+    e->so_fw_store = (cplx *)fw_store_dev;
+    e->so_sigma = sigma_dev;
+    return KH_OK;
+}
+
+// replica engines: the same switch with one sigma row per replica ([B][nt-1]; kh_replica.h, kh_rep_forward_update_so)
+extern "C" int kh_set_second_order_replicas(kh_engine *e, const kh_cdouble *fw_prev_dev, kh_cdouble *fw_store_dev,
+                                            const double *sigma_dev) {
+    if (e == nullptr) return kh_fail(KH_ERR_INVALID, "null engine");
+    if (e->replicas < 1) return kh_fail(KH_ERR_UNSUPPORTED, "only replica engines (kh_engine_create_replicas) take one sigma row per replica; this one runs %s (kh_set_second_order)", kh_engine_kernel(e));
+    const int given = (fw_prev_dev != nullptr) + (fw_store_dev != nullptr) + (sigma_dev != nullptr);
+    if (given != 0 && given != 3)
+        return kh_fail(KH_ERR_INVALID, "fw_prev, fw_store and sigma must be given together (or all NULL)");
     if (fw_prev_dev != nullptr && (const void *)fw_prev_dev == (const void *)fw_store_dev)
         return kh_fail(KH_ERR_INVALID, "fw_store must not alias fw_prev");
     e->so_fw_prev = (const cplx *)fw_prev_dev;

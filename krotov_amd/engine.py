@@ -484,6 +484,28 @@ class HipKrotovEngine:
         _lib.check(self._lib.kh_set_second_order(
             self._handle, fw_prev.data_ptr(), fw_store.data_ptr(), sig.data_ptr()))
 
+    def set_second_order_replicas(self, fw_prev=None, fw_store=None, sigma_vals=None):
+        """Replica engines: switch the following update sweeps to the second-order update with one sigma row per
+        replica (``fw_prev``, ``fw_store``: (K, nt, N) device tensors; ``sigma_vals``: (B, nt-1), sigma_b at replica
+        b's interval mid-points), or back to first order (no arguments).  ``kh_set_second_order_replicas``;
+        ``KrotovHipError`` (``KH_ERR_UNSUPPORTED``) on any other engine."""
+        if fw_prev is None and fw_store is None and sigma_vals is None:
+            _lib.check(self._lib.kh_set_second_order_replicas(self._handle, None, None, None))
+            self._so = None
+            return
+        if not self.replicas:  # (the library's own answer, before any shape is looked at)
+            _lib.check(self._lib.kh_set_second_order_replicas(self._handle, None, None, None))
+        if fw_prev is None or fw_store is None or sigma_vals is None:
+            raise ValueError("fw_prev, fw_store and sigma_vals must be given together (or none of them)")
+        fw_prev = self._c(fw_prev, (self.K, self.nt, self.N))
+        if (not isinstance(fw_store, torch.Tensor) or tuple(fw_store.shape) != (self.K, self.nt, self.N)
+                or fw_store.dtype != torch.complex128 or fw_store.device != self.device or not fw_store.is_contiguous()):
+            raise ValueError("fw_store must be a contiguous (K, nt, N) complex128 device tensor")
+        sig = self._f(sigma_vals, (self.replicas, self.nt - 1))
+        _lib.check(self._lib.kh_set_second_order_replicas(
+            self._handle, fw_prev.data_ptr(), fw_store.data_ptr(), sig.data_ptr()))
+        self._so = (fw_prev, fw_store, sig)  # keep the tensors alive while the engine points at them
+
     def set_update_workgroups(self, max_workgroups=0):
         """Run the following single-launch update sweeps on at most ``max_workgroups`` workgroups (0: the engine's own
         choice again); returns the grid the next sweep will use (``kh_set_update_workgroups``).  Raises

@@ -51,6 +51,7 @@ int main() {
     ops[3] = nullptr;  // objective 1 has no drift
     expect("no drift", kh_engine_create_replicas(&p, 2, nullptr, &e), KH_ERR_INVALID);
     expect("mask on no engine", kh_set_active_replicas(nullptr, nullptr), KH_ERR_INVALID);
+    expect("second order on no engine", kh_set_second_order_replicas(nullptr, nullptr, nullptr, nullptr), KH_ERR_INVALID);
     std::printf(failures ? "%d check(s) failed\n" : "all argument checks passed\n", failures);
     return failures ? 1 : 0;
 }
