@@ -289,6 +289,37 @@ int kh_set_second_order(kh_engine *engine, const kh_cdouble *fw_prev_dev,
 int kh_set_second_order_replicas(kh_engine *engine, const kh_cdouble *fw_prev_dev, kh_cdouble *fw_store_dev,
                                  const double *sigma_dev);
 
+/* Pulse parametrizations (bounded controls): eps_l(t) = f_l(u_l(t)) with an unconstrained u_l, and Krotov's update
+ * applied to u_l.  At interval n, with D_l the update sum of today (second order: with its sigma term),
+ *   D'      = dfdu[l][n] * D_l                       dfdu = f_l'(u_guess): the derivative at the GUESS
+ *   u_new   = u_guess[l][n] + (S_l[n] / lambda_l) D'
+ *   g_a_l  += (S_l[n] / lambda_l) D'^2 dt            the running cost in u
+ *   eps_new = f_l(u_new)                             what the interval is propagated with
+ * A control of kind KH_PAR_NONE is f = identity: the caller passes u = eps and dfdu = 1 for it. */
+enum kh_par_kind {
+    KH_PAR_NONE = 0,   /* eps = u */
+    KH_PAR_LINEAR = 1, /* eps = a u + b */
+    KH_PAR_SQUARE = 2, /* eps = u^2 */
+    KH_PAR_TANHSQ = 3, /* eps = a tanh^2 u            a = eps_max */
+    KH_PAR_TANH = 4    /* eps = a tanh u + b          a = (eps_max - eps_min) / 2, b = (eps_max + eps_min) / 2 */
+};
+
+/* While set, the update sweeps (kh_forward_update, kh_update_begin / _step / _step_dev / _end) read u_guess_dev in
+ * place of their guess argument, write u_new to u_opt_dev and eps_new to their opt argument.
+ *   kind, a, b   [L] host arrays (copied); kind == NULL: parametrizations off, the other arguments are ignored
+ *   u_guess_dev  [L][nt-1] u under the guess pulses
+ *   dfdu_dev     [L][nt-1] f_l'(u_guess)
+ *   u_opt_dev    [L][nt-1] OUT; must not alias u_guess_dev
+ * The device pointers must stay valid while the parametrization is set.  Routes: the whole sweep of a register-tile
+ * engine (N <= 64, 1..4 controls, its K > 1 workgroups resident) runs kh_tile_forward_update_par; everything else --
+ * the other families, the per-interval calls, a grid reduced with kh_set_update_workgroups (any grid >= 1 while
+ * parametrized; dropped again with the parametrization) -- runs kh_gen_forward_update_par on min(K, compute units)
+ * workgroups.  The plain sweeps keep the engine's own family.  KH_ERR_UNSUPPORTED for replica and Lindblad-form
+ * engines, sharded engines (kh_p2p_create_window), a row split above 1 and N beyond the generic kernels' LDS;
+ * KH_ERR_INVALID for an unknown kind. */
+int kh_set_parametrization(kh_engine *engine, const int32_t *kind, const double *a, const double *b,
+                           const double *u_guess_dev, const double *dfdu_dev, double *u_opt_dev);
+
 /* The same sweep cut at the cross-objective sum, for objectives sharded over
  * several GPUs: the caller all-reduces `partial` (L doubles, Im parts) across
  * ranks between two calls (RCCL over xGMI).

@@ -14,6 +14,7 @@ from . import (
     mu,
     objectives,
     parallelization,
+    parametrization,
     propagators,
     result,
     second_order,
@@ -22,13 +23,25 @@ from . import (
 from .objectives import Objective, ensemble_objectives, gate_objectives, propagate_objectives
 from .batch import optimize_pulses_batch
 from .optimize import optimize_pulses
+from .parametrization import (
+    LinearParametrization,
+    Parametrization,
+    SquareParametrization,
+    TanhParametrization,
+    TanhSqParametrization,
+)
 from .result import Result
 
 __version__ = '0.1.0'
 
 __all__ = [
+    'LinearParametrization',
     'Objective',
+    'Parametrization',
     'Result',
+    'SquareParametrization',
+    'TanhParametrization',
+    'TanhSqParametrization',
     'convergence',
     'conversions',
     'ensemble_objectives',
@@ -40,6 +53,7 @@ __all__ = [
     'optimize_pulses',
     'optimize_pulses_batch',
     'parallelization',
+    'parametrization',
     'propagate_objectives',
     'propagators',
     'result',

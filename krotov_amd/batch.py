@@ -91,6 +91,8 @@ def _batch_obstacle(problems, reps, propagator):
     """Why these problems cannot run as one batch (a short reason), or None."""
     if isinstance(propagator, list) or not (propagator is expm or isinstance(propagator, HipExpm)):
         return "the propagator is not expm / HipExpm"
+    if any(_opt._parametrizations(r.objectives, r.pulse_options) is not None for r in reps):
+        return "a pulse parametrization ('parametrization' in pulse_options)"
     if isinstance(propagator, LindbladExpm) or any(len(o.c_ops) > 0 for r in reps for o in r.objectives):
         return "objectives with c_ops"
     if isinstance(propagator, HipExpm) and getattr(propagator, 'sparse', False):

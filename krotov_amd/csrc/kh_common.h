@@ -132,6 +132,21 @@ __device__ __forceinline__ double kh_uniform(double v) {
     return __hiloint2double(hi, lo);
 }
 
+// eps = f(u) of a pulse parametrization (include/krotov_hip.h: enum kh_par_kind, spelled as numbers here: this header
+// does not see the public one); the kind is decided at run time, per control
+__device__ __forceinline__ double kh_par_eps(int kind, double a, double b, double u) {
+    switch (kind) {
+        case 1: return a * u + b;  // KH_PAR_LINEAR
+        case 2: return u * u;      // KH_PAR_SQUARE
+        case 3: {                  // KH_PAR_TANHSQ
+            const double t = tanh(u);
+            return a * (t * t);
+        }
+        case 4: return a * tanh(u) + b;  // KH_PAR_TANH
+        default: return u;               // KH_PAR_NONE
+    }
+}
+
 // full 64-lane sum, same value (and same summation order) in every lane
 __device__ __forceinline__ double sum64(double v) {
     v = sum16(v);

@@ -293,6 +293,14 @@ struct kh_engine {
     const cplx *so_fw_prev = nullptr;
     cplx *so_fw_store = nullptr;
     const double *so_sigma = nullptr;
+    // pulse parametrizations (kh_set_parametrization); par_dfdu NULL = none
+    const double *par_u_guess = nullptr, *par_dfdu = nullptr;
+    double *par_u_opt = nullptr;
+    int *d_par_kind = nullptr;   // [L] the engine's own copies of the host arrays
+    double *d_par_ab = nullptr;  // [2][L] a, b
+    std::vector<int> par_kind_host;   // what d_par_kind / d_par_ab hold
+    std::vector<double> par_ab_host;
+    bool reduced_par = false;    // reduced_G was set while parametrized (kh_set_update_workgroups)
     // cross-GPU exchange (kh_p2p_*): objectives sharded over `p2p_world` ranks
     int p2p_world = 1, p2p_rank = 0;
     kh_u64 *p2p_window = nullptr;            // this rank's window (fine-grained device memory)
@@ -2460,11 +2468,35 @@ static int launch_tile_update(kh_engine *e, const KhSweepArgs &p, const KhUpdate
     });
 }
 
-static int update_generic(kh_engine *e, const KhSweepArgs &p, const KhUpdateArgs &u, const KhExchange &ex, hipStream_t st) {
+static KhParArgs par_args(const kh_engine *e) {
+    return KhParArgs{e->par_dfdu, e->par_u_opt, e->d_par_kind, e->d_par_ab, e->d_par_ab + e->L};
+}
+
+// the register-tile kernel's parametrized form: one launch over the sweep, one GPU, K > 1 resident workgroups
+template <int RPT, int LT>
+static int launch_tile_update_par(kh_engine *e, const KhSweepArgs &p, const KhUpdateArgs &u, const KhExchange &ex,
+                                  hipStream_t st) {
+    constexpr size_t lds = KhTileLds<RPT, LT>::bytes(KhTileLds<RPT, LT>::UPDATE);
+    const dim3 g(e->K), b(512 / RPT);
+    KhExchange exl = ex;
+    if (LT >= 2 && !e->sw.poll_delay_set) exl.first_poll_delay = 24 + 4 * (LT - 2);  // (as launch_tile_update)
+    e->last_update_grid = e->K;
+    return with_bool(u.sigma != nullptr, [&](auto so) {
+        return launch_persistent_lds<kh_tile_forward_update_par<RPT, LT, decltype(so)::value>>(e, g, b, lds, st, p, u, exl, par_args(e));
+    });
+}
+
+// PAR: the kernels with pulse parametrizations (kh_set_parametrization) -- every update sweep of a parametrized engine
+// comes here, whatever its family: the single launch then runs on min(K, max_wgs) workgroups (or what
+// kh_set_update_workgroups allows), each taking its objectives in turns
+template <bool PAR>
+static int update_generic(kh_engine *e, const KhSweepArgs &p, const KhUpdateArgs &u, const KhExchange &ex_in, hipStream_t st) {
     if (!e->gen_fits)
         return kh_fail(KH_ERR_UNSUPPORTED, "N=%d: this form of the update sweep needs the generic kernels, whose vectors do not fit LDS", e->N);
     const size_t lds = kh_gen_lds_bytes(e->N, e->d_csr_fw == nullptr);
-    int rc = ensure_dynamic_lds(e, e->mixed ? (const void *)kh_gen_forward_update<true> : (const void *)kh_gen_forward_update<false>, lds);
+    const void *fn = PAR ? (e->mixed ? (const void *)kh_gen_forward_update_par<true> : (const void *)kh_gen_forward_update_par<false>)
+                         : (e->mixed ? (const void *)kh_gen_forward_update<true> : (const void *)kh_gen_forward_update<false>);
+    int rc = ensure_dynamic_lds(e, fn, lds);
     ensure_gen_scratch(e, e->plan.grid_update);
     if (rc != KH_OK) return rc;
     KhSweepArgs pg = p;
@@ -2482,19 +2514,35 @@ static int update_generic(kh_engine *e, const KhSweepArgs &p, const KhUpdateArgs
         }
     }
     if (e->gen_adj_ready && u.sigma == nullptr) ug.adj_store = e->d_gen_adj;
-    const dim3 g(e->plan.grid_update), b(KH_GEN_THREADS);
-    if (e->mixed) {  // (mixed engines: the sums on the forward side -- gen_adj_failed is set at creation)
-        if (!ug.internal_exchange) {
-            launch_plain<kh_gen_forward_update<true>>(g, b, lds, st, pg, ug, ex, e->mixed_fw);
-            return KH_OK;
+    KhExchange ex = ex_in;
+    int G = e->plan.grid_update;
+    if (PAR && ug.internal_exchange) {
+        // (an engine of another family may hold more workgroups than the exchange of this kernel takes, or fewer
+        // were asked for: the workgroups walk through the objectives)
+        if (G > e->plan.max_wgs) G = e->plan.max_wgs;
+        if (e->reduced_G > 0 && e->reduced_G < G) G = e->reduced_G;
+        ex.G = G;
+        ex.world = 1;
+        e->last_update_grid = G;
+    }
+    const dim3 g(G), b(KH_GEN_THREADS);
+    return with_bool(e->mixed, [&](auto mixed) {
+        constexpr bool MIXED = decltype(mixed)::value;
+        const KhMixedArgs mx = MIXED ? e->mixed_fw : KhMixedArgs{};
+        if constexpr (PAR) {
+            if (!ug.internal_exchange) {
+                launch_plain<kh_gen_forward_update_par<MIXED>>(g, b, lds, st, pg, ug, ex, mx, par_args(e));
+                return (int)KH_OK;
+            }
+            return launch_persistent<kh_gen_forward_update_par<MIXED>>(e, g, b, lds, st, pg, ug, ex, mx, par_args(e));
+        } else {
+            if (!ug.internal_exchange) {
+                launch_plain<kh_gen_forward_update<MIXED>>(g, b, lds, st, pg, ug, ex, mx);
+                return (int)KH_OK;
+            }
+            return launch_persistent<kh_gen_forward_update<MIXED>>(e, g, b, lds, st, pg, ug, ex, mx);
         }
-        return launch_persistent<kh_gen_forward_update<true>>(e, g, b, lds, st, pg, ug, ex, e->mixed_fw);
-    }
-    if (!ug.internal_exchange) {
-        launch_plain<kh_gen_forward_update<false>>(g, b, lds, st, pg, ug, ex, KhMixedArgs{});
-        return KH_OK;
-    }
-    return launch_persistent<kh_gen_forward_update<false>>(e, g, b, lds, st, pg, ug, ex, KhMixedArgs{});
+    });
 }
 
 // five to eight controls, N <= 64, one resident workgroup per objective, first order: the register-tile form with
@@ -2535,6 +2583,26 @@ static int launch_update(kh_engine *e, const KhUpdateArgs &u, hipStream_t st) {
     const bool whole = !stepwise && u.n_begin == 0 && u.n_end == e->nt - 1;
     e->last_update_grid = 0;
     int rc = KH_OK;
+    if (e->par_dfdu != nullptr) {
+        // pulse parametrizations (kh_set_parametrization): the whole sweep of a register-tile engine (q2 kind, mini and
+        // quad included: the kernel they already run stepwise) on the tile kernel's parametrized form while its K workgroups
+        // are all resident; everything else -- other families, stepwise launches, reduced grids -- on the generic one
+        const KhPlan &pl = e->plan;
+        const bool tile_kind = pl.kind == KIND_TILE_Q2 || pl.kind == KIND_TILE_RPT1 || pl.kind == KIND_TILE_RPT2;
+        rc = KH_ERR_UNSUPPORTED;
+        if (whole && tile_kind && !pl.ens && !pl.stream && !pl.stepwise_only && pl.grid_update == e->K && e->K > 1 &&
+            e->reduced_G == 0 && ex.world == 1 && ex.G == e->K && e->sw.tile_single && !e->mixed && e->d_csr_fw == nullptr &&
+            e->N <= KH_TILE_N && e->L >= 1 && e->L <= 4) {
+            rc = with_tile(pl.kind == KIND_TILE_RPT2, e->L, [&](auto rpt, auto lt) {
+                return launch_tile_update_par<decltype(rpt)::value, decltype(lt)::value>(e, p, u, ex, st);
+            });
+            if (rc != KH_OK && rc != KH_ERR_UNSUPPORTED) return rc;  // (unsupported: the grid cannot be resident)
+        }
+        if (rc != KH_OK) rc = update_generic<true>(e, p, u, ex, st);
+        if (rc != KH_OK) return rc;
+        KH_HIP(hipGetLastError());
+        return KH_OK;
+    }
     switch (update_route(e->plan, e->K, stepwise, whole, u.sigma != nullptr, e->reduced_G, ex.world, e->d_sq_fw != nullptr,
                          [e] { return ensure_gen_adj(e); })) {
         case ROUTE_ENS: rc = update_ens(e, p, u, ex, st, false); break;
@@ -2556,7 +2624,7 @@ static int launch_update(kh_engine *e, const KhUpdateArgs &u, hipStream_t st) {
             });
             break;
         case ROUTE_TILEX: rc = update_tilex(e, p, u, ex, st); break;
-        case ROUTE_GENERIC: rc = update_generic(e, p, u, ex, st); break;
+        case ROUTE_GENERIC: rc = update_generic<false>(e, p, u, ex, st); break;
         case ROUTE_LIND: rc = update_lind(e, p, u, ex, st); break;
     }
     if (rc != KH_OK) return rc;
@@ -2589,6 +2657,7 @@ static KhUpdateArgs update_args(kh_engine *e, const kh_cdouble *chi_store, const
     u.internal_exchange = 1;
     u.adj_sign = e->adj_sign;
     u.adj_store = nullptr;
+    if (e->par_dfdu != nullptr) u.guess = e->par_u_guess;  // (the sweep updates u; eps = f(u) goes to `opt`)
     return u;
 }
 
@@ -2681,6 +2750,7 @@ extern "C" int kh_set_update_workgroups(kh_engine *e, int32_t max_workgroups, in
     if (e->row_split > 1 && chosen != nullptr) *chosen = e->split_groups * e->row_split;
     if (max_workgroups == 0) {
         e->reduced_G = 0;
+        e->reduced_par = false;
         return KH_OK;
     }
     if (e->replicas > 0) return kh_fail(KH_ERR_UNSUPPORTED, "replica engines (kh_engine_create_replicas) run one workgroup per replica: no form with fewer workgroups");
@@ -2689,7 +2759,12 @@ extern "C" int kh_set_update_workgroups(kh_engine *e, int32_t max_workgroups, in
     if (e->p2p_ready) return kh_fail(KH_ERR_UNSUPPORTED, "sharded sweeps keep their grid (all ranks must agree on the form)");
     const KhPlan &p = e->plan;
     int G = 0;
-    if (p.ens) {
+    if (e->par_dfdu != nullptr) {
+        // a parametrized engine (kh_set_parametrization): the generic kernels take their objectives in turns on any grid
+        G = p.grid_update < p.max_wgs ? p.grid_update : p.max_wgs;
+        if (max_workgroups < G) G = max_workgroups;
+        e->reduced_par = true;  // (not a grid the engine's own family was asked about: dropped with the parametrization)
+    } else if (p.ens) {
         const int widest = (e->K + 2 * KH_ENS_MAXCG - 1) / (2 * KH_ENS_MAXCG);
         if (max_workgroups < widest)
             return kh_fail(KH_ERR_UNSUPPORTED, "the ensemble kernel needs at least %d workgroups for %d objectives", widest, e->K);
@@ -2748,6 +2823,7 @@ extern "C" int kh_set_row_split(kh_engine *e, int workgroups_per_objective) {
         e->row_split = 1;
         return KH_OK;
     }
+    if (e->par_dfdu != nullptr) return kh_fail(KH_ERR_UNSUPPORTED, "a parametrized engine (kh_set_parametrization) keeps one workgroup per objective");
     const int max_wgs = e->plan.max_wgs;  // (what the exchange takes: at most 256, at most one per CU)
     if (S > e->num_cus || S > max_wgs)
         return kh_fail(KH_ERR_UNSUPPORTED, "%d workgroups per objective: this device runs at most %d at once", S, e->num_cus < max_wgs ? e->num_cus : max_wgs);
@@ -2793,6 +2869,51 @@ extern "C" int kh_set_second_order(kh_engine *e, const kh_cdouble *fw_prev_dev, 
     return KH_OK;
 }
 
+// Pulse parametrizations eps_l = f_l(u_l) (include/krotov_hip.h): the following update sweeps update u and propagate with
+// f(u) -- on the register-tile kernel's parametrized form or the generic kernels', by launch_update's rule
+extern "C" int kh_set_parametrization(kh_engine *e, const int32_t *kind, const double *a, const double *b,
+                                      const double *u_guess_dev, const double *dfdu_dev, double *u_opt_dev) {
+    if (e == nullptr) return kh_fail(KH_ERR_INVALID, "null engine");
+    if (kind == nullptr) {
+        e->par_u_guess = e->par_dfdu = nullptr;
+        e->par_u_opt = nullptr;
+        if (e->reduced_par) e->reduced_G = 0;  // (a reduced grid set while parametrized goes with it)
+        e->reduced_par = false;
+        return KH_OK;
+    }
+    if (e->lind) return kh_fail(KH_ERR_UNSUPPORTED, "Lindblad-form engines (kh_engine_create_lindblad) take no pulse parametrization: build the Liouvillian and use kh_engine_create");
+    if (e->replicas > 0) return kh_fail(KH_ERR_UNSUPPORTED, "replica engines (kh_engine_create_replicas) take no pulse parametrization");
+    if (e->p2p_ready || e->p2p_window != nullptr) return kh_fail(KH_ERR_UNSUPPORTED, "sharded engines take no pulse parametrization (one GPU)");
+    if (e->row_split > 1) return kh_fail(KH_ERR_UNSUPPORTED, "a split engine (kh_set_row_split) takes no pulse parametrization: set the row split to 1 first");
+    if (!e->gen_fits) return kh_fail(KH_ERR_UNSUPPORTED, "N=%d: pulse parametrizations run on the generic kernels, whose vectors do not fit LDS", e->N);
+    if (e->L < 1) return kh_fail(KH_ERR_INVALID, "no controls to parametrize");
+    if (a == nullptr || b == nullptr || u_guess_dev == nullptr || dfdu_dev == nullptr || u_opt_dev == nullptr)
+        return kh_fail(KH_ERR_INVALID, "null argument");
+    if (u_opt_dev == u_guess_dev) return kh_fail(KH_ERR_INVALID, "u_opt_dev must not alias u_guess_dev");
+    for (int l = 0; l < e->L; ++l)
+        if (kind[l] < KH_PAR_NONE || kind[l] > KH_PAR_TANH) return kh_fail(KH_ERR_INVALID, "control %d: unknown parametrization kind %d", l, (int)kind[l]);
+    if (e->d_par_kind == nullptr) {
+        KH_TRY(dev_alloc(e, &e->d_par_kind, sizeof(int) * (size_t)e->L));
+        KH_TRY(dev_alloc(e, &e->d_par_ab, sizeof(double) * 2 * (size_t)e->L));
+    }
+    // the tables change rarely (an optimisation sets the same ones before every sweep): uploaded when they do -- blocking
+    // copies from the caller's host arrays, behind a device-wide wait for an earlier sweep that may still read them
+    std::vector<int> kinds(kind, kind + e->L);
+    std::vector<double> ab(a, a + e->L);
+    ab.insert(ab.end(), b, b + e->L);
+    if (kinds != e->par_kind_host || ab != e->par_ab_host) {
+        KH_HIP(hipDeviceSynchronize());
+        KH_HIP(hipMemcpy(e->d_par_kind, kinds.data(), sizeof(int) * kinds.size(), hipMemcpyHostToDevice));
+        KH_HIP(hipMemcpy(e->d_par_ab, ab.data(), sizeof(double) * ab.size(), hipMemcpyHostToDevice));
+        e->par_kind_host = kinds;
+        e->par_ab_host = ab;
+    }
+    e->par_u_guess = u_guess_dev;
+    e->par_dfdu = dfdu_dev;
+    e->par_u_opt = u_opt_dev;
+    return KH_OK;
+}
+
 // replica engines: the same switch with one sigma row per replica ([B][nt-1]; kh_replica.h, kh_rep_forward_update_so)
 extern "C" int kh_set_second_order_replicas(kh_engine *e, const kh_cdouble *fw_prev_dev, kh_cdouble *fw_store_dev,
                                             const double *sigma_dev) {
@@ -2825,6 +2946,8 @@ extern "C" int kh_update_begin(kh_engine *e, const kh_cdouble *chi_store_dev, co
     KH_HIP(hipMemcpyAsync(opt_dev, guess_dev, sizeof(double) * (size_t)e->L * (e->nt - 1),
                           hipMemcpyDeviceToDevice, st));
     KH_HIP(hipMemsetAsync(g_a_dev, 0, sizeof(double) * e->L, st));
+    if (e->par_dfdu != nullptr)
+        KH_HIP(hipMemcpyAsync(e->par_u_opt, e->par_u_guess, sizeof(double) * (size_t)e->L * (e->nt - 1), hipMemcpyDeviceToDevice, st));
     const KhUpdateArgs u = update_args(e, chi_store_dev, chi_norms_dev, guess_dev, nullptr, nullptr, opt_dev, g_a_dev);
     return update_interval(e, u, nullptr, 0, 0, nullptr, partial_dev, true, st);
 }
@@ -2907,6 +3030,7 @@ extern "C" int kh_p2p_create_window(kh_engine *e, int32_t world, int32_t rank, u
     if (e->mixed) return kh_fail(KH_ERR_UNSUPPORTED, "mixed engines (kh_engine_create_mixed) are not sharded");
     if (e->lind) return kh_fail(KH_ERR_UNSUPPORTED, "Lindblad-form engines (kh_engine_create_lindblad) are not sharded");
     if (e->replicas > 0) return kh_fail(KH_ERR_UNSUPPORTED, "replica engines (kh_engine_create_replicas) are not sharded");
+    if (e->par_dfdu != nullptr) return kh_fail(KH_ERR_UNSUPPORTED, "a parametrized engine (kh_set_parametrization) is not sharded");
     const int Lx = e->L > 0 ? e->L : 1;
     if (world * Lx * 2 > 64 || Lx > KH_MAX_L)
         return kh_fail(KH_ERR_UNSUPPORTED, "world * L = %d exceeds the 32 exchange lanes (or more than %d controls)", world * Lx, KH_MAX_L);

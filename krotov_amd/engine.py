@@ -484,6 +484,36 @@ class HipKrotovEngine:
         _lib.check(self._lib.kh_set_second_order(
             self._handle, fw_prev.data_ptr(), fw_store.data_ptr(), sig.data_ptr()))
 
+    def set_parametrization(self, kind=None, a=None, b=None, u_guess=None, dfdu=None, u_opt=None):
+        """Switch the following update sweeps to pulse parametrizations eps_l = f_l(u_l) (``kh_set_parametrization``):
+        ``kind``, ``a``, ``b``: (L,) host arrays (``enum kh_par_kind`` and its parameters); ``u_guess``, ``dfdu``:
+        (L, nt-1) u under the guess pulses and f'(u_guess); ``u_opt``: (L, nt-1) float64 device tensor the sweep writes
+        u_new to (its ``opt`` holds f(u_new)).  No arguments (``kind=None``): off again.  ``KrotovHipError``
+        (``KH_ERR_UNSUPPORTED``) on replica, Lindblad-form and sharded engines."""
+        if kind is None:
+            self._par = None
+            _lib.check(self._lib.kh_set_parametrization(self._handle, None, None, None, None, None, None))
+            return
+        L = self.L
+        kind = np.ascontiguousarray(kind, dtype=np.int32).reshape(L)
+        a = np.ascontiguousarray(a, dtype=np.float64).reshape(L)
+        b = np.ascontiguousarray(b, dtype=np.float64).reshape(L)
+        if self.replicas or u_guess is None or dfdu is None or u_opt is None:
+            # (the library's own answer, before any shape is looked at: KH_ERR_UNSUPPORTED on a replica engine, whose
+            # pulses have another shape; KH_ERR_INVALID for a missing array)
+            _lib.check(self._lib.kh_set_parametrization(self._handle, kind.ctypes.data, a.ctypes.data, b.ctypes.data,
+                                                        None, None, None))
+            return
+        u_guess = self._f(u_guess, (L, self.nt - 1))
+        dfdu = self._f(dfdu, (L, self.nt - 1))
+        if (not isinstance(u_opt, torch.Tensor) or tuple(u_opt.shape) != (L, self.nt - 1) or u_opt.dtype != torch.float64
+                or u_opt.device != self.device or not u_opt.is_contiguous()):
+            raise ValueError("u_opt must be a contiguous (L, nt-1) float64 device tensor")
+        _lib.check(self._lib.kh_set_parametrization(
+            self._handle, kind.ctypes.data, a.ctypes.data, b.ctypes.data, u_guess.data_ptr(), dfdu.data_ptr(),
+            u_opt.data_ptr()))
+        self._par = (u_guess, dfdu, u_opt)  # keep the tensors alive while the engine points at them
+
     def set_second_order_replicas(self, fw_prev=None, fw_store=None, sigma_vals=None):
         """Replica engines: switch the following update sweeps to the second-order update with one sigma row per
         replica (``fw_prev``, ``fw_store``: (K, nt, N) device tensors; ``sigma_vals``: (B, nt-1), sigma_b at replica

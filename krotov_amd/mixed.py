@@ -129,7 +129,7 @@ class LindbladLayout:
         return out
 
 
-def lindblad_layout_of(objectives, propagator=None, n_controls=None, second_order=False):
+def lindblad_layout_of(objectives, propagator=None, n_controls=None, second_order=False, parametrized=False):
     """Decide, on the host, how a list in which some objective carries ``c_ops`` runs (see :class:`LindbladLayout`).
     A control inside ``c_ops`` raises ``NotImplementedError`` (as the reference's ``mu`` does, mu.py:135-139).  Objectives
     without ``c_ops`` are fine in a matrix-form list when they, too, are d x d density matrices under a d x d
@@ -139,6 +139,8 @@ def lindblad_layout_of(objectives, propagator=None, n_controls=None, second_orde
             raise NotImplementedError("Time-dependent collapse operators not implemented")
     if second_order:
         return LindbladLayout('liouvillian', "second-order update (sigma=)")
+    if parametrized:
+        return LindbladLayout('liouvillian', "pulse parametrization ('parametrization' in pulse_options)")
     ds, n_c = set(), 0
     for k, obj in enumerate(objectives):
         op = _drift(obj, k)

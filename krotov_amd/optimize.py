@@ -54,6 +54,7 @@ from .info_hooks import chain
 from .mixed import Layout, LindbladLayout, layout_of, lindblad_layout_of
 from .mu import derivative_wrt_pulse
 from .parallelization import serial_map
+from .parametrization import Parametrization, PulseParameters
 from .propagators import HipExpm, LindbladExpm, Propagator, expm
 from .result import Result
 from .second_order import _overlap
@@ -123,6 +124,18 @@ def _initialize_krotov_controls(objectives, pulse_options, tlist):
             )
         shape_arrays.append(_checked_shape(control_onto_interval(S)))
     return guess_controls, guess_pulses, pulses_mapping, lambda_vals, shape_arrays
+
+
+def _parametrizations(objectives, pulse_options):
+    """``pulse_options[ctrl]['parametrization']`` per control, in the controls' order (None: the control is its own
+    parameter), or None when no control has one."""
+    options_list = pulse_options_dict_to_list(pulse_options, extract_controls(objectives))
+    params = [o.get('parametrization', None) for o in options_list]
+    for l, par in enumerate(params):
+        if par is not None and not isinstance(par, Parametrization):
+            raise ValueError("control %d: 'parametrization' in pulse_options must be a krotov_amd.parametrization."
+                             "Parametrization, not %r" % (l, par))
+    return params if any(par is not None for par in params) else None
 
 
 def _restore_from_previous_result(result, objectives, tlist, store_all_pulses):
@@ -255,7 +268,7 @@ class _PluginBackend:
         return np.array([self.overlap(obj.target, s) for s, obj in zip(fw_states_T, self.objectives)])
 
     def iterate(self, chi_states, chi_norms, guess_pulses, lambda_vals, shape_arrays, sigma=None,
-                forward_states0=None):
+                forward_states0=None, par=None):
         objectives, tlist = self.objectives, self.tlist
         K, nt = len(objectives), len(tlist)
         backward_states = self.pmap[1](
@@ -264,6 +277,9 @@ class _PluginBackend:
         )
         g_a = np.zeros(len(guess_pulses))
         optimized = copy.deepcopy(guess_pulses)
+        if par is not None:  # pulse parametrizations: u is updated, the interval is propagated with f(u)
+            dfdu = par.dfdu()
+            u_new = [np.array(u, dtype=np.float64) for u in par.u]
         fw_states = [obj.initial_state for obj in objectives]
         forward_states = moved = None
         if sigma is not None:  # second order: keep phi(t_n) and phi(t_n) - phi_prev(t_n) (optimize.py:429-442)
@@ -287,6 +303,12 @@ class _PluginBackend:
                     total += update
                 step = shape_arrays[l][n] / lambda_vals[l]
                 d1 = total.imag
+                if par is not None:
+                    d1 = dfdu[l][n] * d1  # dH/du = f'(u_guess) dH/d eps
+                    u_new[l][n] = par.u[l][n] + step * d1
+                    g_a[l] += step * abs(d1) ** 2 * dt
+                    optimized[l][n] = par.eps(l, u_new[l][n])
+                    continue
                 g_a[l] += step * abs(d1) ** 2 * dt
                 optimized[l][n] += step * d1
             fw_states = self.pmap[2](
@@ -297,6 +319,8 @@ class _PluginBackend:
                 moved = [fw_states[k] - forward_states0[k][n + 1] for k in range(K)]
                 for k in range(K):
                     forward_states[k][n + 1] = fw_states[k]
+        if par is not None:
+            par.commit(u_new, optimized)
         return backward_states, optimized, fw_states, g_a, forward_states
 
 
@@ -463,7 +487,7 @@ class _HipBackend:
     device = True
 
     def __init__(self, objectives, pulses_mapping, tlist, n_controls, propagator, process_group=None,
-                 second_order=False):
+                 second_order=False, parametrized=False):
         import torch
 
         from .engine import HipKrotovEngine
@@ -491,7 +515,7 @@ class _HipBackend:
         # built on the host and today's engines (host-only decision)
         self.lindblad = None
         if any(len(obj.c_ops) > 0 for obj in objectives):
-            lind = lindblad_layout_of(objectives, propagator, n_controls, second_order)
+            lind = lindblad_layout_of(objectives, propagator, n_controls, second_order, parametrized)
             if lind.matrix:
                 if process_group is not None:
                     raise ValueError("objectives in Lindblad form run on one GPU: process_group= (sharding) is not "
@@ -645,7 +669,7 @@ class _HipBackend:
         chi, norms = self.last_chi
         return self._gather_rows(chi.cpu().numpy()), self._gather_rows(norms.cpu().numpy())
 
-    def iterate(self, chi_T, chi_norms, guess_pulses, lambda_vals, shape_arrays, sigma=None, chi_coef=None):
+    def iterate(self, chi_T, chi_norms, guess_pulses, lambda_vals, shape_arrays, sigma=None, chi_coef=None, par=None):
         """chi_T: (K_total, N) normalised co-states (host); chi_norms (K_total,) -- or
         ``chi_coef = (c, d)``, (K_total,) each: chi_k(T) = c_k target_k + d_k phi_k(T) is
         then formed and normalised on the device (kh_chi_boundary)."""
@@ -666,6 +690,15 @@ class _HipBackend:
             if self.fw_next is None:
                 self.fw_next = t.empty_like(self.fw_prev)
             eng.set_second_order(self.fw_prev, self.fw_next, sig)
+        u_opt = None
+        if par is not None:
+            # pulse parametrizations: the update sweep reads u under the guess and f'(u) in place of the guess pulses,
+            # writes u_new next to the pulses f(u_new) it propagates with (kh_set_parametrization)
+            kind, a, b = par.device_kinds
+            u_guess = eng.dev(np.array(par.u, dtype=np.float64).reshape(self.L, self.nt - 1), t.float64)
+            dfdu = eng.dev(par.dfdu().reshape(self.L, self.nt - 1), t.float64)
+            u_opt = t.empty_like(u_guess)
+            eng.set_parametrization(kind, a, b, u_guess, dfdu, u_opt)
         if chi_coef is not None:
             c, d = chi_coef
             psi = self.fw_T_dev if self.fw_T_dev is not None else self.init  # (d == 0 without phi(T))
@@ -797,6 +830,8 @@ class _HipBackend:
         opt_host = opt.cpu().numpy()
         self.__dict__.setdefault('_uploads', {})['pulses'] = (opt_host.copy(), opt)  # (the next iteration's guess, if unchanged)
         optimized = [opt_host[l].copy() for l in range(self.L)]
+        if par is not None:
+            par.commit(u_opt.cpu().numpy(), optimized)
         backward_states = _DeviceTrajectories(self.chi_store, self.likes, self.k0, layout=self.layout)
         forward_states = None
         if sigma is not None:
@@ -856,6 +891,11 @@ def optimize_pulses(
       handed to ``info_hook`` and ``sigma.refresh`` fetch single states on
       access (with ``process_group``: all time points of this rank's
       objectives, the final time of every objective).
+    * ``pulse_options[ctrl]['parametrization']`` (extension): a
+      :class:`~krotov_amd.parametrization.Parametrization`, eps = f(u) -- the update is applied to the unconstrained
+      u and the control stays inside the range of f (bounded controls).  ``Result``, hooks and dumps hold eps;
+      ``g_a_integrals`` is the running cost in u.  The built-in kinds run inside the device's update sweep, a subclass
+      of your own through the host loop; not with ``process_group``.
     * ``limit_thread_pool`` is accepted and ignored (no BLAS on the hot path).
     """
     logger = logging.getLogger('krotov')
@@ -866,12 +906,18 @@ def optimize_pulses(
             "skip_initial_forward_propagation is incompatible with second order Krotov (sigma is not None)"
         )
     device_path = _use_device_path(propagator, mu, overlap, sigma, storage, objectives)
+    params = _parametrizations(objectives, pulse_options)
+    if params is not None and process_group is not None:
+        # (host-only, the same verdict on every rank, before any collective)
+        raise ValueError("pulse parametrizations run on one GPU: process_group= (sharding) is not supported with "
+                         "'parametrization' in pulse_options")
     if process_group is not None and not device_path:
         raise ValueError("process_group requires the device path (propagator=krotov_amd.propagators.expm)")
     if device_path and any(len(obj.c_ops) > 0 for obj in objectives):
         # (host-only, before any GPU work and any collective: a control inside c_ops raises here; the same verdict on
         # every rank)
-        if lindblad_layout_of(objectives, propagator, None, second_order).matrix and process_group is not None:
+        if (lindblad_layout_of(objectives, propagator, None, second_order, params is not None).matrix
+                and process_group is not None):
             raise ValueError("objectives in Lindblad form run on one GPU: process_group= (sharding) is not supported "
                              "for the matrix-form engine")
     elif process_group is not None and layout_of(objectives, propagator).mixed:
@@ -911,6 +957,15 @@ def optimize_pulses(
             continue_from, objectives, tlist, store_all_pulses
         )
     g_a_integrals = np.zeros(len(guess_pulses))
+    par = None
+    if params is not None:
+        # u of the first guess (a value outside the range raises, naming control and interval); a continued run
+        # re-derives it from the stored pulses, where rounding may have put a value on a bound
+        par = PulseParameters(params, guess_pulses, pull=continue_from is not None)
+        if device_path and par.device_kinds is None:
+            logger.info("pulse parametrization: a user-defined Parametrization (kind None) is evaluated on the host; "
+                        "running the host loop around single-step propagations on the GPU")
+            device_path = False
     if device_path and len(guess_pulses) > _KH_MAX_CONTROLS and process_group is None:
         # the sweep kernels are compiled for at most 32 controls (KH_GEN_MAX_L: the generic kernels; the register-resident
         # families take 8); the reference takes any number (optimize.py:33-55, conversions.py:140-254).  More than that
@@ -928,7 +983,7 @@ def optimize_pulses(
 
     if device_path:
         backend = _HipBackend(objectives, pulses_mapping, tlist, len(guess_pulses), propagator, process_group,
-                              second_order=second_order)
+                              second_order=second_order, parametrized=par is not None)
     else:
         backend = _PluginBackend(
             objectives, adjoint_objectives, pulses_mapping, tlist, propagators, storage, parallel_map, mu, overlap
@@ -1018,14 +1073,20 @@ def optimize_pulses(
                 chi_T = np.array(vecs)
 
         g_a_integrals[:] = 0.0
+        if par is not None:
+            # u is carried from sweep to sweep; only a pulse that a hook (modify_params_after_iter) has edited since
+            # is inverted again
+            redone = par.sync(guess_pulses)
+            if redone:
+                logger.info("pulse parametrization: controls %s were changed after the last sweep; u re-derived", redone)
         if device_path:
             backward_states, optimized_pulses, fw_states_T, g_a, forward_states = backend.iterate(
-                chi_T, chi_norms, guess_pulses, lambda_vals, shape_arrays, sigma=sigma, chi_coef=chi_coef
+                chi_T, chi_norms, guess_pulses, lambda_vals, shape_arrays, sigma=sigma, chi_coef=chi_coef, par=par
             )
         else:
             backward_states, optimized_pulses, fw_states_T, g_a, forward_states = backend.iterate(
                 chi_states, chi_norms, guess_pulses, lambda_vals, shape_arrays, sigma=sigma,
-                forward_states0=forward_states0,
+                forward_states0=forward_states0, par=par,
             )
         g_a_integrals[:] = g_a
         tau_vals = backend.tau_vals(fw_states_T)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Compile the library for gfx950 and print VGPRs / spills / occupancy per kernel (dev tool, no GPU needed).
+"""Compile the library for gfx950 and print VGPRs / spills / occupancy / static LDS per kernel (dev tool, no GPU needed).
 usage: python scripts/kernel_resources.py [extra hipcc flags]"""
 import os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,6 +21,6 @@ for line in out.splitlines():
     if 'error' in line:
         print(line)
 for name, r in rows.items():
-    print('%-66s VGPR %3d AGPR %3d spill %3d scratch %4d B/lane  SGPR spill %3d occ %d' % (
+    print('%-66s VGPR %3d AGPR %3d spill %3d scratch %4d B/lane  SGPR spill %3d occ %d  LDS %6d B' % (
         name[:66], r.get('VGPRs', -1), r.get('AGPRs', -1), r.get('VGPRs Spill', -1), r.get('ScratchSize [bytes/lane]', -1),
-        r.get('SGPRs Spill', -1), r.get('Occupancy [waves/SIMD]', -1)))
+        r.get('SGPRs Spill', -1), r.get('Occupancy [waves/SIMD]', -1), r.get('LDS Size [bytes/block]', -1)))
