@@ -23,6 +23,37 @@
  *     call.  stream is a hipStream_t passed as void* (NULL = default stream).
  *     All sweeps are asynchronous on that stream.
  *   - not thread-safe per engine; one engine per device per stream.
+ *
+ * Memory contract (every "dev" pointer of every entry point; enforced by tests/test_memory_contract.py on guarded,
+ * minimally aligned buffers)
+ *   Alignment.  A device pointer is aligned to its element type and NO MORE is assumed: 16 bytes for kh_cdouble (the
+ *     kernels load and store a complex number as one 16-byte access), 8 bytes for double, 4 bytes for int32_t.  Any
+ *     element-aligned address qualifies -- a row of a larger array, a slice that starts in the middle of one; no
+ *     kernel widens an access over two doubles or two indices of a caller's array.  A pointer below its element's
+ *     alignment is undefined behaviour; the C entry points do not inspect addresses.
+ *   Extent.  The library reads and writes only the extent documented for each argument ([K][nt][N], [L][nt-1], ...:
+ *     exactly that many elements, densely packed, no padding behind rows), for every N, K, L and nt it accepts -- tiles
+ *     are masked, nothing is prefetched past the last interval, element nt-1 of an [L][nt-1] array does not exist, a
+ *     workgroup without an objective writes nothing.  CSR: indptr [N+1], indices [nnz], data [nnz]; every index read
+ *     from them must be a valid column.  Memory next to an extent may hold anything, NaN included, and may be unmapped.
+ *   Inputs are never written: operator arrays, CSR arrays, expectation operators, pulses, shapes, lambda, norms,
+ *     sigma, init, targets, chi_T, fw_prev_dev, u_guess_dev, dfdu_dev -- and chi_store_dev in the update sweeps
+ *     (kh_forward_update, kh_update_*), which only kh_backward_store writes.  Outputs are the arguments marked OUT
+ *     (and states_dev, psi_T_dev, chi_store_dev of the plain sweeps, tau_dev, out_dev, chi_T_dev, chi_norms_dev,
+ *     partial_dev); fw_store_dev and u_opt_dev are outputs of the update sweeps while set.  A sweep writes its outputs
+ *     in full (replica engines: the active replicas' slices only, kh_set_active_replicas) and never reads what they
+ *     held before it (kh_update_begin ... kh_update_end count as one sweep: opt_dev and g_a_dev are carried from
+ *     call to call).
+ *   Overlap.  No output overlaps any other argument of the same call, nor an array the engine holds a pointer to
+ *     (operators, fw_prev_dev / fw_store_dev / sigma_dev, u_guess_dev / dfdu_dev / u_opt_dev); inputs may overlap one
+ *     another freely (equal operator pointers, init_dev == a row block of a stored trajectory, ...).  One exception,
+ *     which the per-interval driver relies on: D_dev of kh_update_step / kh_update_step_dev may be partial_dev itself
+ *     (the all-reduce ran in place; the sums are read before the next interval's are written).  Between calls every
+ *     buffer is the caller's again: the output of one call is commonly the input of the next (psi_T_dev ->
+ *     kh_chi_boundary -> kh_backward_store -> kh_forward_update; fw_store_dev and fw_prev_dev swapped per iteration).
+ *   Lifetime.  Operator and CSR arrays must stay valid and unchanged while the engine lives; the arrays of
+ *     kh_set_second_order(_replicas) and kh_set_parametrization while they are set (their CONTENT may change between
+ *     sweeps); everything else until the stream has passed the call.
  */
 #ifndef KROTOV_HIP_H
 #define KROTOV_HIP_H

@@ -216,7 +216,7 @@ class HipKrotovEngine:
                     host = op.detach().cpu().numpy() if isinstance(op, torch.Tensor) else np.asarray(op)
                     host = np.ascontiguousarray(host, dtype=np.complex128)
                     self._check_dim(host.shape)
-                    t = torch.from_numpy(host).to(self.device)
+                    t = self._upload(host)
                     self._op_tensors[key] = (t, op)  # keep `op` alive: id() stays unique
                     norms_cache[key] = float(np.linalg.norm(host, 2)) if host.size else 0.0
                 ptrs[idx] = self._op_tensors[key][0].data_ptr()
@@ -261,7 +261,7 @@ class HipKrotovEngine:
                 host = np.ascontiguousarray(host, dtype=np.complex128)
                 if host.shape != (self.d, self.d):
                     raise ValueError("Lindblad form: every operator must be %d x %d" % (self.d, self.d))
-                self._op_tensors[key] = (torch.from_numpy(host).to(self.device), op)
+                self._op_tensors[key] = (self._upload(host), op)
                 if hamiltonian and np.array_equal(host, host.conj().T):
                     ev = np.linalg.eigvalsh(host)
                     norms_cache[key] = 0.5 * float(ev[-1] - ev[0])
@@ -307,9 +307,9 @@ class HipKrotovEngine:
             mat = sp.csr_matrix(mat, dtype=np.complex128)
             mat.sum_duplicates()
             arrays = (
-                torch.from_numpy(np.ascontiguousarray(mat.indptr, dtype=np.int32)).to(self.device),
-                torch.from_numpy(np.ascontiguousarray(mat.indices, dtype=np.int32)).to(self.device),
-                torch.from_numpy(np.ascontiguousarray(mat.data, dtype=np.complex128)).to(self.device),
+                self._upload(np.ascontiguousarray(mat.indptr, dtype=np.int32)),
+                self._upload(np.ascontiguousarray(mat.indices, dtype=np.int32)),
+                self._upload(np.ascontiguousarray(mat.data, dtype=np.complex128)),
             )
             return arrays, int(mat.nnz)
 
@@ -390,6 +390,16 @@ class HipKrotovEngine:
     def _stream(self):
         return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
+    # The two places where the engine itself makes device tensors that a kernel gets the address of (a subclass may
+    # place them elsewhere: tests/guarded.py).  Memory contract: include/krotov_hip.h.
+    def _upload(self, host_array):
+        """A contiguous host array (operator, CSR array) as a device tensor."""
+        return torch.from_numpy(host_array).to(self.device)
+
+    def _empty(self, shape, dtype):
+        """An uninitialised device tensor the engine keeps or returns."""
+        return torch.empty(shape, dtype=dtype, device=self.device)
+
     def dev(self, x, dtype):
         """Contiguous tensor of ``dtype`` on the engine's device."""
         if isinstance(x, torch.Tensor):
@@ -417,7 +427,8 @@ class HipKrotovEngine:
         """``t`` as an output buffer (written in place), or a new one."""
         if t is None:
             return torch.empty(shape, dtype=dtype, device=self.device)
-        if tuple(t.shape) != tuple(shape) or t.dtype != dtype or not t.is_contiguous() or t.device != self.device:
+        if (not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(shape) or t.dtype != dtype or not t.is_contiguous()
+                or t.device != self.device):
             raise ValueError("output buffer must be a contiguous %s %s tensor on %s" % (tuple(shape), dtype, self.device))
         return t
 
@@ -460,8 +471,7 @@ class HipKrotovEngine:
         """Backward sweep storing chi(t_n); returns (K, nt, N).  ``pulses``: (L, nt-1) -- replica engines: (B, L, nt-1)."""
         pulses = self._f(pulses, self._pulse_shape())
         chi_T = self._c(chi_T, (self.K, self.N))
-        if out is None:
-            out = torch.empty((self.K, self.nt, self.N), dtype=torch.complex128, device=self.device)
+        out = self._out(out, (self.K, self.nt, self.N), torch.complex128)
         with self._timed('backward'):
             _lib.check(self._lib.kh_backward_store(
                 self._handle, chi_T.data_ptr(), pulses.data_ptr(), out.data_ptr(), self._stream()))
@@ -477,8 +487,9 @@ class HipKrotovEngine:
             _lib.check(self._lib.kh_set_second_order(self._handle, None, None, None))
             return
         fw_prev = self._c(fw_prev, (self.K, self.nt, self.N))
-        if tuple(fw_store.shape) != (self.K, self.nt, self.N) or fw_store.dtype != torch.complex128:
-            raise ValueError("fw_store must be a (K, nt, N) complex128 device tensor")
+        if (not isinstance(fw_store, torch.Tensor) or tuple(fw_store.shape) != (self.K, self.nt, self.N)
+                or fw_store.dtype != torch.complex128 or fw_store.device != self.device or not fw_store.is_contiguous()):
+            raise ValueError("fw_store must be a contiguous (K, nt, N) complex128 device tensor")
         sig = self._f(sigma_vals, (self.nt - 1,))
         self._so = (fw_prev, fw_store, sig)  # keep the tensors alive while the engine points at them
         _lib.check(self._lib.kh_set_second_order(
@@ -605,18 +616,12 @@ class HipKrotovEngine:
         # persistent buffers: stable addresses let the captured graph be reused
         b = getattr(self, '_sh', None)
         if b is None:
-            c128, f64, dev = torch.complex128, torch.float64, self.device
+            c128, f64 = torch.complex128, torch.float64
             b = self._sh = dict(
-                chi_norms=torch.empty((K,), dtype=f64, device=dev),
-                init=torch.empty((K, N), dtype=c128, device=dev),
-                guess=torch.empty((L, nt - 1), dtype=f64, device=dev),
-                shape=torch.empty((L, nt - 1), dtype=f64, device=dev),
-                lambdas=torch.empty((L,), dtype=f64, device=dev),
-                opt=torch.empty((L, nt - 1), dtype=f64, device=dev),
-                psi_T=torch.empty((K, N), dtype=c128, device=dev),
-                g_a=torch.empty((L,), dtype=f64, device=dev),
-                partial=torch.zeros((L,), dtype=f64, device=dev),
-                n_dev=torch.zeros((1,), dtype=torch.int32, device=dev),
+                chi_norms=self._empty((K,), f64), init=self._empty((K, N), c128), guess=self._empty((L, nt - 1), f64),
+                shape=self._empty((L, nt - 1), f64), lambdas=self._empty((L,), f64), opt=self._empty((L, nt - 1), f64),
+                psi_T=self._empty((K, N), c128), g_a=self._empty((L,), f64), partial=self._empty((L,), f64).zero_(),
+                n_dev=self._empty((1,), torch.int32).zero_(),
                 graph=None, graph_key=None,
             )
         chi_store = self._c(chi_store, (K, nt, N))
@@ -753,7 +758,7 @@ class HipKrotovEngine:
     def tau(self, targets, psi_T):
         targets = self._c(targets, (self.K, self.N))
         psi_T = self._c(psi_T, (self.K, self.N))
-        out = torch.empty((self.K,), dtype=torch.complex128, device=self.device)
+        out = self._empty((self.K,), torch.complex128)
         _lib.check(self._lib.kh_tau(self._handle, targets.data_ptr(), psi_T.data_ptr(), out.data_ptr(), self._stream()))
         return out
 
@@ -795,7 +800,7 @@ class HipKrotovEngine:
                     if side is not None and host.shape != (side, side):
                         raise ValueError("e_ops[%d] of objective %d has shape %s, expected %s" % (
                             i, k, host.shape, (side, side)))
-                    uploaded[key] = (torch.from_numpy(host).to(self.device), op)  # keep `op` alive: id() stays unique
+                    uploaded[key] = (self._upload(host), op)  # keep `op` alive: id() stays unique
                 table[k * n_e + i] = uploaded[key][0].data_ptr()
         if tuple(states.shape) != (self.K, self.nt, self.N) or states.dtype != torch.complex128 \
                 or not states.is_contiguous() or states.device != self.device:
@@ -817,8 +822,8 @@ class HipKrotovEngine:
         psi_T = self._c(psi_T, (self.K, self.N))
         c = self._c(c, (self.K,))
         d = self._c(d, (self.K,))
-        chi = torch.empty((self.K, self.N), dtype=torch.complex128, device=self.device)
-        norms = torch.empty((self.K,), dtype=torch.float64, device=self.device)
+        chi = self._empty((self.K, self.N), torch.complex128)
+        norms = self._empty((self.K,), torch.float64)
         _lib.check(self._lib.kh_chi_boundary(
             self._handle, targets.data_ptr(), psi_T.data_ptr(), c.data_ptr(), d.data_ptr(), chi.data_ptr(),
             norms.data_ptr(), self._stream()))

@@ -39,6 +39,7 @@ import pytest
 
 import helpers
 from krotov_amd import configs
+from krotov_amd.engine import HipKrotovEngine
 from oracle import krotov_oracle as ko
 from test_absent_controls import TOL_HILBERT, TOL_LIOUVILLE, _check, _engine_ops, build_problem, compute_sweeps
 
@@ -454,19 +455,19 @@ def _switch_to(dev, s, ref, name, what):
     _check(dict(chi=np.abs(dev.backward() - ref.chi).max()), s.tol, name, what + ', backward')
 
 
-def run_sequence(name, c, monkeypatch):
+def run_sequence(name, c, monkeypatch, device_cls=Device, engine_cls=HipKrotovEngine):
     from krotov_amd import _lib
-    from krotov_amd.engine import HipKrotovEngine
+
 
     for key, value in c.env.items():
         monkeypatch.setenv(key, value)
     p, a, b = inputs(c.prob)
     ref_a, ref_b = oracle(c.prob)
     spec, fmt = p.spec, PROBLEMS[c.prob].fmt
-    eng = HipKrotovEngine(_engine_ops(spec, fmt), np.diff(spec.tlist), is_super=spec.kinds if fmt == 'mixed' else spec.is_super)
+    eng = engine_cls(_engine_ops(spec, fmt), np.diff(spec.tlist), is_super=spec.kinds if fmt == 'mixed' else spec.is_super)
     try:
         assert eng.kernel == c.kernel
-        dev = Device(eng)
+        dev = device_cls(eng)
         _lib.forget_launched_kernels()
         # 1., 2.: A, then B in the same tensors
         out1 = _plain_and_update(dev, a, ref_a, name, '1. A', c)
@@ -543,11 +544,10 @@ def test_engine_reused_with_changed_inputs(name, monkeypatch):
 # ---------------------------------------------------------------------------
 @pytest.mark.gpu
 @pytest.mark.parametrize('name', sorted(GRAPH_CASES))
-def test_captured_graph_reused_with_changed_inputs(name, monkeypatch):
+def test_captured_graph_reused_with_changed_inputs(name, monkeypatch, device_cls=Device, engine_cls=HipKrotovEngine):
     """``forward_update_sharded`` replays a graph captured for (co-state store address, block length): B in the same
     tensors hits the cache, a store at another address re-captures, a plain-loop sweep in between disturbs nothing."""
     from krotov_amd import _lib
-    from krotov_amd.engine import HipKrotovEngine
 
     g = GRAPH_CASES[name]
     for key, value in g.env.items():
@@ -555,10 +555,10 @@ def test_captured_graph_reused_with_changed_inputs(name, monkeypatch):
     p, a, b = inputs(g.prob)
     ref_a, ref_b = oracle(g.prob)
     spec, fmt = p.spec, PROBLEMS[g.prob].fmt
-    eng = HipKrotovEngine(_engine_ops(spec, fmt), np.diff(spec.tlist), is_super=spec.kinds if fmt == 'mixed' else spec.is_super)
+    eng = engine_cls(_engine_ops(spec, fmt), np.diff(spec.tlist), is_super=spec.kinds if fmt == 'mixed' else spec.is_super)
     try:
         assert eng.kernel == g.kernel and eng.nt - 1 > 2 * GRAPH_CHUNK
-        dev = Device(eng)
+        dev = device_cls(eng)
         _lib.forget_launched_kernels()
 
         def replay(s, ref, what, chi=None):
@@ -621,19 +621,18 @@ def test_lindblad_inputs_differ():
 
 
 @pytest.mark.gpu
-def test_lindblad_engine_reused_with_changed_inputs():
+def test_lindblad_engine_reused_with_changed_inputs(device_cls=Device, engine_cls=HipKrotovEngine):
     import torch
 
     from krotov_amd import _lib
-    from krotov_amd.engine import HipKrotovEngine
 
     case_, a, b, ref_a, ref_b = lindblad_inputs()
     name = 'lindblad_form'
     c = types.SimpleNamespace(plain=('kh_lind_sweep_store<1>',), upd='kh_lind_forward_update<1>')
-    eng = HipKrotovEngine(case_.H, case_.dt, c_ops=case_.C)
+    eng = engine_cls(case_.H, case_.dt, c_ops=case_.C)
     try:
         assert eng.kernel == 'lindblad/matrix'
-        dev = Device(eng)
+        dev = device_cls(eng)
         _lib.forget_launched_kernels()
         out1 = _plain_and_update(dev, a, ref_a, name, '1. A', c)
         _plain_and_update(dev, b, ref_b, name, '2. B', c)
@@ -687,19 +686,18 @@ def test_replica_inputs_differ():
 
 
 @pytest.mark.gpu
-def test_replica_engine_reused_with_changed_inputs_and_mask():
+def test_replica_engine_reused_with_changed_inputs_and_mask(device_cls=Device, engine_cls=HipKrotovEngine):
     """All replicas on A; replica 1 off and B in the same tensors: the others are the oracle's B, replica 1's slices of
     every output still hold A's values bit for bit; all on A again: the first run bit for bit.  The same with one sigma
     row per replica (``set_second_order_replicas``), B's rows copied into the same tensor; and off again."""
     import test_replicas as tr
     from krotov_amd import _lib
-    from krotov_amd.engine import HipKrotovEngine
 
     reps, sets = replica_inputs()
     nB, Kr, L = len(reps), reps[0].K, reps[0].L
     name = 'replicas'
     arrays = tr._inputs(reps)
-    eng = HipKrotovEngine(arrays['ops'], arrays['dt'], is_super=reps[0].is_super, replicas=nB)
+    eng = engine_cls(arrays['ops'], arrays['dt'], is_super=reps[0].is_super, replicas=nB)
     plain, upd, so = 'kh_rep_sweep_store<%d>' % L, 'kh_rep_forward_update<%d>' % L, 'kh_rep_forward_update_so<%d>' % L
     outputs = ('fw_T', 'states', 'chi', 'opt', 'psi_T', 'g_a')
 
@@ -739,7 +737,7 @@ def test_replica_engine_reused_with_changed_inputs_and_mask():
 
     try:
         assert eng.kernel == 'replica16/wave'
-        dev = Device(eng, B=nB)
+        dev = device_cls(eng, B=nB)
         _lib.forget_launched_kernels()
         all_a, refs_a = batch_of('aaa')
         all_b, refs_b = batch_of('bbb')
