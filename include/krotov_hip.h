@@ -108,7 +108,9 @@ typedef struct kh_problem {
                                       spectral norms, or NULL (engine then uses
                                       Frobenius norms: safe, slower) */
     double tol;       /* truncation tolerance of the exponential action per
-                         step; 0 -> 2^-53 */
+                         sub-step; tol <= 0 or NaN -> 2^-53.  Every series
+                         table of the engine is built for it (as
+                         kh_series_tables does). */
     double theta_max; /* largest ||A dt|| handled by one Taylor sub-step;
                          0 -> 1.0 */
 } kh_problem;
@@ -154,7 +156,7 @@ typedef struct kh_problem_csr {
     const double *dt;                          /* host [nt-1] */
     const kh_csr *ops;                         /* host [K*(1+L)] */
     const kh_csr *ops_adj;                     /* host [K*(1+L)] */
-    const double *op_norms;                    /* host [K*(1+L)] */
+    const double *op_norms;                    /* host [K*(1+L)]; required: NULL is KH_ERR_INVALID */
     double tol, theta_max;                     /* as in kh_problem */
 } kh_problem_csr;
 
@@ -472,7 +474,7 @@ int kh_last_stats(kh_engine *engine, double stats[4]);
 
 /* The coefficient tables the kernels evaluate exp(f A dt) v with (host only, no GPU needed; for inspection
  * and tests).  The series is sum_j c_j (f A dt)^j v with real c_j; for every degree m <= 64:
- *   theta[m]            largest ||A dt|| the degree serves at tolerance `tol` (tol <= 0: 2^-53),
+ *   theta[m]            largest ||A dt|| the degree serves at tolerance `tol` (tol <= 0 or NaN: 2^-53),
  *   ratios[m*65 + 0]    c_0,   ratios[m*65 + 1] = c_1,   ratios[m*65 + j] = c_j / c_{j-1}  (j = 2..m).
  * real_spectrum = 0: Taylor (c_j = 1/j!, any generator; replaces SciPy's Pade expm behind
  * krotov.propagators.expm, propagators.py:100-117).  real_spectrum = 1: what an engine uses when every

@@ -71,8 +71,13 @@ class HipKrotovEngine:
     objective k uses the first N_k entries of its rows and the engine writes zeros behind them (see
     :func:`krotov_amd.mixed.layout`).  Dense operators only.  When every objective has the same dimension and kind the
     engine is the uniform one, as before.
-        op_norms: optional (K, 1+L) spectral-norm bounds; computed on the host
-            with ``numpy.linalg.norm(., 2)`` per distinct operator when omitted.
+        op_norms: optional (K, 1+L) spectral-norm bounds (true upper bounds; a loose one only costs series terms);
+            computed on the host with ``numpy.linalg.norm(., 2)`` per distinct operator when omitted.  ``'frobenius'``:
+            the library gets no bounds (a NULL ``op_norms``) and computes Frobenius norms itself (on the device; Lindblad
+            form: on the host); ``self.op_norms`` then holds the host's ``numpy.linalg.norm(., 'fro')`` of every operator
+            (0 for an absent one).  Sparse operators: ``kh_problem_csr.op_norms`` is required, so ``'frobenius'`` raises
+            ``ValueError`` before anything touches the GPU.
+        tol: truncation tolerance of the series per sub-step (``<= 0`` or NaN: 2^-53).
         device: torch device (default: current CUDA/HIP device).
         c_ops: Lindblad form (``kh_engine_create_lindblad``, kernel family ``"lindblad/matrix"``): list (K) of lists of
             (d, d) Lindblad operators (``None`` / shorter lists where an objective has fewer; ``[]`` for none).  ``ops``
@@ -94,6 +99,11 @@ class HipKrotovEngine:
 
     def __init__(self, ops, dt, is_super=False, op_norms=None, device=None, tol=0.0, theta_max=0.0, c_ops=None,
                  row_split=None, replicas=None):
+        frobenius = isinstance(op_norms, str)
+        if frobenius and op_norms != 'frobenius':
+            raise ValueError("op_norms: an array of bounds, None or 'frobenius'")
+        if frobenius and any(_is_sparse(op) for row in ops for op in row):
+            raise ValueError("op_norms='frobenius': sparse operators need norm bounds (kh_problem_csr.op_norms is required)")
         _require_gpu()
         self._lib = _lib.load()
         self.replicas = int(replicas) if replicas else 0
@@ -201,6 +211,7 @@ class HipKrotovEngine:
 
     def _create_dense(self, ops, dt, op_norms, tol, theta_max):
         """Dense row-major operators; each distinct object is uploaded once."""
+        frobenius = isinstance(op_norms, str)
         n_ops = self.K * (1 + self.L)
         ptrs = (ctypes.c_void_p * n_ops)()
         norms = np.zeros(n_ops, dtype=np.float64)
@@ -218,16 +229,17 @@ class HipKrotovEngine:
                     self._check_dim(host.shape)
                     t = self._upload(host)
                     self._op_tensors[key] = (t, op)  # keep `op` alive: id() stays unique
-                    norms_cache[key] = float(np.linalg.norm(host, 2)) if host.size else 0.0
+                    norms_cache[key] = float(np.linalg.norm(host, 'fro' if frobenius else 2)) if host.size else 0.0
                 ptrs[idx] = self._op_tensors[key][0].data_ptr()
                 norms[idx] = norms_cache[key]
-        norms = self._norms(norms, op_norms)
+        if not frobenius:
+            norms = self._norms(norms, op_norms)
         pr = _lib.kh_problem()
         pr.K, pr.N, pr.L, pr.nt = self.K, self.N, self.L, self.nt
         pr.is_super = 1 if (not self.mixed and self.is_super) else 0
         pr.dt = dt.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
         pr.ops = ctypes.cast(ptrs, ctypes.POINTER(ctypes.c_void_p))
-        pr.op_norms = norms.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+        pr.op_norms = None if frobenius else norms.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
         pr.tol = float(tol)
         pr.theta_max = float(theta_max)
         if self.replicas:
@@ -253,6 +265,7 @@ class HipKrotovEngine:
         cptrs = (ctypes.c_void_p * max(n_cops, 1))()
         norms = np.zeros(self.K * stride, dtype=np.float64)
         norms_cache = {}
+        frobenius = isinstance(op_norms, str)
 
         def upload(op, hamiltonian):
             key = id(op)
@@ -262,7 +275,9 @@ class HipKrotovEngine:
                 if host.shape != (self.d, self.d):
                     raise ValueError("Lindblad form: every operator must be %d x %d" % (self.d, self.d))
                 self._op_tensors[key] = (self._upload(host), op)
-                if hamiltonian and np.array_equal(host, host.conj().T):
+                if frobenius:
+                    norms_cache[key] = float(np.linalg.norm(host, 'fro'))
+                elif hamiltonian and np.array_equal(host, host.conj().T):
                     ev = np.linalg.eigvalsh(host)
                     norms_cache[key] = 0.5 * float(ev[-1] - ev[0])
                 else:
@@ -276,7 +291,7 @@ class HipKrotovEngine:
             for j, op in enumerate(rows[k]):
                 if op is not None:
                     cptrs[k * n_c + j], norms[k * stride + 1 + self.L + j] = upload(op, False)
-        if op_norms is not None:
+        if op_norms is not None and not frobenius:
             norms = np.ascontiguousarray(np.asarray(op_norms, dtype=np.float64).reshape(-1))
             if norms.size != self.K * stride:
                 raise ValueError("op_norms must have K*(1+L+n_c) entries")
@@ -285,7 +300,7 @@ class HipKrotovEngine:
         pr.dt = dt.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
         pr.ops = ctypes.cast(ptrs, ctypes.POINTER(ctypes.c_void_p))
         pr.c_ops = ctypes.cast(cptrs, ctypes.POINTER(ctypes.c_void_p))
-        pr.op_norms = norms.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+        pr.op_norms = None if frobenius else norms.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
         pr.tol = float(tol)
         pr.theta_max = float(theta_max)
         _lib.check(self._lib.kh_engine_create_lindblad(ctypes.byref(pr), ctypes.byref(self._handle)))

@@ -223,11 +223,12 @@ def _set_dt(obj, dt):
         obj.dt = np.asarray(dt, dtype=np.float64)
 
 
-def series_bounds(obj):
+def series_bounds(obj, norm=None, factor=1.0):
     """(K, 1 + L) norm bounds (n_0, n_l) with theta_n = dt_n (n_0 + sum_l |eps_l[n]| n_l): the formulas of
     ``HipKrotovEngine._create_dense`` (2-norm), ``_create_sparse`` (sqrt(||A||_1 ||A||_inf)) and ``_create_lindblad`` +
     ``kh_engine_create_lindblad`` (Hermitian Hamiltonian part: half the spread of its spectrum; n_0 = 2 ||H0|| +
-    2 sum_j ||C_j||^2, n_l = 2 ||H_l||), restated."""
+    2 sum_j ||C_j||^2, n_l = 2 ||H_l||), restated.  ``norm='frobenius'``: what the library computes when it gets no
+    bounds (``op_norms='frobenius'``); ``factor``: every operator's bound times this (a caller's loose bound)."""
     cache = {}
 
     def two(op):
@@ -244,11 +245,16 @@ def series_bounds(obj):
             return 0.5 * float(ev[-1] - ev[0])
         return two(op)
 
+    def fro(op):
+        return float(np.linalg.norm(np.asarray(op), 'fro'))
+
     def bound(op, fn):
         if op is None:
             return 0.0
+        if norm == 'frobenius':
+            fn = fro
         if id(op) not in cache:
-            cache[id(op)] = (fn(op), op)
+            cache[id(op)] = (factor * fn(op), op)
         return cache[id(op)][0]
 
     if _is_lindblad(obj):
@@ -261,9 +267,10 @@ def series_bounds(obj):
     return np.array([[bound(obj.H0[k], fn)] + [bound(obj.Hc[k][l], fn) for l in range(obj.L)] for k in range(obj.K)])
 
 
-def theta_sequence(obj, pulses=None):
-    """theta[k, n] of a regime problem under ``pulses`` (default: its own guess)."""
-    b = series_bounds(obj)
+def theta_sequence(obj, pulses=None, bounds=None):
+    """theta[k, n] of a regime problem under ``pulses`` (default: its own guess) and the norm bounds ``bounds`` (default:
+    ``series_bounds(obj)``)."""
+    b = series_bounds(obj) if bounds is None else bounds
     eps = np.abs(np.array(obj.pulses if pulses is None else pulses, dtype=np.float64)).reshape(obj.L, -1)
     return regime_dt(obj)[None, :] * (b[:, :1] + b[:, 1:] @ eps)
 
@@ -355,45 +362,88 @@ REGIMES = {'ramp': regime_ramp, 'pulse_ramp': regime_pulse_ramp, 'tiny': lambda 
            'long': regime_long}
 
 
-def series_degree_tables(theta_cap=2.0, defect=3e-3):
-    """{'taylor' | 'real' | 'defect': theta thresholds per degree} from the library's exported host code (no GPU)."""
+def series_degree_tables(theta_cap=2.0, defect=3e-3, tol=0.0):
+    """{'taylor' | 'real' | 'defect': theta thresholds per degree} at the truncation tolerance ``tol`` (0: the engine's
+    default, 2^-53) from the library's exported host code (no GPU)."""
     import ctypes
 
     from krotov_amd import _lib
 
     lib = _lib.load()
     out = {}
-    for name, call in (('taylor', lambda th, ra: lib.kh_series_tables(0, 0.0, th, ra)),
-                       ('real', lambda th, ra: lib.kh_series_tables(1, 0.0, th, ra)),
-                       ('defect', lambda th, ra: lib.kh_series_tables_defect(0.0, theta_cap, defect, th, ra))):
+    for name, call in (('taylor', lambda th, ra: lib.kh_series_tables(0, tol, th, ra)),
+                       ('real', lambda th, ra: lib.kh_series_tables(1, tol, th, ra)),
+                       ('defect', lambda th, ra: lib.kh_series_tables_defect(tol, theta_cap, defect, th, ra))):
         th, ra = (ctypes.c_double * 65)(), (ctypes.c_double * (65 * 65))()
         assert call(th, ra) == 0
         out[name] = np.array(th)
     return out
 
 
-def series_coefficients(theta_cap=2.0):
-    """(theta_b[m], c[m][j]) of the real-spectrum (Chebyshev-form) series with the cap ``theta_cap`` from the library's
-    exported host code: the polynomial of degree m is sum_j c[m][j] Z^j with Z = f A dt (``ratios``: c_0, c_1, c_j / c_{j-1})."""
+def _coefficients_of_ratios(ratios):
+    """c[m][j] from ``ratios`` (c_0, c_1, c_j / c_{j-1}).  The rows of the degrees that stay with Taylor's coefficients are
+    filled up to j = 64: the polynomial of degree m is c[m][:m + 1]."""
+    ratios = np.array(ratios).reshape(65, 65)
+    coeff = np.zeros((65, 65))
+    coeff[:, :2] = ratios[:, :2]
+    for j in range(2, 65):
+        coeff[:, j] = coeff[:, j - 1] * ratios[:, j]
+    return coeff
+
+
+def series_coefficients(theta_cap=2.0, tol=0.0, defect=0.0):
+    """(theta_b[m], c[m][j]) of the real-spectrum (Chebyshev-form) series with the cap ``theta_cap`` (and the margin for a
+    Hermitian ``defect``) at the tolerance ``tol`` from the library's exported host code: the polynomial of degree m is
+    sum_{j <= m} c[m][j] Z^j with Z = f A dt (``ratios``: c_0, c_1, c_j / c_{j-1})."""
     import ctypes
 
     from krotov_amd import _lib
 
     lib = _lib.load()
     th, ra = (ctypes.c_double * 65)(), (ctypes.c_double * (65 * 65))()
-    assert lib.kh_series_tables_defect(0.0, theta_cap, 0.0, th, ra) == 0
-    ratios = np.array(ra).reshape(65, 65)
+    assert lib.kh_series_tables_defect(tol, theta_cap, defect, th, ra) == 0
+    return np.array(th), _coefficients_of_ratios(ra)
+
+
+def series_taylor_coefficients(tol=0.0):
+    """(theta[m], c[m][j] = 1 / j!) of the Taylor tables (``kh_series_tables(0, tol, ...)``)."""
+    import ctypes
+
+    from krotov_amd import _lib
+
+    th, ra = (ctypes.c_double * 65)(), (ctypes.c_double * (65 * 65))()
+    assert _lib.load().kh_series_tables(0, tol, th, ra) == 0
+    return np.array(th), _coefficients_of_ratios(ra)
+
+
+def series_tables_odd(tol=0.0):
+    """(theta[m], c[m][j]) of ``kh_series_tables_odd``: the table the two-terms-per-phase kernels get where the series
+    is the exactly-Hermitian Chebyshev form.  The export holds c_0 and the rows {r1_p, r2_p} (r1_0 = c_1, r2_0 = c_2;
+    r1_p = c_{2p+1} / c_{2p}, r2_p = c_{2p+2} / c_{2p} for p >= 1; an odd degree m = 2P - 1 ends with {r1_{P-1}, 0}); the
+    coefficients are rebuilt from them up to the degree."""
+    import ctypes
+
+    from krotov_amd import _lib
+
+    th, c0, rows = (ctypes.c_double * 65)(), (ctypes.c_double * 65)(), (ctypes.c_double * (65 * 32 * 2))()
+    assert _lib.load().kh_series_tables_odd(tol, th, c0, rows) == 0
+    c0, rows = np.array(c0), np.array(rows).reshape(65, 32, 2)
     coeff = np.zeros((65, 65))
-    coeff[:, :2] = ratios[:, :2]
-    for j in range(2, 65):
-        coeff[:, j] = coeff[:, j - 1] * ratios[:, j]
+    for m in range(1, 65):
+        coeff[m, 0] = c0[m]
+        for p in range((m + 1) // 2):
+            even = 1.0 if p == 0 else coeff[m, 2 * p]
+            coeff[m, 2 * p + 1] = rows[m, p, 0] * even
+            if 2 * p + 2 <= m:
+                coeff[m, 2 * p + 2] = rows[m, p, 1] * even
     return np.array(th), coeff
 
 
-def series_polynomial(c, Z):
-    """sum_j c[j] Z^j (Horner) for a matrix or an array of scalars ``Z``."""
-    Z = np.asarray(Z, dtype=np.complex128)
-    one = np.eye(Z.shape[0], dtype=np.complex128) if Z.ndim == 2 else np.ones_like(Z)
+def series_polynomial(c, Z, dtype=np.complex128):
+    """sum_j c[j] Z^j (Horner) for a matrix or an array of scalars ``Z`` (``dtype``: ``numpy.clongdouble`` where the
+    rounding of the evaluation itself must stay below a truncation error that is being measured)."""
+    Z = np.asarray(Z, dtype=dtype)
+    one = np.eye(Z.shape[0], dtype=dtype) if Z.ndim == 2 else np.ones_like(Z)
     mul = (lambda a, b: a @ b) if Z.ndim == 2 else (lambda a, b: a * b)
     out = c[-1] * one
     for cj in c[-2::-1]:
@@ -477,18 +527,19 @@ def regime_oracle(obj):
     return spec_to_oracle(obj)
 
 
-def regime_engine(obj, theta_max=0.0):
-    """The engine of a regime problem (dense, CSR, mixed or Lindblad form)."""
+def regime_engine(obj, theta_max=0.0, tol=0.0, op_norms=None):
+    """The engine of a regime problem (dense, CSR, mixed or Lindblad form); ``tol`` and ``op_norms`` as
+    ``HipKrotovEngine`` takes them."""
     from krotov_amd import configs
     from krotov_amd.engine import HipKrotovEngine
 
     if obj.fmt == 'lindblad':
-        return HipKrotovEngine(obj.H, obj.dt, c_ops=obj.C, theta_max=theta_max)
+        return HipKrotovEngine(obj.H, obj.dt, c_ops=obj.C, theta_max=theta_max, tol=tol, op_norms=op_norms)
     if obj.fmt == 'csr':
         ops = configs.sparse_ops(obj)
     else:
         ops = [[obj.H0[k]] + [obj.Hc[k][l] for l in range(obj.L)] for k in range(obj.K)]
-    return HipKrotovEngine(ops, regime_dt(obj), is_super=obj.is_super, theta_max=theta_max)
+    return HipKrotovEngine(ops, regime_dt(obj), is_super=obj.is_super, theta_max=theta_max, tol=tol, op_norms=op_norms)
 
 
 class MemoExpm:

@@ -125,12 +125,13 @@ def oracle_sweeps(name, b):
     return fw, chi, upd
 
 
-def run_engine(reps, mask=None, out=None, theta_max=0.0):
+def run_engine(reps, mask=None, out=None, theta_max=0.0, tol=0.0, op_norms=None):
     """Forward, backward and update sweep of a replica engine over `reps`; host arrays (psi0, chi, opt, psi_T, g_a)."""
     from krotov_amd.engine import HipKrotovEngine
 
     a = _inputs(reps)
-    eng = HipKrotovEngine(a['ops'], a['dt'], is_super=reps[0].is_super, replicas=len(reps), theta_max=theta_max)
+    eng = HipKrotovEngine(a['ops'], a['dt'], is_super=reps[0].is_super, replicas=len(reps), theta_max=theta_max, tol=tol,
+                          op_norms=op_norms)
     try:
         assert eng.kernel == 'replica16/wave'
         if mask is not None:

@@ -70,7 +70,7 @@ def _nans(shape, dtype):
     return torch.full(shape, fill, dtype=dtype, device='cuda')
 
 
-def run_so(reps, sigma, mask=None, nan_outputs=False, first_order_too=False, then_first_order=False):
+def run_so(reps, sigma, mask=None, nan_outputs=False, first_order_too=False, then_first_order=False, tol=0.0):
     """Forward sweep with storage (fw_prev), backward sweep and second-order update sweep of a replica engine over
     `reps`.  Host arrays: dict(opt, psi_T, g_a, fw_store, init[, first: (opt, psi_T, g_a) of the first-order sweep run
     before][, back: the same of a first-order sweep run after three NULLs])."""
@@ -80,7 +80,7 @@ def run_so(reps, sigma, mask=None, nan_outputs=False, first_order_too=False, the
 
     a = _inputs(reps)
     nB, Kr, N, L, nt = len(reps), reps[0].K, reps[0].N, reps[0].L, len(reps[0].tlist)
-    eng = HipKrotovEngine(a['ops'], a['dt'], is_super=reps[0].is_super, replicas=nB)
+    eng = HipKrotovEngine(a['ops'], a['dt'], is_super=reps[0].is_super, replicas=nB, tol=tol)
     try:
         assert eng.kernel == 'replica16/wave'
         if mask is not None:
