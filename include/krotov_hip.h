@@ -95,7 +95,10 @@ typedef struct kh_problem {
     int32_t K;        /* objectives handled by this engine (this GPU's shard) */
     int32_t N;        /* state dimension */
     int32_t L;        /* controls: at most 32 (KH_ERR_UNSUPPORTED beyond); the register-resident kernel families
-                         take up to 8 (4, 2 for some), with more the generic kernels run */
+                         take up to 8 (4, 2 for some), with more the generic kernels run.
+                         L = 0 (no controls) is accepted by every constructor except kh_engine_create_replicas
+                         (KH_ERR_UNSUPPORTED: 1..4 controls): the plain sweeps run with pulses_dev == NULL, while
+                         kh_forward_update, kh_update_begin and kh_set_parametrization answer KH_ERR_INVALID */
     int32_t nt;       /* len(tlist); nt-1 intervals */
     int32_t is_super; /* 0: Hilbert space, eqm factor -i (propagators.py:94);
                          1: Liouville space, factor 1 (propagators.py:96-98),
@@ -544,7 +547,8 @@ int kh_debug_occupy(kh_engine *engine, int32_t workgroups, double milliseconds, 
  * only, no GPU needed); which = 0: those this process has launched so far; which = 2: forget that list (returns 0).  Writes at most cap - 1 characters and a
  * terminating 0 into buf (may be NULL); returns the buffer size the whole list needs.  With the environment variable
  * KH_LAUNCH_LOG=<file> every process also appends an instantiation's name to that file at its first launch:
- * tests/test_zz_kernel_coverage.py fails when an instantiation was never launched by an oracle-comparing test. */
+ * tests/test_zz_kernel_coverage.py fails when an instantiation was never launched by an oracle-comparing test.  The
+ * adjoint-side pre-passes in front of an update sweep are listed too ("kh_gen_adjoint_side", "kh_coop_adjoint_side"). */
 int kh_debug_launched(int32_t which, char *buf, int32_t cap);
 
 #ifdef __cplusplus

@@ -2004,7 +2004,8 @@ static int with_coop(int cols, int ks, F &&f) {
 // update sweep that reads its sums from there
 static int gen_adjoint_side(kh_engine *e, const cplx *chi_store, int L, hipStream_t st) {
     const dim3 grid((unsigned)(e->K * L), (unsigned)((e->nt + KH_GEN_ADJ_POINTS - 1) / KH_GEN_ADJ_POINTS));
-    kh_gen_adjoint_side<<<grid, KH_GEN_ADJ_THREADS, 0, st>>>(e->d_ops_bw, chi_store, e->d_gen_adj, e->K, e->N, L, e->nt);
+    // (through the launch registry: a test can tell that the pre-pass ran)
+    launch_plain<kh_gen_adjoint_side>(grid, dim3(KH_GEN_ADJ_THREADS), 0, st, e->d_ops_bw, chi_store, e->d_gen_adj, e->K, e->N, L, e->nt);
     KH_HIP(hipGetLastError());
     return KH_OK;
 }
@@ -2108,8 +2109,9 @@ static int launch_coop_update(kh_engine *e, const KhSweepArgs &p, const KhUpdate
         if (e->d_coop_sq_fw != nullptr && e->plan.coop_adj && !so && e->L == 1) {
             // V = H_1^+ X over the whole co-state store, block-sparse on the matrix cores (kh_coop.h)
             const long long M = (long long)e->K * e->nt;
-            kh_coop_adjoint_side<<<(unsigned)((M + 63) / 64), KH_COOP_ADJ_THREADS, 0, st>>>(e->coop_adj_op, e->d_coop_adj_nz, u.chi_store,
-                                                                                          e->d_coop_adj, e->N, e->plan.coop_G, M);
+            // (through the launch registry: a test can tell that the pre-pass ran)
+            launch_plain<kh_coop_adjoint_side>(dim3((unsigned)((M + 63) / 64)), dim3(KH_COOP_ADJ_THREADS), 0, st, e->coop_adj_op,
+                                               e->d_coop_adj_nz, u.chi_store, e->d_coop_adj, e->N, e->plan.coop_G, M);
             KH_HIP(hipGetLastError());
             u.adj_store = e->d_coop_adj;
             if (ex.world == 1 && e->sw.coop_single)

@@ -6,7 +6,7 @@ scaled and per-objective operators; objectives without one of their controls; Hi
 
 Test infrastructure (it imports ``oracle/``): run on a GPU box,
 
-    python tests/fuzz_parity.py [--seconds 300] [--seed 1] [--cases 0] [--level sweeps|optimize] [--regimes] [--drop-any] [--nonselfadjoint]
+    python tests/fuzz_parity.py [--seconds 300] [--seed 1] [--cases 0] [--level sweeps|optimize] [--regimes] [--drop-any] [--nonselfadjoint] [--short-grids]
 
 prints one line per case (kernel, shape, largest deviation) and a summary; exit code 1 if any case is off by more than
 the tolerance of tests/test_hip_parity.py (1e-12, 1e-11 in Liouville space).  ``tests/test_hip_parity.py::
@@ -17,7 +17,9 @@ Lindblad-form and mixed-dimension problems; it draws from a generator of its own
 default stream never does -- with one control, with one objective, from objective 0, a middle objective or the last one
 (tests/test_absent_controls.py) -- again decided by a generator of its own.  ``--nonselfadjoint`` (sweeps level) replaces a
 random subset of the controls of the drawn ``config_c5`` problems by operators that are not Hermitian (``lower``, ``ladder``,
-``anti``: tests/test_nonselfadjoint_controls.py), by a third generator of its own.
+``anti``: tests/test_nonselfadjoint_controls.py), by a third generator of its own.  ``--short-grids`` (sweeps level) cuts
+every drawn problem's grid to nt = 2 or 3 with update shapes, guess pulses and step widths of ``helpers.grid_ends`` (the
+drawn ones vanish at both ends of the grid: tests/test_grid_ends.py), decided by a fourth generator of its own.
 """
 import argparse
 import os
@@ -180,6 +182,17 @@ def draw_regime(rng, spec, tag, fmt):
     return out, '%s %s theta_max=%g' % (tag, regime, theta_max), theta_max
 
 
+def draw_short_grid(rng, spec, tag, fmt):
+    """``--short-grids``: the drawn problem on one or two intervals (nt = 2, 3) as ``helpers.grid_ends`` builds it; ``rng`` is
+    NOT the generator of :func:`draw`.  Returns the regime problem, its tag and the theta_max it was built for."""
+    nt = int(rng.choice([2, 3]))
+    theta_max = float(rng.choice([1.0, 1.0, 4.0]))
+    spec.tlist = np.linspace(spec.tlist[0], spec.tlist[-1], nt)
+    obj = hp.grid_ends(hp.explicit(spec, 'dense' if fmt is None else fmt), theta_max)
+    hp.grid_ends_witness(obj, theta_max)
+    return obj, '%s short nt=%d theta_max=%g' % (tag, nt, theta_max), theta_max
+
+
 def run_regime_case(obj, theta_max):
     """:func:`run_case` for a regime problem (explicit interval values, any operator form)."""
     prob = hp.regime_oracle(obj)
@@ -288,7 +301,7 @@ def run_optimize_case(spec, fmt, rng):
 
 
 def fuzz(seed, seconds=None, cases=None, verbose=True, level='sweeps', regimes=False, drop_any=False, stats=None,
-         nonselfadjoint=False):
+         nonselfadjoint=False, short_grids=False):
     """Run random cases until `seconds` have passed or `cases` are done; returns (number run, list of failures).
     ``stats``: a dict that receives how many cases had an absent control (``'absent'``) and how many of those had one
     control (``'absent_L1'``), and how many a control that is not self-adjoint (``'nonselfadjoint'``)."""
@@ -296,6 +309,7 @@ def fuzz(seed, seconds=None, cases=None, verbose=True, level='sweeps', regimes=F
     rng_regimes = np.random.default_rng([int(seed), 0x7e91]) if regimes else None  # (the default stream stays untouched)
     rng_drop = np.random.default_rng([int(seed), 0xd709]) if drop_any and level == 'sweeps' else None  # (likewise)
     rng_nsa = np.random.default_rng([int(seed), 0x5ad1]) if nonselfadjoint and level == 'sweeps' else None  # (likewise)
+    rng_short = np.random.default_rng([int(seed), 0x2e9d]) if short_grids and level == 'sweeps' else None  # (likewise)
     counts = {'absent': 0, 'absent_L1': 0}
     if rng_nsa is not None:  # (the key only where it was asked for: the older tests compare the whole dict)
         counts['nonselfadjoint'] = 0
@@ -320,7 +334,11 @@ def fuzz(seed, seconds=None, cases=None, verbose=True, level='sweeps', regimes=F
         tol = (1e-10 if spec.is_super else 1e-11) if level == 'optimize' else (1e-11 if spec.is_super else 1e-12)
         tol2 = 1e-9  # second order (the kernel tag ends in '2nd'): sigma's A is a ratio of small differences (1e-9)
         try:
-            if rng_regimes is not None and level == 'sweeps':
+            if rng_short is not None:
+                obj, tag, theta_max = draw_short_grid(rng_short, spec, tag, fmt)
+                tol = 1e-11 if bool(np.any(obj.is_super)) else 1e-12
+                kernel, dev = run_regime_case(obj, theta_max)
+            elif rng_regimes is not None and level == 'sweeps':
                 obj, tag, theta_max = draw_regime(rng_regimes, spec, tag, fmt)
                 liouville = obj.fmt == 'lindblad' or bool(np.any(obj.is_super))
                 tol = 1e-11 if liouville or ' ramp ' in tag else 1e-12  # (as tests/test_series_regimes.py)
@@ -365,7 +383,10 @@ if __name__ == '__main__':
     ap.add_argument('--nonselfadjoint', action='store_true',
                     help="a random subset of the controls of the drawn config_c5 problems becomes lower / ladder / anti variants "
                          "(not Hermitian); decided by a separate generator (sweeps level)")
+    ap.add_argument('--short-grids', action='store_true',
+                    help="every drawn problem on nt = 2 or 3 grid points with shapes, pulses and step widths that do not vanish "
+                         "at the ends (helpers.grid_ends); decided by a separate generator (sweeps level)")
     a = ap.parse_args()
     n, bad = fuzz(a.seed, seconds=None if a.cases else a.seconds, cases=a.cases or None, level=a.level, regimes=a.regimes,
-                  drop_any=a.drop_any, nonselfadjoint=a.nonselfadjoint)
+                  drop_any=a.drop_any, nonselfadjoint=a.nonselfadjoint, short_grids=a.short_grids)
     sys.exit(1 if bad else 0)

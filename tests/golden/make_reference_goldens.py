@@ -354,7 +354,19 @@ REF_CASES = {
     # (config_c2_liouville is no use here: one of its three states is invariant, chi_k(T) = 0, and the reference
     # divides by its norm -- NaN pulses)
     'ref_c4_small_hs': (lambda c: _with_chi(c.config_c4(d=5, nt=201, n_logical=2), 'hs'), 5),
+    # two- and three-point grids: one and two intervals (tests/helpers.py: update_shape = 1, a guess that is non-zero on
+    # the grid -- the configs' own vanish at both ends)
+    'ref_c5_nt2': (lambda c: _short_grid('ref_c5_nt2', c), 5),
+    'ref_c5_nt3': (lambda c: _short_grid('ref_c5_nt3', c), 5),
+    'ref_c3_nt2': (lambda c: _short_grid('ref_c3_nt2', c), 5),
 }
+
+
+def _short_grid(name, c):
+    sys.path.insert(0, os.path.dirname(HERE))
+    import helpers
+
+    return helpers.short_grid_spec(name, c)
 
 
 def _with_chi(spec, chi):

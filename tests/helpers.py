@@ -17,6 +17,27 @@ DUMP_CONTINUE_CASES = {
 }
 
 
+# the reference-loop fixtures on two- and three-point grids (tests/golden/make_reference_goldens.py makes them; the GPU and
+# the oracle tests rebuild the same specs): name -> (builder of krotov_amd.configs, guess amplitude)
+SHORT_GRID_CASES = {
+    'ref_c5_nt2': (lambda c: c.config_c5(K=6, N=16, nt=2, L=1), 0.5),
+    'ref_c5_nt3': (lambda c: c.config_c5(K=6, N=16, nt=3, L=1), 0.5),
+    'ref_c3_nt2': (lambda c: c.config_c3(nt=2), 0.3),
+}
+
+
+def short_grid_spec(name, configs):
+    """A spec of SHORT_GRID_CASES: ``update_shape = 1`` and a guess control that is non-zero on the whole grid, amplitude x
+    (0.4 + 0.6 t / T) -- the configs' own flat-tops and guesses vanish at both ends of the grid, which on one or two
+    intervals leaves the update nothing to do."""
+    builder, amplitude = SHORT_GRID_CASES[name]
+    spec = builder(configs)
+    T = float(spec.tlist[-1])
+    spec.update_shape = lambda t: 1.0
+    spec.controls = [lambda t, args, l=l: amplitude * (1.0 + 0.5 * l) * (0.4 + 0.6 * t / T) for l in range(spec.L)]
+    return spec
+
+
 def golden(name):
     return np.load(os.path.join(GOLDEN, name + '.npz'))
 
@@ -313,17 +334,18 @@ def regime_ramp(obj, theta_max):
     return new
 
 
-def regime_pulse_ramp(obj, theta_max, periods=1, zeros=True):
+def regime_pulse_ramp(obj, theta_max, periods=1, zeros=True, steps=None):
     """Uniform grid (dt x PULSE_RAMP_DT: the drift alone sits at a low degree); every guess pulse is replaced by
     a_n (0.3 + |guess|) with a_n such that theta_n follows ``ramp_profile`` (a_n >= PULSE_RAMP_FLOOR max a where the drift
     alone is beyond the level), and is exactly 0.0 on the first and the last interval and on the first interval of the way
-    down that needs no sub-steps."""
+    down that needs no sub-steps.  ``zeros='inner'``: only the latter; ``steps``: step-width factors <= 1, repeated along
+    the grid (a non-uniform grid under the same theta_n)."""
     new = explicit(obj)
     dt = regime_dt(new)
     M = len(dt)
     if M < RAMP_MIN_INTERVALS * periods:
         raise ValueError("a ramp needs at least %d intervals" % (RAMP_MIN_INTERVALS * periods))
-    _set_dt(new, dt * PULSE_RAMP_DT)
+    _set_dt(new, dt * PULSE_RAMP_DT * (1.0 if steps is None else np.resize(np.asarray(steps, dtype=np.float64), M)))
     new.pulses = [0.3 + np.abs(p) for p in new.pulses]
     k, rate = _largest(new)
     drift = series_bounds(new)[k, 0]
@@ -335,7 +357,7 @@ def regime_pulse_ramp(obj, theta_max, periods=1, zeros=True):
     new.pulses = [a * p for p in new.pulses]
     if zeros:
         falling = [n for n in range(1, M) if profile[n] < 1.0 <= profile[n - 1]]  # (one per period)
-        for n in [0, M - 1] + falling:
+        for n in ([] if zeros == 'inner' else [0, M - 1]) + falling:
             for p in new.pulses:
                 p[n] = 0.0
     return new
@@ -360,6 +382,75 @@ def regime_long(obj, theta_max):
 
 REGIMES = {'ramp': regime_ramp, 'pulse_ramp': regime_pulse_ramp, 'tiny': lambda obj, theta_max: regime_tiny(obj),
            'long': regime_long}
+
+
+# ---- the ends of the interval pipeline (tests/test_grid_ends.py, tests/fuzz_parity.py --short-grids)
+GRID_ENDS_SHORT = 3  # up to here: interval values of this module's own, one sub-step per interval
+# theta_n / theta_max of the short grids (4 ... 10 intervals, the graph-replay cases: the last one repeated along the grid)
+GRID_ENDS_THETA = {1: (0.5,), 2: (0.3, 0.8), 3: (0.25, 0.9, 0.45), 4: (0.25, 0.9, 0.45, 0.7)}
+GRID_ENDS_STEPS = (1.0, 0.6, 0.85, 0.55, 0.7)  # step-width factors of the long grids (max / min = 1.8)
+
+
+def grid_ends_pulses(obj, M):
+    """Guess pulses of a short grid: eps_l[n] = a_l c[l, n] with 0.4 <= |c| <= 1 different on every interval and for every
+    control, the sign changing from interval to interval and from control to control; a_l puts the L control terms together
+    at the drift's norm bound (the objective with the largest drift bound), whatever the operators' scale."""
+    b = series_bounds(obj)
+    k = int(np.argmax(b[:, 0]))
+    n, out = np.arange(M), []
+    for l in range(obj.L):
+        a = b[k, 0] / (obj.L * b[k, 1 + l]) if b[k, 1 + l] > 0.0 and b[k, 0] > 0.0 else 1.0
+        out.append(a * (-1.0) ** (l + n) * (0.4 + 0.1 * ((3 * l + 5 * n + 1) % 7)))
+    return out
+
+
+def grid_ends(obj, theta_max):
+    """The problem of ``obj`` (built with nt = I + 1) for a test of the ends of the sweeps' software pipeline:
+
+    * update shapes S_l[n] = 0.2 + 0.8 (n + 1) / I -- the fixtures' flat-tops are 0 at both ends, which on one to three
+      intervals is everywhere;
+    * I <= 3 (and up to 10, for the graph-replay cases): ``grid_ends_pulses`` and step widths such that theta_n / theta_max
+      of the objective with the largest theta is GRID_ENDS_THETA[I] (one sub-step; the steps differ by more than a factor
+      1.5);
+    * I >= 11: ``regime_pulse_ramp`` on a non-uniform grid (GRID_ENDS_STEPS), one period per 64 intervals (one up to
+      I = 127: |eps| spans decades inside every restart window), exactly 0.0 on its inner intervals only -- not on the first
+      and the last one."""
+    new = explicit(obj)
+    M = len(regime_dt(new))
+    if M < RAMP_MIN_INTERVALS:
+        new.pulses = grid_ends_pulses(new, M)
+        _set_dt(new, theta_max * np.resize(GRID_ENDS_THETA[min(M, 4)], M) / _largest(new)[1])
+    else:
+        new = regime_pulse_ramp(new, theta_max, periods=max(1, M // 64), zeros='inner', steps=GRID_ENDS_STEPS)
+    new.shapes = [0.2 + 0.8 * (np.arange(M) + 1.0) / M for _ in range(new.L)]
+    return new
+
+
+def grid_ends_witness(obj, theta_max):
+    """Assert the input conditions of a ``grid_ends`` problem (host only); returns theta[k, n]."""
+    pulses, dt = np.array(obj.pulses, dtype=np.float64).reshape(obj.L, -1), regime_dt(obj)
+    M = len(dt)
+    assert all(np.array_equal(s, 0.2 + 0.8 * (np.arange(M) + 1.0) / M) and np.all(s > 0.2) for s in obj.shapes)
+    assert len(obj.shapes) == obj.L and pulses.shape == (obj.L, M)
+    theta = theta_sequence(obj)
+    if M >= 2:
+        assert dt.max() / dt.min() >= 1.5
+    if M < RAMP_MIN_INTERVALS:
+        assert np.all(np.abs(pulses) >= 0.1 * np.abs(pulses).max())
+        for l in range(obj.L):
+            assert len(set(pulses[l].tolist())) == M or M > GRID_ENDS_SHORT  # differ between intervals
+        assert len({tuple(p.tolist()) for p in pulses}) == obj.L  # and between controls
+        top = theta.max(axis=0)
+        assert np.all(top >= 0.1 * theta_max * (1 - 1e-12)) and np.all(top <= 0.9 * theta_max * (1 + 1e-12))
+    else:
+        assert np.all(pulses[:, 0] != 0.0) and np.all(pulses[:, -1] != 0.0)
+        assert np.count_nonzero(pulses[0] == 0.0) >= 1  # (the inner zero stays)
+        for start in range(0, M, 64):
+            w = np.abs(pulses[0, start:start + 64])
+            w = w[w > 0]
+            if len(w) >= 32:
+                assert np.log10(w.max() / w.min()) >= 2.0, "pulse spans %.1f decades" % np.log10(w.max() / w.min())
+    return theta
 
 
 def series_degree_tables(theta_cap=2.0, defect=3e-3, tol=0.0):

@@ -12,6 +12,7 @@ import krotov_amd
 from krotov_amd import configs
 from oracle import krotov_oracle as ko
 
+import helpers
 from helpers import CHI, golden, oracle_controls, oracle_optimize, spec_to_oracle
 
 pytestmark = pytest.mark.gpu
@@ -959,6 +960,10 @@ GOLDEN_CASES = {
     'ref_c5_n64': lambda: configs.config_c5(K=8, N=64, nt=401, L=1),
     # chis_hs from the reference's own loop (functionals.py:389-437): chi_k(T) = w/2K (rho_tgt - rho(T))
     'ref_c4_small_hs': lambda: _with_chi(configs.config_c4(d=5, nt=201, n_logical=2), 'hs'),
+    # one and two intervals (tests/helpers.py: SHORT_GRID_CASES)
+    'ref_c5_nt2': lambda: helpers.short_grid_spec('ref_c5_nt2', configs),
+    'ref_c5_nt3': lambda: helpers.short_grid_spec('ref_c5_nt3', configs),
+    'ref_c3_nt2': lambda: helpers.short_grid_spec('ref_c3_nt2', configs),
 }
 
 
@@ -1513,6 +1518,12 @@ def _two_rank_spec(case):
         spec = configs.config_c5(K=6, N=64, nt=61, L=1)
         spec.chi = 'sm'
         return spec
+    if case == 'c5nt3':  # two intervals (the peer-window epochs advance once per interval), constant update shape and a
+        spec = configs.config_c5(K=6, N=64, nt=3, L=1)  # guess that is non-zero on the grid: the update is no no-op
+        spec.chi = 'sm'
+        spec.update_shape = lambda t: 1.0
+        spec.controls = [lambda t, args: 0.5 * (0.4 + 0.6 * t * 2000.0)]
+        return spec
     if case == 'c3':  # small problem: the one-wave-per-objective kernels, 2 + 2 objectives
         return configs.config_c3(nt=301)
     if case == 'k1100':  # 550 objectives per rank: not co-resident, so no in-kernel exchange -- the peer windows
@@ -1651,7 +1662,7 @@ def _two_rank_worker(rank, world, port, queue, case='c5'):
         dist.destroy_process_group()
 
 
-@pytest.mark.parametrize('case', ['c5', 'c3', 'c4', 'c4so', 'c4k25', 'k1100', 'k1100ens', 'n80', 'L6', 'sparse'])
+@pytest.mark.parametrize('case', ['c5', 'c5nt3', 'c3', 'c4', 'c4so', 'c4k25', 'k1100', 'k1100ens', 'n80', 'L6', 'sparse'])
 def test_two_ranks_sharded_on_one_gpu(case):
     import socket
 
@@ -1677,13 +1688,15 @@ def test_two_ranks_sharded_on_one_gpu(case):
         ref = oracle_optimize(spec, 2, sigma=SigmaA(0.0, 2e-3))
     else:
         ref = oracle_optimize(spec, 2)
-    tol = 1e-12 if case in ('c5', 'c3', 'k1100', 'k1100ens', 'n80', 'L6', 'sparse') else 1e-11  # (stiff Liouvillian, as in test_sweeps_match_oracle)
+    tol = 1e-12 if case in ('c5', 'c5nt3', 'c3', 'k1100', 'k1100ens', 'n80', 'L6', 'sparse') else 1e-11  # (stiff Liouvillian, as in test_sweeps_match_oracle)
     for _, pulses, tau, used_p2p, kernel, _diag in out:
         assert np.abs(pulses - ref['all_pulses']).max() < tol * max(1.0, np.abs(ref['all_pulses']).max())
         assert np.abs(tau - ref['tau_vals']).max() < tol
-        assert kernel == {'c5': 'tile64q2/512', 'c3': 'mini4/wave', 'k1100': 'tile64/stream', 'k1100ens': 'ens64/mfma',
+        assert kernel == {'c5': 'tile64q2/512', 'c5nt3': 'tile64q2/512', 'c3': 'mini4/wave', 'k1100': 'tile64/stream', 'k1100ens': 'ens64/mfma',
                           'n80': 'tile128/512', 'L6': 'tile64x/512', 'sparse': 'ell/csr'}.get(case, 'coop16/mfma')
     assert np.array_equal(out[0][1], out[1][1])
+    if case == 'c5nt3':  # (both intervals move in the first iteration)
+        assert np.abs(ref['all_pulses'][1] - ref['all_pulses'][0]).min() > 1e-6
     # the path this test is here for: the sums crossed the ranks inside the persistent kernels, through the
     # peer-mapped windows -- not through the per-interval fallback
     if case == 'k1100':

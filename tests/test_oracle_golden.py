@@ -15,6 +15,7 @@ import pytest
 from krotov_amd import configs
 from oracle import krotov_oracle as ko
 
+import helpers
 from helpers import CHI, golden, oracle_controls, oracle_optimize, spec_to_oracle
 
 
@@ -167,6 +168,10 @@ REF_CASES = {
     'ref_c5_small_L3': lambda: configs.config_c5(K=5, N=12, nt=151, L=3, distinct=True),
     'ref_c5_n64': lambda: configs.config_c5(K=8, N=64, nt=401, L=1),
     'ref_c4_small_hs': lambda: _with_chi(configs.config_c4(d=5, nt=201, n_logical=2), 'hs'),
+    # one and two intervals (tests/helpers.py: SHORT_GRID_CASES)
+    'ref_c5_nt2': lambda: helpers.short_grid_spec('ref_c5_nt2', configs),
+    'ref_c5_nt3': lambda: helpers.short_grid_spec('ref_c5_nt3', configs),
+    'ref_c3_nt2': lambda: helpers.short_grid_spec('ref_c3_nt2', configs),
 }
 
 
@@ -195,6 +200,9 @@ def test_against_real_reference_loop(name, use_scipy):
     assert np.abs(out['all_pulses'] - g['all_pulses']).max() < tol * scale
     assert np.abs(out['tau_vals'] - g['tau_vals']).max() < tol
     assert np.abs(out['fw_T'] - g['fw_T']).max() < tol
+    if name in helpers.SHORT_GRID_CASES:  # one or two intervals: the first iteration moves the pulse on every one of them
+        assert g['all_pulses'].shape[-1] == len(spec.tlist) - 1 <= 2
+        assert np.abs(g['all_pulses'][1] - g['all_pulses'][0]).min() > 1e-6
 
 
 def test_kat_parallelization_transmon5():

@@ -231,14 +231,19 @@ _references = {}
 def reference(row, states=False):
     """The oracle's results of a row's problem: co-states and the update sweep (first or second order); with ``states`` the
     stored forward states too (the GPU test needs them, the witness does not)."""
-    key = (row.base, row.regime, row.theta_max, row.so)
-    if key in _references:
-        ref = _references[key]
+    return oracle_sweeps(_references, (row.base, row.regime, row.theta_max, row.so), lambda: problem(row), row.so, states)
+
+
+def oracle_sweeps(cache, key, problem_of, so, states=False):
+    """``reference``'s recipe for any regime problem (``problem_of()``), cached in ``cache`` under ``key``
+    (tests/test_grid_ends.py runs it on its own problems)."""
+    if key in cache:
+        ref = cache[key]
         if states and 'states' not in ref:
             with hp.MemoExpm():
-                ref['psi_T'], ref['states'] = ko.forward_propagation(ref['prob'], problem(row).pulses, store=True)
+                ref['psi_T'], ref['states'] = ko.forward_propagation(ref['prob'], problem_of().pulses, store=True)
         return ref
-    obj = problem(row)
+    obj = problem_of()
     prob = hp.regime_oracle(obj)
     norms = chi_norms(obj)
     # boundary co-states: the targets plus a random complex part (real operators between real states leave Im <chi| H_1
@@ -256,7 +261,7 @@ def reference(row, states=False):
             ref['psi_T'], ref['states'] = ko.forward_propagation(prob, obj.pulses, store=True)
         ref['chi'] = ko.backward_sweep(prob, chi_T, obj.pulses)
         kw = {}
-        if row.so:
+        if so:
             rng = np.random.default_rng(5)
             older = [p * (1.0 + 0.2 * rng.standard_normal(p.shape)) for p in obj.pulses]
             ref['prev'] = ko.forward_propagation(prob, older, store=True)[1]
@@ -264,9 +269,9 @@ def reference(row, states=False):
             kw = dict(sigma_vals=ref['sigma'], fw_prev=ref['prev'], store=True)
         out = ko.forward_update_sweep(prob, ref['chi'], norms, obj.pulses, obj.shapes, obj.lambdas, **kw)
     ref['opt'], ref['upd_T'], ref['g_a'] = np.array(out[0]), out[1], np.array(out[2])
-    if row.so:
+    if so:
         ref['store'] = out[3]
-    _references[key] = ref
+    cache[key] = ref
     return ref
 
 
