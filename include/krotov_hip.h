@@ -37,8 +37,10 @@
  *     workgroup without an objective writes nothing.  CSR: indptr [N+1], indices [nnz], data [nnz]; every index read
  *     from them must be a valid column.  Memory next to an extent may hold anything, NaN included, and may be unmapped.
  *   Inputs are never written: operator arrays, CSR arrays, expectation operators, pulses, shapes, lambda, norms,
- *     sigma, init, targets, chi_T, fw_prev_dev, u_guess_dev, dfdu_dev -- and chi_store_dev in the update sweeps
- *     (kh_forward_update, kh_update_*), which only kh_backward_store writes.  Outputs are the arguments marked OUT
+ *     sigma, init, targets, chi_T, fw_prev_dev, u_guess_dev, dfdu_dev, src_store_dev and chi_norms_dev of
+ *     kh_backward_store_source, ops_table_dev (and the operators it points to), factors_dev and in_store_dev of
+ *     kh_apply_store -- and chi_store_dev in the update sweeps (kh_forward_update, kh_update_*), which only
+ *     kh_backward_store / kh_backward_store_source write.  Outputs are the arguments marked OUT
  *     (and states_dev, psi_T_dev, chi_store_dev of the plain sweeps, tau_dev, out_dev, chi_T_dev, chi_norms_dev,
  *     partial_dev); fw_store_dev and u_opt_dev are outputs of the update sweeps while set.  A sweep writes its outputs
  *     in full (replica engines: the active replicas' slices only, kh_set_active_replicas) and never reads what they
@@ -269,6 +271,39 @@ int kh_forward_store(kh_engine *engine, const double *pulses_dev,
 int kh_backward_store(kh_engine *engine, const kh_cdouble *chi_T_dev,
                       const double *pulses_dev, kh_cdouble *chi_store_dev,
                       void *stream);
+
+/* Backward propagation with a source term: the co-state equation of a functional with a state-dependent running cost
+ * g_b(phi(t)), d chi / dt = -i H^+ chi + d g_b / d <phi| (no counterpart in the reference, whose how-to "penalize
+ * population in a forbidden subspace" names the inhomogeneous equation as not implemented).  With W_k(t_n) =
+ * -d g_b / d <phi_k| (t_n) -- the sign convention of chi_k(T) = -d J_T / d <phi_k| --, trapezoid in the source and the
+ * engine's own backward step V_n of kh_backward_store:
+ *     chi[nt-1] = chi_T,   chi[n] = V_n (chi[n+1] + h_n W[n+1]) + h_n W[n],   h_n = dt_n / 2 / chi_norms[k]
+ * (the sweeps propagate chi / ||chi(T)||, so the source is divided by the same norm; it is added once per interval, not
+ * per sub-step of the series, with that interval's dt).
+ *   chi_T_dev     [K][N]
+ *   src_store_dev [K][nt][N] W_k(t_n); read-only (kh_apply_store forms it from a stored trajectory)
+ *   chi_norms_dev [K] the norms taken out of chi_T, or NULL: 1
+ *   chi_store_dev [K][nt][N] OUT; [:, nt-1] = chi_T
+ * With src_store_dev all zeros the result equals kh_backward_store's where the same kernel family runs both.
+ * KH_ERR_UNSUPPORTED on replica, Lindblad-form and mixed engines, and where neither the register-tile form (N <= 64, 1..4
+ * controls) nor the generic kernels (N <= 2540) take the engine; KH_ERR_INVALID on a null argument (chi_norms_dev
+ * excepted) and when src_store_dev overlaps chi_store_dev. */
+int kh_backward_store_source(kh_engine *engine, const kh_cdouble *chi_T_dev, const double *pulses_dev,
+                             const kh_cdouble *src_store_dev, const double *chi_norms_dev, kh_cdouble *chi_store_dev,
+                             void *stream);
+
+/* out[k][n] = factors[n] * Op_k * in[k][n] for a whole stored trajectory, one batched product on the fp64 matrix cores.
+ *   ops_table_dev [K] DEVICE array of device pointers to row-major N x N operators in the engine's state space; equal
+ *                 pointers share an operator, NULL writes exact zeros for that objective
+ *   factors_dev   [nt] real factor per time point, or NULL: 1
+ *   in_store_dev  [K][nt][N] read-only
+ *   out_store_dev [K][nt][N] OUT
+ * The source of kh_backward_store_source for g_b = (lambda_b / T) s_b(t) sum_k <phi_k|D_k|phi_k> is this call with
+ * Op_k = D_k and factors[n] = -(lambda_b / T) s_b(t_n) on the forward states of the previous iteration.
+ * Uniform engines only: KH_ERR_UNSUPPORTED on mixed and Lindblad-form engines; KH_ERR_INVALID on a null argument
+ * (factors_dev excepted) and when in_store_dev overlaps out_store_dev. */
+int kh_apply_store(kh_engine *engine, const kh_cdouble *const *ops_table_dev, const double *factors_dev,
+                   const kh_cdouble *in_store_dev, kh_cdouble *out_store_dev, void *stream);
 
 /* Forward sweep with the sequential pulse update, whole grid, one launch.
  * Replaces the time loop optimize.py:444-501 (mu() / overlap() per

@@ -7,6 +7,7 @@ kernels behind a C ABI (include/krotov_hip.h).  See DESIGN.md.
 """
 from . import (
     configs,
+    constraints,
     convergence,
     conversions,
     functionals,
@@ -22,6 +23,7 @@ from . import (
 )
 from .objectives import Objective, ensemble_objectives, gate_objectives, propagate_objectives
 from .batch import optimize_pulses_batch
+from .constraints import QuadraticStateConstraint, StateDependentConstraint
 from .optimize import optimize_pulses
 from .parametrization import (
     LinearParametrization,
@@ -38,10 +40,13 @@ __all__ = [
     'LinearParametrization',
     'Objective',
     'Parametrization',
+    'QuadraticStateConstraint',
     'Result',
     'SquareParametrization',
+    'StateDependentConstraint',
     'TanhParametrization',
     'TanhSqParametrization',
+    'constraints',
     'convergence',
     'conversions',
     'ensemble_objectives',

@@ -96,6 +96,8 @@ SYMBOLS = {
     'kh_engine_kernel': (ctypes.c_char_p, [_P]),
     'kh_forward_store': (ctypes.c_int, [_P, _P, _P, _P, _P, _P]),
     'kh_backward_store': (ctypes.c_int, [_P, _P, _P, _P, _P]),
+    'kh_backward_store_source': (ctypes.c_int, [_P] * 7),
+    'kh_apply_store': (ctypes.c_int, [_P] * 6),
     'kh_forward_update': (ctypes.c_int, [_P] * 11),
     'kh_set_second_order': (ctypes.c_int, [_P, _P, _P, _P]),
     'kh_set_second_order_replicas': (ctypes.c_int, [_P, _P, _P, _P]),

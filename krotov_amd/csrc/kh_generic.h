@@ -319,42 +319,36 @@ __device__ __forceinline__ void kh_gen_put(cplx *__restrict__ dst, const cplx *s
 // direction +1: n = 0..nt-2, state index n -> n+1 (optimize.py:806-846)
 // direction -1: n = nt-2..0, state index n+1 -> n (optimize.py:849-886)
 // MIXED: objective k has its own dimension mx.dims[k] and factor mx.f[k] (kh_engine_create_mixed)
+// SRC (kh_gen_sweep_store_src): the backward sweep of a co-state equation with a source term (state-dependent running
+// costs, kh_backward_store_source):
+//     chi[n] = V_n (chi[n+1] + h_n W[n+1]) + h_n W[n],   h_n = dt_n / 2 / ||chi_k(T)||
+// -- trapezoid in the source, the engine's own step V_n, the source added once per interval.  A kernel of its own, so that
+// the sweep without a source keeps its code; both include one body (kh_gen_store.inc).
+struct KhSrcArgs {
+    const cplx *src;          // [K][nt][N] W_k(t_n), read-only
+    const double *chi_norms;  // [K] ||chi_k(T)|| the source is divided by, or NULL: 1
+};
+
 template <bool MIXED>
 __global__ void __launch_bounds__(KH_GEN_THREADS)
 kh_gen_sweep_store(KhSweepArgs p, KhMixedArgs mx, const double *__restrict__ pulses, const cplx *__restrict__ state_in,
                    cplx *__restrict__ store, cplx *__restrict__ state_out, int direction) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const KhGenLds s = kh_gen_carve(smem, p.N, p.csr == nullptr);
-    const int tid = threadIdx.x, NS = p.N, L = p.L, nt = p.nt;
-    double matvecs = 0.0;
-    for (int k = blockIdx.x; k < p.K; k += gridDim.x) {
-        const cplx *const *ops_k = p.ops + (size_t)k * (1 + L);
-        const double *norms_k = p.op_norms + (size_t)k * (1 + L);
-        const int N = MIXED ? mx.dims[k] : NS;
-        const double fre = MIXED ? mx.f[k].x : p.fre, fim = MIXED ? mx.f[k].y : p.fim;
-        for (int i = tid; i < N; i += KH_GEN_THREADS) s.acc[i] = state_in[(size_t)k * NS + i];
-        __syncthreads();
-        if (store != nullptr) {
-            const int idx0 = direction > 0 ? 0 : nt - 1;
-            kh_gen_put<MIXED>(store + ((size_t)k * nt + idx0) * NS, s.acc, N, NS);
-        }
-        for (int step = 0; step < nt - 1; ++step) {
-            const int n = direction > 0 ? step : nt - 2 - step;
-            // (the interval's pulse values in LDS, thread l fetching control l: up to KH_GEN_MAX_L of them; the previous
-            // step's readers are behind the barrier that ends its last term)
-            if (tid < L) s.eps[tid] = pulses[(size_t)tid * (nt - 1) + n];
-            __syncthreads();
-            matvecs += kh_gen_expm_action(p, N, fre, fim, ops_k, p.csr ? p.csr + (size_t)k * (1 + L) : nullptr, norms_k,
-                                          s.eps, p.dt[n], s);
-            if (store != nullptr) {
-                const int idx = direction > 0 ? n + 1 : n;
-                kh_gen_put<MIXED>(store + ((size_t)k * nt + idx) * NS, s.acc, N, NS);
-            }
-        }
-        if (state_out != nullptr) kh_gen_put<MIXED>(state_out + (size_t)k * NS, s.acc, N, NS);
-        __syncthreads();
-    }
-    if (tid == 0 && p.stats != nullptr) atomicAdd(p.stats, matvecs);
+    constexpr bool SRC = false;
+    const KhSrcArgs sa{};
+#include "kh_gen_store.inc"
+}
+
+// backward direction only: chi_T -> store[:, nt-1], then n = nt-2 .. 0; uniform engines (MIXED = false) only
+template <bool MIXED>
+__global__ void __launch_bounds__(KH_GEN_THREADS)
+kh_gen_sweep_store_src(KhSweepArgs p, KhSrcArgs sa, const double *__restrict__ pulses, const cplx *__restrict__ state_in,
+                       cplx *__restrict__ store) {
+    static_assert(!MIXED, "the source form is compiled for uniform engines");
+    constexpr bool SRC = true;
+    constexpr int direction = -1;
+    const KhMixedArgs mx{};
+    cplx *const state_out = nullptr;
+#include "kh_gen_store.inc"
 }
 
 // ---------------------------------------------------------------------------
@@ -444,56 +438,42 @@ kh_gen_adjoint_side(const cplx *const *__restrict__ ops_adj /*[K (1 + L)] adjoin
                     int N, int L, int nt)
 #if KH_DEFINES(KH_TU_GENERIC)
 {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int j = lane & 15, kq = lane >> 4;
     const int l = blockIdx.x / K, k = blockIdx.x % K;
     const cplx *op = ops_adj[(size_t)k * (1 + L) + 1 + l];
     if (op == nullptr) return;  // (the control does not occur in this objective: its sums are skipped in the sweep too)
-    // this lane's time points (B operand columns): one per vector group
-    const int n0 = (blockIdx.y * 4 + wave) * 16 * KH_GEN_ADJ_VG + j;
     const cplx *xk = chi_store + (size_t)k * nt * N;
     cplx *vk = V + ((size_t)l * K + k) * nt * N;
-    const int G = (N + 15) / 16;
-    for (int g = 0; g < G; ++g) {
-        kh_gen_d4 dr[KH_GEN_ADJ_VG], di[KH_GEN_ADJ_VG];
-#pragma unroll
-        for (int vg = 0; vg < KH_GEN_ADJ_VG; ++vg) dr[vg] = di[vg] = kh_gen_d4{0.0, 0.0, 0.0, 0.0};
-        const int arow = 16 * g + j;  // A operand: row lane & 15
-        for (int kb = 0; kb < G; ++kb) {
-            cplx a[4];
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                const int kk = 16 * kb + 4 * ks + kq;
-                a[ks] = (kk < N && arow < N) ? op[(size_t)arow * N + kk] : c_make(0.0, 0.0);
-            }
-#pragma unroll
-            for (int vg = 0; vg < KH_GEN_ADJ_VG; ++vg) {
-                const int n = n0 + 16 * vg;
-                cplx b[4];
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) {
-                    const int kk = 16 * kb + 4 * ks + kq;
-                    b[ks] = (kk < N && n < nt) ? xk[(size_t)n * N + kk] : c_make(0.0, 0.0);
-                }
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) {
-                    dr[vg] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[ks].x, b[ks].x, dr[vg], 0, 0, 0);
-                    dr[vg] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[ks].y, -b[ks].y, dr[vg], 0, 0, 0);
-                    di[vg] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[ks].x, b[ks].y, di[vg], 0, 0, 0);
-                    di[vg] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[ks].y, b[ks].x, di[vg], 0, 0, 0);
-                }
-            }
-        }
-#pragma unroll
-        for (int vg = 0; vg < KH_GEN_ADJ_VG; ++vg) {
-            const int n = n0 + 16 * vg;
-#pragma unroll
-            for (int reg = 0; reg < 4; ++reg) {
-                const int row = 16 * g + 4 * reg + kq;
-                if (n < nt && row < N) vk[(size_t)n * N + row] = c_make(dr[vg][reg], di[vg][reg]);
-            }
-        }
+    constexpr bool APPLY = false;
+    const double *factors = nullptr;
+#include "kh_gen_adjoint.inc"
+}
+#else
+    ;  // (defined in the translation unit that owns it: kh_common.h, KH_DEFINES)
+#endif
+
+// Out[k][n] = c[n] Op_k In[k][n] for a whole stored trajectory (kh_apply_store): the same batched product -- one body,
+// kh_gen_adjoint.inc -- with one operator per objective from a pointer table (equal pointers: a shared operator; NULL:
+// exact zeros are written), a real factor per time point applied at the store (NULL: none), any N.  Forms the source
+// W_k(t_n) = -(lambda_b / T) s_b(t_n) D_k phi_k(t_n) of a state-dependent running cost in front of the backward sweep, off
+// its chain.  blockIdx.x: objective k, blockIdx.y: KH_GEN_ADJ_POINTS time points.
+__global__ void __launch_bounds__(KH_GEN_ADJ_THREADS)
+kh_gen_apply_store(const cplx *const *__restrict__ ops /*[K] row-major N x N, or NULL*/, const double *__restrict__ factors /*[nt] or NULL*/,
+                   const cplx *__restrict__ in_store /*[K][nt][N]*/, cplx *__restrict__ out_store /*[K][nt][N]*/, int K, int N,
+                   int nt)
+#if KH_DEFINES(KH_TU_GENERIC)
+{
+    const int k = blockIdx.x;
+    const cplx *op = ops[k];
+    const cplx *xk = in_store + (size_t)k * nt * N;
+    cplx *vk = out_store + (size_t)k * nt * N;
+    if (op == nullptr) {
+        const int n_first = blockIdx.y * KH_GEN_ADJ_POINTS;
+        const int n_end = n_first + KH_GEN_ADJ_POINTS < nt ? n_first + KH_GEN_ADJ_POINTS : nt;
+        for (size_t i = (size_t)n_first * N + threadIdx.x; i < (size_t)n_end * N; i += KH_GEN_ADJ_THREADS) vk[i] = c_make(0.0, 0.0);
+        return;
     }
+    constexpr bool APPLY = true;
+#include "kh_gen_adjoint.inc"
 }
 #else
     ;  // (defined in the translation unit that owns it: kh_common.h, KH_DEFINES)

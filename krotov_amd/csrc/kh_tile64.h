@@ -245,82 +245,27 @@ __device__ __forceinline__ void kh_tile_load_ratios(const KhSweepArgs &p, double
 // ---------------------------------------------------------------------------
 // plain propagation with storage (backward sweep / iteration-0 forward sweep)
 // ---------------------------------------------------------------------------
+// SRC (kh_tile_sweep_store_src): the backward sweep of a co-state equation with a source term (state-dependent running
+// costs, kh_backward_store_source) -- a kernel of its own, so that the sweep without a source keeps its code; both include
+// one body (kh_tile64_store.inc).  KhSrcArgs: kh_generic.h.
 template <int RPT, int LT>
 __global__ void __launch_bounds__(512 / RPT, 2)
 kh_tile_sweep_store(KhSweepArgs p, const double *__restrict__ pulses, const cplx *__restrict__ state_in,
                     cplx *__restrict__ store, cplx *__restrict__ state_out, int direction) {
-    __shared__ __attribute__((aligned(16))) cplx buf[2][KH_TILE_N];
-    __shared__ __attribute__((aligned(16))) double inv_sh[KH_MAX_DEGREE + 2];
-    __shared__ __attribute__((aligned(16))) double deg_sh[KH_MAX_DEGREE + 2];
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const bool writer = KhTile<RPT>::writer(lane);
-    if (tid <= KH_MAX_DEGREE) {
-        deg_sh[tid] = p.q2_theta[tid];
-    }
-    const int N = p.N, nt = p.nt;
-    double matvecs = 0.0;
-    for (int k = blockIdx.x; k < p.K; k += gridDim.x) {
-        const cplx *const *ops_k = p.ops + (size_t)k * (1 + LT);
-        const double *norms_k = p.op_norms + (size_t)k * (1 + LT);
-        KhTileOps<RPT, LT, KhTileLds<RPT, LT>::STORE> h;
-        h.load(ops_k, N, wave, lane, kh_tile_dyn_lds, tid);
-        double nrm[1 + LT];
-#pragma unroll
-        for (int o = 0; o <= LT; ++o) nrm[o] = norms_k[o];
+    constexpr bool SRC = false;
+    const KhSrcArgs sa{};
+#include "kh_tile64_store.inc"
+}
 
-        cplx state[RPT];
-#pragma unroll
-        for (int r = 0; r < RPT; ++r) {
-            const int row = KhTile<RPT>::row(wave, lane, r);
-            state[r] = row < N ? state_in[(size_t)k * N + row] : c_make(0.0, 0.0);
-        }
-        __syncthreads();  // previous objective's readers are done with buf
-        int cur = 0;
-        if (writer) {
-#pragma unroll
-            for (int r = 0; r < RPT; ++r) buf[0][KhTile<RPT>::row(wave, lane, r)] = state[r];
-        }
-        __syncthreads();
-        if (store != nullptr && wave == 0 && lane < N)
-            store[((size_t)k * nt + (direction > 0 ? 0 : nt - 1)) * N + lane] = buf[0][lane];
-
-        // per-interval scalars are fetched one interval ahead (their load
-        // latency would otherwise sit on the critical path of every interval)
-        const int n0 = direction > 0 ? 0 : nt - 2;
-        double eps_next[LT], dt_next = p.dt[n0];
-#pragma unroll
-        for (int l = 0; l < LT; ++l) eps_next[l] = pulses[(size_t)l * (nt - 1) + n0];
-        int m_hint = 12;
-        for (int step = 0; step < nt - 1; ++step) {
-            const int n = direction > 0 ? step : nt - 2 - step;
-            double eps[LT];
-            double theta = nrm[0];
-            const double dt = dt_next;
-#pragma unroll
-            for (int l = 0; l < LT; ++l) {
-                eps[l] = eps_next[l];
-                theta += fabs(eps[l]) * nrm[1 + l];
-            }
-            if (step + 1 < nt - 1) {
-                const int nn = direction > 0 ? n + 1 : n - 1;
-                dt_next = p.dt[nn];
-#pragma unroll
-                for (int l = 0; l < LT; ++l) eps_next[l] = pulses[(size_t)l * (nt - 1) + nn];
-            }
-            int nsub, m;
-            kh_degree_lookup(theta * dt, deg_sh, p.theta_max, p.inv_theta_max, m_hint, &nsub, &m);
-            if (m != m_hint || step == 0) kh_tile_load_ratios(p, inv_sh, m, tid);  // (workgroup-uniform, rare)
-            m_hint = m;
-            cplx a[RPT][8];
-            h.build(eps, a);
-            matvecs += kh_tile_expm_action<RPT>(a, state, buf, inv_sh, cur, p.fre, p.fim, dt, nsub, m, wave, lane);
-            // buf[cur] now holds the new state: stream it to HBM, one coalesced 1 KiB store
-            if (store != nullptr && wave == 0 && lane < N)
-                store[((size_t)k * nt + (direction > 0 ? n + 1 : n)) * N + lane] = buf[cur][lane];
-        }
-        if (state_out != nullptr && wave == 0 && lane < N) state_out[(size_t)k * N + lane] = buf[cur][lane];
-    }
-    if (tid == 0 && p.stats != nullptr) atomicAdd(p.stats, matvecs);
+// backward direction only: chi_T -> store[:, nt-1], then n = nt-2 .. 0
+template <int RPT, int LT>
+__global__ void __launch_bounds__(512 / RPT, 2)
+kh_tile_sweep_store_src(KhSweepArgs p, KhSrcArgs sa, const double *__restrict__ pulses, const cplx *__restrict__ state_in,
+                        cplx *__restrict__ store) {
+    constexpr bool SRC = true;
+    constexpr int direction = -1;
+    cplx *const state_out = nullptr;
+#include "kh_tile64_store.inc"
 }
 
 // ---------------------------------------------------------------------------

@@ -2271,6 +2271,74 @@ extern "C" int kh_backward_store(kh_engine *e, const kh_cdouble *chi_T_dev, cons
                        (hipStream_t)stream);
 }
 
+// [a, a + bytes) and [b, b + bytes) share an address
+static bool ranges_overlap(const void *a, const void *b, size_t bytes) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + bytes && y < x + bytes;
+}
+
+// The backward sweep of a co-state equation with a source (state-dependent running costs; kh_tile64.h / kh_generic.h, SRC):
+// the register-tile form for the engines whose plain sweeps are the q2 (mini and quad included) or the 512-thread tile
+// kernels, the generic form for every other engine its vectors fit.
+extern "C" int kh_backward_store_source(kh_engine *e, const kh_cdouble *chi_T_dev, const double *pulses_dev,
+                                        const kh_cdouble *src_store_dev, const double *chi_norms_dev,
+                                        kh_cdouble *chi_store_dev, void *stream) {
+    if (e == nullptr || chi_T_dev == nullptr || src_store_dev == nullptr || chi_store_dev == nullptr ||
+        pulses_dev == nullptr && e->L > 0)
+        return kh_fail(KH_ERR_INVALID, "null argument");
+    if (ranges_overlap(src_store_dev, chi_store_dev, sizeof(cplx) * (size_t)e->K * e->nt * e->N))
+        return kh_fail(KH_ERR_INVALID, "src_store_dev overlaps chi_store_dev");
+    if (e->replicas > 0 || e->lind || e->mixed)
+        return kh_fail(KH_ERR_UNSUPPORTED, "the backward sweep with a source takes uniform engines (no replica, Lindblad-form or mixed engine)");
+    const KhPlan &pl = e->plan;
+    const bool tile = (pl.kind_store == KIND_TILE_Q2 || pl.kind_store == KIND_TILE_RPT1) && e->L >= 1 && e->L <= 4;
+    if (!tile && !e->gen_fits)
+        return kh_fail(KH_ERR_UNSUPPORTED, "N=%d: the backward sweep with a source runs on the generic kernels, whose vectors do not fit LDS", e->N);
+    hipStream_t st = (hipStream_t)stream;
+    const KhSweepArgs p = sweep_args(e, true);
+    const KhSrcArgs sa{(const cplx *)src_store_dev, chi_norms_dev};
+    const cplx *in = (const cplx *)chi_T_dev;
+    cplx *store = (cplx *)chi_store_dev;
+    KH_HIP(hipMemsetAsync(e->d_stats, 0, sizeof(double) * 4, st));
+    int rc = KH_OK;
+    if (tile) {
+        rc = with_tile_L(e->L, [&](auto lt) {
+            constexpr int LT = decltype(lt)::value;
+            constexpr size_t lds = KhTileLds<1, LT>::bytes(KhTileLds<1, LT>::STORE);  // operator tiles parked in LDS
+            return launch_plain_lds<kh_tile_sweep_store_src<1, LT>>(e, dim3(e->K), dim3(512), lds, st, p, sa, pulses_dev, in, store);
+        });
+    } else {
+        const int grid = e->K < 2 * e->num_cus ? e->K : 2 * e->num_cus;  // (as the plain generic sweep: sweep_store)
+        ensure_gen_scratch(e, grid);
+        KhSweepArgs pg = p;
+        pg.gen_scratch = e->d_gen_scratch;
+        pg.gen_scratch_wgs = e->gen_scratch_wgs;
+        rc = launch_plain_lds<kh_gen_sweep_store_src<false>>(e, dim3(grid), dim3(KH_GEN_THREADS), kh_gen_lds_bytes(e->N, e->d_csr_fw == nullptr),
+                                                             st, pg, sa, pulses_dev, in, store);
+    }
+    if (rc != KH_OK) return rc;
+    KH_HIP(hipGetLastError());
+    e->last_intervals = e->nt - 1;
+    e->last_wgs = e->K;
+    return KH_OK;
+}
+
+// Out[k][n] = c[n] Op_k In[k][n] over a stored trajectory (kh_generic.h, kh_gen_apply_store)
+extern "C" int kh_apply_store(kh_engine *e, const kh_cdouble *const *ops_table_dev, const double *factors_dev,
+                              const kh_cdouble *in_store_dev, kh_cdouble *out_store_dev, void *stream) {
+    if (e == nullptr || ops_table_dev == nullptr || in_store_dev == nullptr || out_store_dev == nullptr)
+        return kh_fail(KH_ERR_INVALID, "null argument");
+    if (ranges_overlap(in_store_dev, out_store_dev, sizeof(cplx) * (size_t)e->K * e->nt * e->N))
+        return kh_fail(KH_ERR_INVALID, "in_store_dev overlaps out_store_dev");
+    if (e->mixed || e->lind)
+        return kh_fail(KH_ERR_UNSUPPORTED, "kh_apply_store takes uniform engines (one dimension for all objectives, operators of the states' dimension)");
+    const dim3 grid((unsigned)e->K, (unsigned)((e->nt + KH_GEN_ADJ_POINTS - 1) / KH_GEN_ADJ_POINTS));
+    launch_plain<kh_gen_apply_store>(grid, dim3(KH_GEN_ADJ_THREADS), 0, (hipStream_t)stream, (const cplx *const *)ops_table_dev,
+                                     factors_dev, (const cplx *)in_store_dev, (cplx *)out_store_dev, e->K, e->N, e->nt);
+    KH_HIP(hipGetLastError());
+    return KH_OK;
+}
+
 // ---- the update sweep: one route per call (update_route), one small launcher per family
 
 enum KhRoute { ROUTE_ENS, ROUTE_ENS2, ROUTE_STREAM, ROUTE_QUAD, ROUTE_MINI, ROUTE_Q2, ROUTE_COOP, ROUTE_TILEN, ROUTE_ELL, ROUTE_TILE, ROUTE_TILEX, ROUTE_GENERIC, ROUTE_LIND };

@@ -492,6 +492,57 @@ class HipKrotovEngine:
                 self._handle, chi_T.data_ptr(), pulses.data_ptr(), out.data_ptr(), self._stream()))
         return out
 
+    def backward_source(self, chi_T, pulses, src_store, chi_norms=None, out=None):
+        """Backward sweep with a source term (``kh_backward_store_source``; state-dependent constraints):
+        ``chi[n] = V_n (chi[n+1] + h_n W[n+1]) + h_n W[n]``, ``h_n = dt_n / 2 / chi_norms[k]``, with ``src_store`` the
+        (K, nt, N) device tensor W (read-only; it must not be ``out``) and ``chi_norms`` the (K,) norms taken out of
+        ``chi_T`` (``None``: 1).  Returns (K, nt, N).  ``KrotovHipError`` (``KH_ERR_UNSUPPORTED``) on replica,
+        Lindblad-form and mixed engines."""
+        pulses = self._f(pulses, self._pulse_shape())
+        chi_T = self._c(chi_T, (self.K, self.N))
+        src_store = self._c(src_store, (self.K, self.nt, self.N))
+        norms = None if chi_norms is None else self._f(chi_norms, (self.K,))
+        out = self._out(out, (self.K, self.nt, self.N), torch.complex128)
+        with self._timed('backward'):
+            _lib.check(self._lib.kh_backward_store_source(
+                self._handle, chi_T.data_ptr(), pulses.data_ptr(), src_store.data_ptr(),
+                None if norms is None else norms.data_ptr(), out.data_ptr(), self._stream()))
+        return out
+
+    def apply_store(self, ops, factors, in_store, out=None):
+        """``out[k][n] = factors[n] * ops[k] @ in_store[k][n]`` for a whole (K, nt, N) stored trajectory
+        (``kh_apply_store``).  ``ops``: K operators of the states' dimension -- arrays, tensors or Qobj-like objects, every
+        distinct object uploaded once and kept; ``None`` writes exact zeros for that objective.  ``factors``: (nt,) real,
+        or ``None``.  ``KrotovHipError`` (``KH_ERR_UNSUPPORTED``) on mixed and Lindblad-form engines."""
+        from ._ingest import to_dense
+
+        ops = list(ops)
+        if len(ops) != self.K:
+            raise ValueError("ops: %d operators for %d objectives" % (len(ops), self.K))
+        cache = self.__dict__.setdefault('_apply_ops', {})
+        ptrs = np.zeros(self.K, dtype=np.int64)
+        for k, op in enumerate(ops):
+            if op is None:
+                continue
+            if id(op) not in cache:
+                host = op.detach().cpu().numpy() if isinstance(op, torch.Tensor) else to_dense(op)
+                host = np.ascontiguousarray(host, dtype=np.complex128)
+                if host.shape != (self.N, self.N):
+                    raise ValueError("ops[%d] has shape %s, expected %s" % (k, host.shape, (self.N, self.N)))
+                cache[id(op)] = (self._upload(host), op)  # keep `op` alive: id() stays unique
+            ptrs[k] = cache[id(op)][0].data_ptr()
+        key = ptrs.tobytes()
+        if self.__dict__.get('_apply_table_key') != key:  # (the same operators call after call: one table)
+            # (as 8-byte words of the upload seam's element types: complex128, float64, int32)
+            self._apply_table, self._apply_table_key = self._upload(ptrs.view(np.float64)), key
+        in_store = self._c(in_store, (self.K, self.nt, self.N))
+        fac = None if factors is None else self._f(factors, (self.nt,))
+        out = self._out(out, (self.K, self.nt, self.N), torch.complex128)
+        _lib.check(self._lib.kh_apply_store(
+            self._handle, self._apply_table.data_ptr(), None if fac is None else fac.data_ptr(), in_store.data_ptr(),
+            out.data_ptr(), self._stream()))
+        return out
+
     def set_second_order(self, fw_prev=None, fw_store=None, sigma_vals=None):
         """Switch the following update sweeps to the second-order update
         (``fw_prev``, ``fw_store``: (K, nt, N) device tensors; ``sigma_vals``:

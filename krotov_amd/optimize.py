@@ -36,6 +36,7 @@ import numpy as np
 
 from . import functionals as _functionals
 from ._ingest import state_to_vector, to_dense, to_sparse, vector_to_state
+from .constraints import QuadraticStateConstraint, StateDependentConstraint
 from .conversions import (
     control_onto_interval,
     discretize,
@@ -229,6 +230,28 @@ def _backward_propagation(i_state, chi_states, adjoint_objectives, pulses, pulse
     return out
 
 
+def _backward_propagation_source(i_state, chi_states, adjoint_objectives, pulses, pulses_mapping, tlist, propagators,
+                                 storage, source, chi_norms):
+    """:func:`_backward_propagation` with a source term (state-dependent constraints, krotov_amd.constraints):
+    ``chi[n] = V_n (chi[n+1] + h W[n+1]) + h W[n]`` with ``h = dt_n / 2 / ||chi(T)||``, V_n the propagator's own step."""
+    state = chi_states[i_state]
+    obj = adjoint_objectives[i_state]
+    mapping = pulses_mapping[i_state]
+    nt = len(tlist)
+    out = storage(nt)
+    out[-1] = state
+    for n in range(nt - 2, -1, -1):
+        dt = tlist[n + 1] - tlist[n]
+        h = 0.5 * dt / chi_norms[i_state]
+        H = plug_in_pulse_values(obj.H, pulses, mapping[0], n, conjugate=True)
+        c_ops = [plug_in_pulse_values(c, pulses, mapping[ic + 1], n) for ic, c in enumerate(obj.c_ops)]
+        state = state + h * vector_to_state(source[i_state, n + 1], state)
+        state = propagators[i_state](H, state, dt, c_ops, backwards=True, initialize=(n == nt - 2))
+        state = state + h * vector_to_state(source[i_state, n], state)
+        out[n] = state
+    return out
+
+
 def _forward_propagation_step(i_state, states, objectives, pulses, pulses_mapping, tlist, time_index, propagators):
     """Task for ``parallel_map[2]`` (reference optimize.py:889-911)."""
     obj = objectives[i_state]
@@ -268,13 +291,22 @@ class _PluginBackend:
         return np.array([self.overlap(obj.target, s) for s, obj in zip(fw_states_T, self.objectives)])
 
     def iterate(self, chi_states, chi_norms, guess_pulses, lambda_vals, shape_arrays, sigma=None,
-                forward_states0=None, par=None):
+                forward_states0=None, par=None, constraint=None):
         objectives, tlist = self.objectives, self.tlist
         K, nt = len(objectives), len(tlist)
-        backward_states = self.pmap[1](
-            _backward_propagation, list(range(K)),
-            (chi_states, self.adjoint_objectives, guess_pulses, self.mapping, tlist, self.propagators, self.storage),
-        )
+        if constraint is not None:
+            # state-dependent constraint: the source on the states under the guess pulses drives the co-states
+            source = np.asarray(constraint.source(forward_states0, tlist), dtype=np.complex128)
+            backward_states = self.pmap[1](
+                _backward_propagation_source, list(range(K)),
+                (chi_states, self.adjoint_objectives, guess_pulses, self.mapping, tlist, self.propagators, self.storage,
+                 source, chi_norms),
+            )
+        else:
+            backward_states = self.pmap[1](
+                _backward_propagation, list(range(K)),
+                (chi_states, self.adjoint_objectives, guess_pulses, self.mapping, tlist, self.propagators, self.storage),
+            )
         g_a = np.zeros(len(guess_pulses))
         optimized = copy.deepcopy(guess_pulses)
         if par is not None:  # pulse parametrizations: u is updated, the interval is propagated with f(u)
@@ -282,10 +314,13 @@ class _PluginBackend:
             u_new = [np.array(u, dtype=np.float64) for u in par.u]
         fw_states = [obj.initial_state for obj in objectives]
         forward_states = moved = None
-        if sigma is not None:  # second order: keep phi(t_n) and phi(t_n) - phi_prev(t_n) (optimize.py:429-442)
+        if sigma is not None or constraint is not None:
+            # second order: keep phi(t_n) and phi(t_n) - phi_prev(t_n) (optimize.py:429-442); a state-dependent
+            # constraint needs phi(t_n) for the next iteration's source
             forward_states = [self.storage(nt) for _ in range(K)]
             for k in range(K):
                 forward_states[k][0] = objectives[k].initial_state
+        if sigma is not None:
             moved = [fw_states[k] - forward_states0[k][0] for k in range(K)]  # zero at t=0
         for n in range(nt - 1):
             dt = tlist[n + 1] - tlist[n]
@@ -317,6 +352,7 @@ class _PluginBackend:
             )
             if sigma is not None:
                 moved = [fw_states[k] - forward_states0[k][n + 1] for k in range(K)]
+            if forward_states is not None:
                 for k in range(K):
                     forward_states[k][n + 1] = fw_states[k]
         if par is not None:
@@ -399,9 +435,10 @@ class _DeviceTrajectories:
     ``sigma.refresh``: (K_loc, nt, N) in HBM, fetched on access.  ``final``: the
     states at T of all objectives of all ranks on the host, if known."""
 
-    def __init__(self, tensor, likes, k0=0, final=None, layout=None):
+    def __init__(self, tensor, likes, k0=0, final=None, layout=None, engine=None):
         self._t, self._likes, self._k0, self._final = tensor, likes, k0, final
         self._layout = layout  # (mixed objective lists: rows at the stride, sliced back to N_k)
+        self._engine = engine  # (krotov_amd.constraints: expectation values of the trajectory on the device)
 
     def _state(self, row, k, like):
         if self._layout is not None:
@@ -647,7 +684,7 @@ class _HipBackend:
         fw_states_T = self._final_states(self.fw_T_dev)
         if store:
             forward_states = _DeviceTrajectories(self.fw_prev, self.likes, self.k0, final=fw_states_T._array,
-                                                 layout=self.layout)
+                                                 layout=self.layout, engine=self.engine)
         return fw_states_T, forward_states
 
     def tau_vals(self, fw_states_T):
@@ -669,7 +706,30 @@ class _HipBackend:
         chi, norms = self.last_chi
         return self._gather_rows(chi.cpu().numpy()), self._gather_rows(norms.cpu().numpy())
 
-    def iterate(self, chi_T, chi_norms, guess_pulses, lambda_vals, shape_arrays, sigma=None, chi_coef=None, par=None):
+    def _constraint_source(self, constraint):
+        """W_k(t_n) of a state-dependent constraint on the stored states under the guess pulses, a (K, nt, N) device
+        tensor: formed on the device (kh_apply_store) for the built-in quadratic cost, on the host from the fetched
+        trajectory for a ``source()`` of the user's own."""
+        t, eng = self.torch, self.engine
+        if self.__dict__.get('_src_store') is None:
+            self._src_store = t.empty_like(self.fw_prev)
+        if isinstance(constraint, QuadraticStateConstraint) and type(constraint).source is QuadraticStateConstraint.source:
+            ops = constraint.operators(self.objectives)
+            for k, op in enumerate(ops):
+                if op is not None and op.shape != (self.N, self.N):
+                    raise ValueError("state_dependent_constraint: D of objective %d has shape %s, the states have "
+                                     "dimension %d" % (k, op.shape, self.N))
+            factors = self._cached_upload('sdc_factors', np.asarray(constraint.factors(self.tlist_host), dtype=np.float64))
+            return eng.apply_store(ops, factors, self.fw_prev, out=self._src_store)
+        W = np.asarray(constraint.source(self.fw_prev.cpu().numpy(), self.tlist_host), dtype=np.complex128)
+        if W.shape != tuple(self.fw_prev.shape):
+            raise ValueError("state_dependent_constraint.source returned shape %s, expected %s" % (
+                W.shape, tuple(self.fw_prev.shape)))
+        self._src_store.copy_(eng.dev(W, t.complex128))
+        return self._src_store
+
+    def iterate(self, chi_T, chi_norms, guess_pulses, lambda_vals, shape_arrays, sigma=None, chi_coef=None, par=None,
+                constraint=None):
         """chi_T: (K_total, N) normalised co-states (host); chi_norms (K_total,) -- or
         ``chi_coef = (c, d)``, (K_total,) each: chi_k(T) = c_k target_k + d_k phi_k(T) is
         then formed and normalised on the device (kh_chi_boundary)."""
@@ -682,11 +742,16 @@ class _HipBackend:
         # two copies and a launch per iteration).  Shapes and step widths rarely change: uploaded when they do.
         shapes = self._cached_upload('shapes', np.array(shape_arrays, dtype=np.float64).reshape(self.L, self.nt - 1))
         lambdas = self._cached_upload('lambdas', np.asarray(lambda_vals, dtype=np.float64))
-        if sigma is not None:
+        if sigma is not None or constraint is not None:
             # sigma at the interval mid-points (optimize.py:451-452); phi under the guess pulses is
             # the trajectory the previous sweep stored, the running one goes to the other buffer
+            # (a state-dependent constraint without sigma: sigma = 0 -- the second-order kernels are the ones that store
+            # phi(t_n), which the next iteration's source is formed from)
             tl = np.asarray(self.tlist_host)
-            sig = np.array([sigma(tl[n] + 0.5 * (tl[n + 1] - tl[n])) for n in range(self.nt - 1)], dtype=np.float64)
+            if sigma is None:
+                sig = np.zeros(self.nt - 1)
+            else:
+                sig = np.array([sigma(tl[n] + 0.5 * (tl[n + 1] - tl[n])) for n in range(self.nt - 1)], dtype=np.float64)
             if self.fw_next is None:
                 self.fw_next = t.empty_like(self.fw_prev)
             eng.set_second_order(self.fw_prev, self.fw_next, sig)
@@ -709,7 +774,11 @@ class _HipBackend:
             chi_loc = eng.dev(chi_T[self.k0:self.k1], t.complex128)
             norms_loc = eng.dev(np.asarray(chi_norms, dtype=np.float64)[self.k0:self.k1], t.float64)
         self.last_chi = (chi_loc, norms_loc)
-        self.chi_store = self._split_guarded(lambda: eng.backward(chi_loc, guess, out=self.chi_store), 'backward')
+        if constraint is not None:
+            src = self._constraint_source(constraint)
+            self.chi_store = eng.backward_source(chi_loc, guess, src, norms_loc, out=self.chi_store)
+        else:
+            self.chi_store = self._split_guarded(lambda: eng.backward(chi_loc, guess, out=self.chi_store), 'backward')
         done = False
         if self.group is None:
             if self._single_launch_ok:
@@ -834,9 +903,9 @@ class _HipBackend:
             par.commit(u_opt.cpu().numpy(), optimized)
         backward_states = _DeviceTrajectories(self.chi_store, self.likes, self.k0, layout=self.layout)
         forward_states = None
-        if sigma is not None:
+        if sigma is not None or constraint is not None:
             forward_states = _DeviceTrajectories(self.fw_next, self.likes, self.k0, final=fw_states_T._array,
-                                                 layout=self.layout)
+                                                 layout=self.layout, engine=self.engine)
         return backward_states, optimized, fw_states_T, g_a.cpu().numpy(), forward_states
 
     def advance_second_order(self):
@@ -873,6 +942,7 @@ def optimize_pulses(
     overlap=None,
     limit_thread_pool=None,
     process_group=None,
+    state_dependent_constraint=None,
 ):
     """Optimise all controls in ``objectives`` with Krotov's method.
 
@@ -896,6 +966,13 @@ def optimize_pulses(
       u and the control stays inside the range of f (bounded controls).  ``Result``, hooks and dumps hold eps;
       ``g_a_integrals`` is the running cost in u.  The built-in kinds run inside the device's update sweep, a subclass
       of your own through the host loop; not with ``process_group``.
+    * ``state_dependent_constraint`` (extension): a :class:`~krotov_amd.constraints.StateDependentConstraint`, a running
+      cost g_b(phi(t)) -- the backward sweep then carries its source term (:mod:`krotov_amd.constraints`), on the device
+      (``kh_apply_store`` + ``kh_backward_store_source``) or, with a propagator of your own, in the host loop.  The
+      trajectories phi(t_n) of the last two iterations are kept as in second-order runs (``forward_states`` /
+      ``forward_states0`` of ``info_hook``); without ``sigma`` the device's update sweep is the second-order one with
+      sigma = 0.  Not with ``process_group``, ``c_ops``, objectives of different dimension or kind, or
+      ``skip_initial_forward_propagation``.
     * ``limit_thread_pool`` is accepted and ignored (no BLAS on the hot path).
     """
     logger = logging.getLogger('krotov')
@@ -905,6 +982,24 @@ def optimize_pulses(
         raise ValueError(
             "skip_initial_forward_propagation is incompatible with second order Krotov (sigma is not None)"
         )
+    constraint = state_dependent_constraint
+    if constraint is not None:
+        # (host-only, before any GPU work and any collective)
+        if not isinstance(constraint, StateDependentConstraint):
+            raise ValueError("state_dependent_constraint must be a krotov_amd.constraints.StateDependentConstraint, "
+                             "not %r" % (constraint,))
+        if process_group is not None:
+            raise ValueError("state-dependent constraints run on one GPU: process_group= (sharding) is not supported "
+                             "with state_dependent_constraint")
+        if any(len(obj.c_ops) > 0 for obj in objectives):
+            raise NotImplementedError("state_dependent_constraint is not implemented for objectives with c_ops "
+                                      "(Lindblad form)")
+        if skip_initial_forward_propagation:
+            raise ValueError("skip_initial_forward_propagation is incompatible with state_dependent_constraint (the "
+                             "source term needs the states under the guess pulses)")
+        if layout_of(objectives, propagator).mixed:
+            raise ValueError("state_dependent_constraint needs objectives of one dimension and kind")
+    keeps_states = second_order or constraint is not None  # phi(t_n) of the last two iterations are kept
     device_path = _use_device_path(propagator, mu, overlap, sigma, storage, objectives)
     params = _parametrizations(objectives, pulse_options)
     if params is not None and process_group is not None:
@@ -1004,14 +1099,14 @@ def optimize_pulses(
         tau_vals = np.array([overlap(obj.target, s) for s, obj in zip(fw_states_T, objectives)])
     else:
         if device_path:
-            fw_states_T, forward_states = backend.initial_forward(guess_pulses, store=second_order)
+            fw_states_T, forward_states = backend.initial_forward(guess_pulses, store=keeps_states)
         else:
             fw_states_T, forward_states = backend.initial_forward(guess_pulses)
         tau_vals = backend.tau_vals(fw_states_T)
     toc = time.time()
     # the stored trajectories are only needed by the second-order update (optimize.py:324-329);
     # in iteration 0 the states under "optimized" and guess pulses coincide
-    forward_states0 = forward_states = forward_states if second_order else None
+    forward_states0 = forward_states = forward_states if keeps_states else None
 
     info = None
     optimized_pulses = copy.deepcopy(guess_pulses)
@@ -1081,12 +1176,13 @@ def optimize_pulses(
                 logger.info("pulse parametrization: controls %s were changed after the last sweep; u re-derived", redone)
         if device_path:
             backward_states, optimized_pulses, fw_states_T, g_a, forward_states = backend.iterate(
-                chi_T, chi_norms, guess_pulses, lambda_vals, shape_arrays, sigma=sigma, chi_coef=chi_coef, par=par
+                chi_T, chi_norms, guess_pulses, lambda_vals, shape_arrays, sigma=sigma, chi_coef=chi_coef, par=par,
+                constraint=constraint,
             )
         else:
             backward_states, optimized_pulses, fw_states_T, g_a, forward_states = backend.iterate(
                 chi_states, chi_norms, guess_pulses, lambda_vals, shape_arrays, sigma=sigma,
-                forward_states0=forward_states0, par=par,
+                forward_states0=forward_states0, par=par, constraint=constraint,
             )
         g_a_integrals[:] = g_a
         tau_vals = backend.tau_vals(fw_states_T)
@@ -1133,6 +1229,7 @@ def optimize_pulses(
                 chi_norms=chi_norms, optimized_pulses=optimized_pulses, guess_pulses=guess_pulses,
                 objectives=objectives, result=result,
             )
+        if keeps_states:
             forward_states0 = forward_states
             if device_path:
                 backend.advance_second_order()
