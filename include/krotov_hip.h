@@ -586,6 +586,16 @@ int kh_debug_occupy(kh_engine *engine, int32_t workgroups, double milliseconds, 
  * adjoint-side pre-passes in front of an update sweep are listed too ("kh_gen_adjoint_side", "kh_coop_adjoint_side"). */
 int kh_debug_launched(int32_t which, char *buf, int32_t cap);
 
+/* Test hook (host only, no GPU needed): the lane roles of the two-terms-per-phase kernels' row-broadcast map, as the
+ * kernels compute them, for lane `lane` (0..63) of wave `wave` (0..7) of the 512-thread workgroup.
+ *   out[0]  the matrix row whose elements the lane holds        out[1]  the first of its 8 adjacent columns
+ *   out[2]  the vector element the lane reads from LDS (lane n of a 16-lane row: column out[1] + (n & 7))
+ *   out[3]  the first of the four lanes on which the matrix core leaves the sum over the wave's lanes of that row
+ *   out[4]  the row whose sum the lane receives                 out[5]  1: the lane writes it to LDS
+ *   out[6]  the column half (0: columns 0..31, 1: 32..63) the wave's sums are partial sums of
+ * KH_ERR_INVALID outside those ranges. */
+int kh_debug_q2_lane_map(int32_t wave, int32_t lane, int32_t *out /* [7] */);
+
 #ifdef __cplusplus
 }
 #endif

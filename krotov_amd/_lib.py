@@ -129,6 +129,7 @@ SYMBOLS = {
     'kh_series_tables_odd': (ctypes.c_int, [ctypes.c_double, ctypes.POINTER(ctypes.c_double),
                                             ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
     'kh_ell_rows_of': (ctypes.c_int32, [ctypes.c_int32]),
+    'kh_debug_q2_lane_map': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)]),
     'kh_ell_layout': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, _P, ctypes.POINTER(ctypes.c_int32),
                                      ctypes.POINTER(ctypes.c_int32), _P, _P, ctypes.c_int32]),
     'kh_ell_layout_global': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, _P, ctypes.POINTER(ctypes.c_int32),

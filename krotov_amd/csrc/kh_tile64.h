@@ -62,6 +62,54 @@ struct KhLanes<false> {
 };
 typedef KhLanes<false> KhTileLanes;
 
+// Lane roles of the row-broadcast map (512 threads; the two-terms-per-phase kernels, kh_tile64q2.h).  A wave is
+// (rb, half) = (wave >> 1, wave & 1); lane i of its DPP row d (lane = 16 d + i) holds matrix row 16 rb + i and the 8
+// columns 8 (d + 4 half) + 0..7: a wave covers 16 rows x 32 columns, the pair (rb, 0), (rb, 1) the full rows.
+//   input side:  lane n of a DPP row holds ONE element of the vector, x[8 (d + 4 half) + (n & 7)] (lanes 8..15 repeat
+//     lanes 0..7: no load under a branch); product j takes it from lane j of the row as the FMA's own DPP operand
+//     (row_newbcast:j) -- one or two ds_read_b128 per lane and product instead of eight, and no registers for the vector.
+//   output side: the four column blocks of a row are the lanes 16 k + i, which ONE v_mfma_f64_4x4x4 with a constant B
+//     operand adds; the sum for i = 4 blk + r4 lands on lanes 16 r4 + 4 blk + (0..3), whose first is the writer.  What
+//     lands is the wave's HALF of the row sum: everything kept on these lanes is the partial that belongs to the wave's
+//     column half, and the two are added where a complete vector is read.
+struct KhLanesR16 {
+    static __host__ __device__ __forceinline__ int half(int wave) { return wave & 1; }
+    static __host__ __device__ __forceinline__ int row_in(int wave, int lane) { return 16 * (wave >> 1) + (lane & 15); }
+    static __host__ __device__ __forceinline__ int col0(int wave, int lane) { return 8 * ((lane >> 4) + 4 * (wave & 1)); }
+    static __host__ __device__ __forceinline__ int x_index(int wave, int lane) { return col0(wave, lane) + (lane & 7); }
+    // where the row sum of input lane `lane` lands (first of four lanes), and the row whose sum an output lane holds
+    static __host__ __device__ __forceinline__ int landing_lane(int lane) { return 16 * (lane & 3) + 4 * ((lane >> 2) & 3); }
+    static __host__ __device__ __forceinline__ int row_out(int wave, int lane) {
+        return 16 * (wave >> 1) + 4 * ((lane >> 2) & 3) + (lane >> 4);
+    }
+    static __host__ __device__ __forceinline__ bool writer(int lane) { return (lane & 3) == 0; }
+    static __device__ __forceinline__ double rowsum(double v, double scale) {
+        return __builtin_amdgcn_mfma_f64_4x4x4f64(v, scale, 0.0, 0, 0, 0);
+    }
+    // acc += sum_j t[j] * x(lane j of this lane's DPP row).  The compiler neither folds a DPP move into an fp64 FMA nor
+    // sees inside the string: 2 wait states in front (x may come straight from a VALU add; a DPP read after a VALU
+    // write needs them) and 2 behind (acc goes to the matrix core next).
+    // Preconditions, both the caller's: (1) all 64 lanes active -- a row_newbcast from a disabled lane leaves the
+    // destination unwritten, so never call this inside a divergent branch; (2) no VALU write of EXEC (v_cmpx, ...)
+    // directly in front: a DPP instruction needs 5 wait states behind one, which the string does not carry.
+#define KH_R16_FMAC(J, RE, IM)                                                           \
+    "v_fmac_f64_dpp %0, %2, %" #RE " row_newbcast:" #J " row_mask:0xf bank_mask:0xf\n\t"  \
+    "v_fmac_f64_dpp %1, %3, %" #RE " row_newbcast:" #J " row_mask:0xf bank_mask:0xf\n\t"  \
+    "v_fmac_f64_dpp %0, -%3, %" #IM " row_newbcast:" #J " row_mask:0xf bank_mask:0xf\n\t" \
+    "v_fmac_f64_dpp %1, %2, %" #IM " row_newbcast:" #J " row_mask:0xf bank_mask:0xf\n\t"
+    static __device__ __forceinline__ void dot8(cplx &acc, const cplx (&t)[8], cplx x) {
+        asm("s_nop 1\n\t"
+            KH_R16_FMAC(0, 4, 5) KH_R16_FMAC(1, 6, 7) KH_R16_FMAC(2, 8, 9) KH_R16_FMAC(3, 10, 11)
+            KH_R16_FMAC(4, 12, 13) KH_R16_FMAC(5, 14, 15) KH_R16_FMAC(6, 16, 17) KH_R16_FMAC(7, 18, 19)
+            "s_nop 1"
+            : "+v"(acc.x), "+v"(acc.y)
+            : "v"(x.x), "v"(x.y), "v"(t[0].x), "v"(t[0].y), "v"(t[1].x), "v"(t[1].y), "v"(t[2].x), "v"(t[2].y),
+              "v"(t[3].x), "v"(t[3].y), "v"(t[4].x), "v"(t[4].y), "v"(t[5].x), "v"(t[5].y), "v"(t[6].x), "v"(t[6].y),
+              "v"(t[7].x), "v"(t[7].y));
+    }
+#undef KH_R16_FMAC
+};
+
 template <int RPT>
 struct KhTile {
     static constexpr int THREADS = 512 / RPT;

@@ -14,9 +14,10 @@
 // Flop count is unchanged (one matvec per term).
 //
 // Register budget (512 threads, 2 waves per SIMD, 256 VGPRs): H1, P1, P2, A, B
-// tiles (5 x 32 dwords) + the broadcast vector (32).  H0 and P0 tiles live in
-// LDS (2 x 64 KiB, lane-linear: conflict-free ds_read_b128) and are re-read
-// once per interval when A and B are rebuilt.
+// tiles (5 x 32 dwords); the vector takes one element per lane (4 dwords) under
+// the row-broadcast map, 32 dwords under the previous one (KH_Q2_R16 below).
+// H0 and P0 tiles live in LDS (2 x 64 KiB, lane-linear: conflict-free
+// ds_read_b128) and are re-read when A and B restart.
 #pragma once
 
 #include "kh_common.h"
@@ -31,12 +32,46 @@ typedef KhLanes<true> KhQ2Lanes;  // row sums on the matrix core (kh_tile64.h, "
 #endif
 #define KH_Q2_TILE_ELEMS (8 * KH_Q2_THREADS)  // complex elements of one 64x64 operator, lane-linear
 
+// The lane map of kh_q2_sweep_store in the backward direction.  R16 (default): the row-broadcast map of KhLanesR16 (kh_tile64.h) -- the term
+// vector reaches the FMAs through their DPP operand, two ds_read_b128 per lane and product.  -DKH_Q2_LDS_BROADCAST: the
+// previous map (KhQ2Lanes: a lane = 1 row x 8 strided columns, eight broadcast ds_read_b128 per lane and product), for
+// A/B timing.  kh_q2_forward_update stays on the previous map: on the new one it measured -1.4 % on its sweep, inside
+// the run-to-run ranges, for a second pass of a vector through LDS per interval (docs/HISTORY.md, "Row broadcast").
+#ifdef KH_Q2_LDS_BROADCAST
+constexpr bool KH_Q2_R16 = false;
+#else
+constexpr bool KH_Q2_R16 = true;
+#endif
+
+// What a kernel needs to know of its map.  Under R16 a vector in LDS is two partial vectors, one per column half of
+// the wave pairs that wrote it (`half`), and whatever a lane accumulates on the output side is its wave's partial.
+template <bool R16>
+struct KhQ2Map;
+template <>
+struct KhQ2Map<false> {
+    static __device__ __forceinline__ int half(int) { return 0; }
+    static __device__ __forceinline__ int row_in(int wave, int lane) { return wave * 8 + KhQ2Lanes::row_in(lane); }
+    static __device__ __forceinline__ int col(int, int lane, int j) { return KhQ2Lanes::cg(lane) + 8 * j; }
+    static __device__ __forceinline__ int row_out(int wave, int lane) { return wave * 8 + KhQ2Lanes::row_out(lane); }
+    static __device__ __forceinline__ bool writer(int lane) { return (lane & 7) == 0; }
+    static __device__ __forceinline__ double rowsum(double v, double scale) { return KhQ2Lanes::rowsum(v, scale); }
+};
+template <>
+struct KhQ2Map<true> {
+    static __device__ __forceinline__ int half(int wave) { return KhLanesR16::half(wave); }
+    static __device__ __forceinline__ int row_in(int wave, int lane) { return KhLanesR16::row_in(wave, lane); }
+    static __device__ __forceinline__ int col(int wave, int lane, int j) { return KhLanesR16::col0(wave, lane) + j; }
+    static __device__ __forceinline__ int row_out(int wave, int lane) { return KhLanesR16::row_out(wave, lane); }
+    static __device__ __forceinline__ bool writer(int lane) { return KhLanesR16::writer(lane); }
+    static __device__ __forceinline__ double rowsum(double v, double scale) { return KhLanesR16::rowsum(v, scale); }
+};
+
 struct KhQ2Lds {
     cplx *h0;    // [8][512]
     cplx *p0;    // [8][512]
-    cplx (*buf)[KH_TILE_N];  // [2][64]
+    cplx (*buf)[2][KH_TILE_N];  // [2][half][64] (the previous map: half 0 only)
     cplx *chib;  // [64] chi(t_{n+1}) for the adjoint-side partial sums
-    cplx *sbuf;  // [64] the vector s of kh_q2_expm_action
+    cplx (*sbuf)[KH_TILE_N];  // [half][64] the vector s of kh_q2_expm_action
     double *red; // [2][8 waves][2]
     double *D;   // [2][2]
     double2 *inv2;  // [KH_Q2_ROWS] the series' rows {r1_p, r2_p} of the current degree (Taylor: {1/(2p+1),
@@ -45,7 +80,7 @@ struct KhQ2Lds {
 };
 
 __host__ __device__ inline size_t kh_q2_lds_bytes() {
-    return (size_t)2 * KH_Q2_TILE_ELEMS * sizeof(cplx) + 4 * KH_TILE_N * sizeof(cplx) + (2 * 8 * 2 + 4) * sizeof(double) +
+    return (size_t)2 * KH_Q2_TILE_ELEMS * sizeof(cplx) + 7 * KH_TILE_N * sizeof(cplx) + (2 * 8 * 2 + 4) * sizeof(double) +
            (KH_MAX_DEGREE / 2 + 1) * sizeof(double2) + (KH_MAX_DEGREE + 2) * sizeof(double);
 }
 
@@ -53,29 +88,32 @@ __device__ __forceinline__ KhQ2Lds kh_q2_carve(char *smem) {
     KhQ2Lds s;
     s.h0 = (cplx *)smem;
     s.p0 = s.h0 + KH_Q2_TILE_ELEMS;
-    s.buf = (cplx(*)[KH_TILE_N])(s.p0 + KH_Q2_TILE_ELEMS);
+    s.buf = (cplx(*)[2][KH_TILE_N])(s.p0 + KH_Q2_TILE_ELEMS);
     s.chib = (cplx *)(s.buf + 2);
-    s.sbuf = s.chib + KH_TILE_N;
-    s.red = (double *)(s.sbuf + KH_TILE_N);
+    s.sbuf = (cplx(*)[KH_TILE_N])(s.chib + KH_TILE_N);
+    s.red = (double *)(s.sbuf + 2);
     s.D = s.red + 2 * 8 * 2;
     s.inv2 = (double2 *)(s.D + 4);
     s.deg = (double *)(s.inv2 + KH_MAX_DEGREE / 2 + 1);
     return s;
 }
 
-// this lane's 8 elements of an operator (row wave*8 + row_in, columns cg + 8 j)
+// this lane's 8 elements of an operator (R16: row 16 rb + i, columns 8 (d + 4 half) + j; the previous map: row
+// wave*8 + row_in, columns cg + 8 j)
+template <bool R16>
 __device__ __forceinline__ void kh_q2_load_tile(const cplx *op, int N, int wave, int lane, cplx (&t)[8]) {
-    const int row = wave * 8 + KhQ2Lanes::row_in(lane), cg = KhQ2Lanes::cg(lane);
+    const int row = KhQ2Map<R16>::row_in(wave, lane);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-        const int col = cg + 8 * j;
+        const int col = KhQ2Map<R16>::col(wave, lane, j);
         t[j] = (op != nullptr && row < N && col < N) ? op[(size_t)row * N + col] : c_make(0.0, 0.0);
     }
 }
 
+template <bool R16>
 __device__ __forceinline__ void kh_q2_stage_tile(const cplx *op, int N, int wave, int lane, int tid, cplx *dst) {
     cplx t[8];
-    kh_q2_load_tile(op, N, wave, lane, t);
+    kh_q2_load_tile<R16>(op, N, wave, lane, t);
 #pragma unroll
     for (int j = 0; j < 8; ++j) dst[j * KH_Q2_THREADS + tid] = t[j];
 }
@@ -89,6 +127,36 @@ __device__ __forceinline__ void kh_q2_load_rows(const KhSweepArgs &p, const KhQ2
     }
     if (tid == KH_Q2_ROWS) s.inv2[KH_Q2_ROWS] = make_double2(p.q2_c0[m], 0.0);
     __syncthreads();
+}
+
+// acc = sum_j t[j] x[column j of this lane]: the lane's part of the row's product with the vector x in LDS, before the
+// row sum.  R16: x = x0 + x1, the two partial vectors; one element per lane, the rest by row broadcast.
+template <bool R16>
+__device__ __forceinline__ cplx kh_q2_dot(const cplx (&t)[8], const cplx *x0, const cplx *x1, int wave, int lane) {
+    cplx acc = c_make(0.0, 0.0);
+    if constexpr (R16) {
+        const int xi = KhLanesR16::x_index(wave, lane);
+        const cplx xa = x0[xi], xb = x1[xi];
+        KhLanesR16::dot8(acc, t, c_make(xa.x + xb.x, xa.y + xb.y));
+    } else {
+        const int cg = KhQ2Lanes::cg(lane);
+        cplx xv[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) xv[j] = x0[cg + 8 * j];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) c_fma(acc, t[j], xv[j]);
+    }
+    return acc;
+}
+// element i of a complete vector in LDS
+template <bool R16>
+__device__ __forceinline__ cplx kh_q2_vec_at(const cplx (*v)[KH_TILE_N], int i) {
+    cplx x = v[0][i];
+    if constexpr (R16) {
+        x.x += v[1][i].x;
+        x.y += v[1][i].y;
+    }
+    return x;
 }
 
 // A = H0 + eps H1,  B = P0 + eps P1 + eps^2 P2  (H0, P0 from LDS)
@@ -167,15 +235,20 @@ __device__ __forceinline__ void kh_q2_advance(const KhQ2Lds &s, int tid, double 
 // of P + 1.  Without `odd` an odd m evaluates degree m + 1 (Taylor's table has odd entries).
 // `epilogue()` runs once, when the new state is complete in `state` and before the last barrier: work that
 // depends on the new state and must be visible after that barrier rides on it instead of a barrier of its own.
+// R16: `state`, s and every term are linear in the incoming vector, so each wave of a pair carries the partial of its
+// column half on its output lanes and writes it to its half of the LDS vectors; the halves meet only where a vector is
+// read (kh_q2_dot, kh_q2_vec_at).  One barrier per phase as before; the order of summation differs from the
+// previous map's; an epilogue would see its wave's half of `state` (the one R16 caller passes none).  `state` on entry: the complete vector's partials (e.g. the vector on half 0, zero on half 1).
 // Returns the number of matrix-vector products issued.
-template <class Epilogue>
+template <bool R16, class Epilogue>
 __device__ __forceinline__ int kh_q2_expm_action(const cplx (&a)[8], const cplx (&b)[8], cplx &state,
-                                                 cplx (*buf)[KH_TILE_N], cplx *sbuf, const double2 *inv2, int &cur,
-                                                 cplx *store_in, int N, double fre, double fim,
+                                                 cplx (*buf)[2][KH_TILE_N], cplx (*sbuf)[KH_TILE_N], const double2 *inv2,
+                                                 int &cur, cplx *store_in, int N, double fre, double fim,
                                                  double dt, int nsub, int m, bool odd, int wave, int lane,
                                                  Epilogue epilogue) {
-    const int cg = KhQ2Lanes::cg(lane), row = wave * 8 + KhQ2Lanes::row_out(lane);
-    const bool writer = (lane & 7) == 0;
+    typedef KhQ2Map<R16> Map;
+    const int row = Map::row_out(wave, lane), half = Map::half(wave);
+    const bool writer = Map::writer(lane);
     const double h = nsub == 1 ? dt : dt / nsub;
     const double f2h2 = (fre * fre - fim * fim) * h * h;  // f is purely real or purely imaginary
     const int phases = (m + 1) >> 1;
@@ -183,7 +256,7 @@ __device__ __forceinline__ int kh_q2_expm_action(const cplx (&a)[8], const cplx 
     if (store_in != nullptr && wave == 0 && lane < N) {
         // the interval's incoming state goes to HBM from here (one LDS read + one fire-and-forget
         // coalesced store, outside the phase loop so the loop carries no exec-mask juggling for it)
-        store_in[lane] = buf[cur][lane];
+        store_in[lane] = kh_q2_vec_at<R16>(buf[cur], lane);
     }
     for (int sub = 0; sub < nsub; ++sub) {
         // this row of s = sum_p r1_p h T_2p (T_0 = c_0 v, r1_0 relative to the incoming state v; Taylor: 1/(2p+1))
@@ -191,45 +264,49 @@ __device__ __forceinline__ int kh_q2_expm_action(const cplx (&a)[8], const cplx 
         cplx sacc = c_make(hr * state.x, hr * state.y);
         state = c_make(c0 * state.x, c0 * state.y);
         if (phases == 1) {  // (degree <= 2) s = h t_0 is final already: one extra barrier in this rare case
-            if (writer) sbuf[row] = sacc;
+            if (writer) sbuf[half][row] = sacc;
             __syncthreads();
         }
         for (int ph = 0; ph < phases; ++ph) {
             const bool last = (ph + 1 == phases);
             if (!(last && no_last_b)) {
-                const double c2 = f2h2 * inv2[ph].y;  // inv2[p] = {r1_p, r2_p}
-                cplx xv[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) xv[j] = buf[cur][cg + 8 * j];
-                cplx yb = c_make(0.0, 0.0);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) c_fma(yb, b[j], xv[j]);
-                const double t2x = KhQ2Lanes::rowsum(yb.x, c2), t2y = KhQ2Lanes::rowsum(yb.y, c2);
+                double c2, hn = 0.0;  // inv2[p] = {r1_p, r2_p}
+                cplx yb;
+                if constexpr (R16) {
+                    // every LDS read of the phase in one batch, the vector's in front: nothing waits for the series'
+                    // rows, neither the product nor -- behind the row sums -- the write of the term
+                    const int xi = KhLanesR16::x_index(wave, lane);
+                    const cplx x0 = buf[cur][0][xi], x1 = buf[cur][1][xi];
+                    const double r2 = inv2[ph].y, r1n = inv2[ph + 1].x;  // ([ph + 1] <= [KH_Q2_ROWS]: in the array)
+                    c2 = f2h2 * r2;
+                    hn = h * r1n;
+                    yb = c_make(0.0, 0.0);
+                    KhLanesR16::dot8(yb, b, c_make(x0.x + x1.x, x0.y + x1.y));
+                } else {
+                    c2 = f2h2 * inv2[ph].y;
+                    yb = kh_q2_dot<R16>(b, buf[cur][0], buf[cur][1], wave, lane);
+                }
+                const double t2x = Map::rowsum(yb.x, c2), t2y = Map::rowsum(yb.y, c2);
                 state.x += t2x;
                 state.y += t2y;
                 if (!last) {
-                    const double hn = h * inv2[ph + 1].x;
+                    if constexpr (!R16) hn = h * inv2[ph + 1].x;
                     sacc.x = fma(hn, t2x, sacc.x);
                     sacc.y = fma(hn, t2y, sacc.y);
                     if (writer) {
-                        buf[cur ^ 1][row] = c_make(t2x, t2y);
-                        if (ph + 2 == phases) sbuf[row] = sacc;  // s is complete: next phase multiplies it by A
+                        buf[cur ^ 1][half][row] = c_make(t2x, t2y);
+                        if (ph + 2 == phases) sbuf[half][row] = sacc;  // s is complete: next phase multiplies it by A
                     }
                 }
             }
             if (last) {
                 // (the B product is finished before s is fetched: both vectors at once do not fit next to the tiles)
                 __builtin_amdgcn_sched_barrier(0);
-                cplx sv[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) sv[j] = sbuf[cg + 8 * j];
-                cplx ya = c_make(0.0, 0.0);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) c_fma(ya, a[j], sv[j]);
-                const cplx odd_sum = c_mul(c_make(fre, fim), c_make(KhQ2Lanes::rowsum(ya.x, 1.0), KhQ2Lanes::rowsum(ya.y, 1.0)));
+                const cplx ya = kh_q2_dot<R16>(a, sbuf[0], sbuf[1], wave, lane);
+                const cplx odd_sum = c_mul(c_make(fre, fim), c_make(Map::rowsum(ya.x, 1.0), Map::rowsum(ya.y, 1.0)));
                 state.x += odd_sum.x;
                 state.y += odd_sum.y;
-                if (writer) buf[cur ^ 1][row] = c_make(state.x, state.y);
+                if (writer) buf[cur ^ 1][half][row] = c_make(state.x, state.y);
                 if (sub + 1 == nsub) epilogue();
             }
             __syncthreads();
@@ -243,35 +320,35 @@ __device__ __forceinline__ int kh_q2_expm_action(const cplx (&a)[8], const cplx 
 // plain propagation with storage (backward sweep / iteration-0 forward sweep)
 // ---------------------------------------------------------------------------
 // sq: [K*3] pointers to P0, P1, P2 of this direction's operators
-__global__ void __launch_bounds__(KH_Q2_THREADS)
-kh_q2_sweep_store(KhSweepArgs p, const cplx *const *__restrict__ sq, const double *__restrict__ pulses,
-                  const cplx *__restrict__ state_in, cplx *__restrict__ store, cplx *__restrict__ state_out,
-                  int direction)
-#if KH_DEFINES(KH_TU_Q2)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
+template <bool R16>
+__device__ __forceinline__ void kh_q2_sweep_store_body(const KhSweepArgs &p, const cplx *const *__restrict__ sq,
+                                                       const double *__restrict__ pulses,
+                                                       const cplx *__restrict__ state_in, cplx *__restrict__ store,
+                                                       cplx *__restrict__ state_out, int direction, char *smem) {
     const KhQ2Lds s = kh_q2_carve(smem);
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     if (tid <= KH_MAX_DEGREE) s.deg[tid] = p.q2_theta[tid];
-    const int row = wave * 8 + KhQ2Lanes::row_out(lane);  // the row whose sums/state this lane holds
-    const bool writer = (lane & 7) == 0;
+    typedef KhQ2Map<R16> Map;
+    const int row = Map::row_out(wave, lane);  // the row whose sums/state this lane holds (R16: its wave's half of them)
+    const int half = Map::half(wave);
+    const bool writer = Map::writer(lane);
     const int N = p.N, nt = p.nt;
     double matvecs = 0.0;
     for (int k = blockIdx.x; k < p.K; k += gridDim.x) {
         const cplx *const *ops_k = p.ops + (size_t)k * 2;
         const cplx *const *sq_k = sq + (size_t)k * 3;
         __syncthreads();  // previous objective's readers are done with LDS
-        kh_q2_stage_tile(ops_k[0], N, wave, lane, tid, s.h0);
-        kh_q2_stage_tile(sq_k[0], N, wave, lane, tid, s.p0);
+        kh_q2_stage_tile<R16>(ops_k[0], N, wave, lane, tid, s.h0);
+        kh_q2_stage_tile<R16>(sq_k[0], N, wave, lane, tid, s.p0);
         cplx h1[8], p1[8], p2[8];
-        kh_q2_load_tile(ops_k[1], N, wave, lane, h1);
-        kh_q2_load_tile(sq_k[1], N, wave, lane, p1);
-        kh_q2_load_tile(sq_k[2], N, wave, lane, p2);
+        kh_q2_load_tile<R16>(ops_k[1], N, wave, lane, h1);
+        kh_q2_load_tile<R16>(sq_k[1], N, wave, lane, p1);
+        kh_q2_load_tile<R16>(sq_k[2], N, wave, lane, p2);
         const double nrm0 = p.op_norms[(size_t)k * 2], nrm1 = p.op_norms[(size_t)k * 2 + 1];
 
-        cplx state = row < N ? state_in[(size_t)k * N + row] : c_make(0.0, 0.0);
+        cplx state = (row < N && half == 0) ? state_in[(size_t)k * N + row] : c_make(0.0, 0.0);
         int cur = 0;
-        if (writer) s.buf[0][row] = state;
+        if (writer) s.buf[0][half][row] = state;
         __syncthreads();
         // the state entering interval `step` is stored from inside its first phase
         // (index n for the forward direction, n+1 for the backward one); the last
@@ -315,8 +392,8 @@ kh_q2_sweep_store(KhSweepArgs p, const cplx *const *__restrict__ sq, const doubl
             const long long tq1 = clock64();
             t_build += tq1 - tq0;
 #endif
-            matvecs += kh_q2_expm_action(a, b, state, s.buf, s.sbuf, s.inv2, cur, store_in, N, p.fre, p.fim, dt, nsub, m,
-                                         p.q2_odd != 0, wave, lane, [] {});
+            matvecs += kh_q2_expm_action<R16>(a, b, state, s.buf, s.sbuf, s.inv2, cur, store_in, N, p.fre, p.fim, dt, nsub,
+                                              m, p.q2_odd != 0, wave, lane, [] {});
 #ifdef KH_TIMING
             t_phases += clock64() - tq1;
 #endif
@@ -329,10 +406,27 @@ kh_q2_sweep_store(KhSweepArgs p, const cplx *const *__restrict__ sq, const doubl
         }
 #endif
         if (store != nullptr && wave == 0 && lane < N)
-            store[((size_t)k * nt + (direction > 0 ? nt - 1 : 0)) * N + lane] = s.buf[cur][lane];
-        if (state_out != nullptr && wave == 0 && lane < N) state_out[(size_t)k * N + lane] = s.buf[cur][lane];
+            store[((size_t)k * nt + (direction > 0 ? nt - 1 : 0)) * N + lane] = kh_q2_vec_at<R16>(s.buf[cur], lane);
+        if (state_out != nullptr && wave == 0 && lane < N)
+            state_out[(size_t)k * N + lane] = kh_q2_vec_at<R16>(s.buf[cur], lane);
     }
     if (tid == 0 && p.stats != nullptr) atomicAdd(p.stats, matvecs);
+}
+
+// The backward sweep (every iteration) runs on the row-broadcast map.  The forward sweep with storage (iteration 0) keeps
+// the map of kh_q2_forward_update: where no control acts the update sweep must reproduce it bit for bit
+// (tests/test_absent_controls.py), which two orders of summation cannot.
+__global__ void __launch_bounds__(KH_Q2_THREADS)
+kh_q2_sweep_store(KhSweepArgs p, const cplx *const *__restrict__ sq, const double *__restrict__ pulses,
+                  const cplx *__restrict__ state_in, cplx *__restrict__ store, cplx *__restrict__ state_out,
+                  int direction)
+#if KH_DEFINES(KH_TU_Q2)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    if (KH_Q2_R16 && !(direction > 0))
+        kh_q2_sweep_store_body<true>(p, sq, pulses, state_in, store, state_out, direction, smem);
+    else
+        kh_q2_sweep_store_body<false>(p, sq, pulses, state_in, store, state_out, direction, smem);
 }
 #else
     ;  // (defined in the translation unit that owns it: kh_common.h, KH_DEFINES)
@@ -386,10 +480,10 @@ kh_q2_forward_update(KhSweepArgs p, const cplx *const *__restrict__ sq, KhUpdate
 
     const cplx *const *ops_k = p.ops + (size_t)k * 2;
     const cplx *const *sq_k = sq + (size_t)k * 3;
-    kh_q2_stage_tile(sq_k[1], N, wave, lane, tid, s.h0);  // P1, P2 (kh_q2_advance)
-    kh_q2_stage_tile(sq_k[2], N, wave, lane, tid, s.p0);
+    kh_q2_stage_tile<false>(sq_k[1], N, wave, lane, tid, s.h0);  // P1, P2 (kh_q2_advance)
+    kh_q2_stage_tile<false>(sq_k[2], N, wave, lane, tid, s.p0);
     cplx h1[8], a[8], b[8];
-    kh_q2_load_tile(ops_k[1], N, wave, lane, h1);  // also dH/d eps (mu.py:123-134)
+    kh_q2_load_tile<false>(ops_k[1], N, wave, lane, h1);  // also dH/d eps (mu.py:123-134)
     double eps_prev = 0.0;
     // (wave-uniform scalars live in SGPRs: the VGPR file is full of operator tiles)
     const double nrm0 = kh_uniform(p.op_norms[(size_t)k * 2]), nrm1 = kh_uniform(p.op_norms[(size_t)k * 2 + 1]);
@@ -397,7 +491,7 @@ kh_q2_forward_update(KhSweepArgs p, const cplx *const *__restrict__ sq, KhUpdate
 
     cplx state = row < N ? u.phi[(size_t)k * N + row] : c_make(0.0, 0.0);
     int cur = 0;
-    if (writer) s.buf[0][row] = state;
+    if (writer) s.buf[0][0][row] = state;
     __syncthreads();
 
     double g_a_loc = 0.0;
@@ -417,7 +511,7 @@ kh_q2_forward_update(KhSweepArgs p, const cplx *const *__restrict__ sq, KhUpdate
     auto partial_pieces = [&](int par) {
         cplx xv[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) xv[j] = s.buf[cur][cg + 8 * j];
+        for (int j = 0; j < 8; ++j) xv[j] = s.buf[cur][0][cg + 8 * j];
         cplx y = c_make(0.0, 0.0);
 #pragma unroll
         for (int j = 0; j < 8; ++j) c_fma(y, h1[j], xv[j]);
@@ -487,8 +581,8 @@ kh_q2_forward_update(KhSweepArgs p, const cplx *const *__restrict__ sq, KhUpdate
     // indices (multiples of KH_Q2_REFRESH, plus the launch's first interval), so a sweep cut into several launches
     // restarts where the single launch does.  Rounding: an advanced tile carries an absolute error of a few
     // ulp(max |eps|^2 |P2|) over the window -- relative to the LARGEST pulse value of the window, not the current one.
-    kh_q2_load_tile(ops_k[0], N, wave, lane, a);
-    kh_q2_load_tile(sq_k[0], N, wave, lane, b);
+    kh_q2_load_tile<false>(ops_k[0], N, wave, lane, a);
+    kh_q2_load_tile<false>(sq_k[0], N, wave, lane, b);
     eps_prev = 0.0;
     n_stop = (nr / KH_Q2_REFRESH + 1) * KH_Q2_REFRESH;
     n_stop = n_stop < u.n_end ? n_stop : u.n_end;
@@ -599,11 +693,11 @@ kh_q2_forward_update(KhSweepArgs p, const cplx *const *__restrict__ sq, KhUpdate
             epilogue();
             __syncthreads();
 #else
-            matvecs += kh_q2_expm_action(a, b, state, s.buf, s.sbuf, s.inv2, cur, fw_out, N, p.fre, p.fim, dt, nsub, m,
+            matvecs += kh_q2_expm_action<false>(a, b, state, s.buf, s.sbuf, s.inv2, cur, fw_out, N, p.fre, p.fim, dt, nsub, m,
                                          p.q2_odd != 0, wave, lane, epilogue);
 #endif
         } else {
-            matvecs += kh_q2_expm_action(a, b, state, s.buf, s.sbuf, s.inv2, cur, fw_out, N, p.fre, p.fim, dt, nsub, m,
+            matvecs += kh_q2_expm_action<false>(a, b, state, s.buf, s.sbuf, s.inv2, cur, fw_out, N, p.fre, p.fim, dt, nsub, m,
                                          p.q2_odd != 0, wave, lane, [] {});
         }
 #ifdef KH_TIMING
@@ -629,8 +723,8 @@ kh_q2_forward_update(KhSweepArgs p, const cplx *const *__restrict__ sq, KhUpdate
     }
 #endif
     if (wave == 0 && lane < N) {
-        u.phi[(size_t)k * N + lane] = s.buf[cur][lane];
-        if constexpr (SO) u.fw_store[((size_t)k * nt + u.n_end) * N + lane] = s.buf[cur][lane];
+        u.phi[(size_t)k * N + lane] = s.buf[cur][0][lane];
+        if constexpr (SO) u.fw_store[((size_t)k * nt + u.n_end) * N + lane] = s.buf[cur][0][lane];
     }
     if (k == 0 && tid == 0) u.g_a[0] = g_a_loc;
     if (tid == 0 && p.stats != nullptr) atomicAdd(p.stats, matvecs);

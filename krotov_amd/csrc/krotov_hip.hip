@@ -3391,6 +3391,19 @@ extern "C" int kh_last_stats(kh_engine *e, double stats[4]) {
 
 extern "C" int32_t kh_ell_rows_of(int32_t N) { return N >= 1 && N <= KH_ELL_NMAX ? kh_ell_rows(N) : 0; }
 
+extern "C" int kh_debug_q2_lane_map(int32_t wave, int32_t lane, int32_t *out) {
+    if (out == nullptr || wave < 0 || wave >= KH_Q2_THREADS / 64 || lane < 0 || lane >= 64)
+        return kh_fail(KH_ERR_INVALID, "bad argument");
+    out[0] = KhLanesR16::row_in(wave, lane);
+    out[1] = KhLanesR16::col0(wave, lane);
+    out[2] = KhLanesR16::x_index(wave, lane);
+    out[3] = KhLanesR16::landing_lane(lane);
+    out[4] = KhLanesR16::row_out(wave, lane);
+    out[5] = KhLanesR16::writer(lane) ? 1 : 0;
+    out[6] = KhLanesR16::half(wave);
+    return KH_OK;
+}
+
 static int ell_layout(int32_t N, int32_t n_ops, const kh_csr *ops_host, int32_t *E_out, int32_t *Ec_out, int32_t *off_out,
                       kh_cdouble *vals_out, int32_t E_cap, bool global) {
     if (ops_host == nullptr || E_out == nullptr || Ec_out == nullptr || n_ops < 1 || N < 1)
