@@ -7,6 +7,7 @@ scaled and per-objective operators; objectives without one of their controls; Hi
 Test infrastructure (it imports ``oracle/``): run on a GPU box,
 
     python tests/fuzz_parity.py [--seconds 300] [--seed 1] [--cases 0] [--level sweeps|optimize] [--regimes] [--drop-any] [--nonselfadjoint] [--short-grids]
+                                 [--bounded-constrained]
 
 prints one line per case (kernel, shape, largest deviation) and a summary; exit code 1 if any case is off by more than
 the tolerance of tests/test_hip_parity.py (1e-12, 1e-11 in Liouville space).  ``tests/test_hip_parity.py::
@@ -20,6 +21,10 @@ random subset of the controls of the drawn ``config_c5`` problems by operators t
 ``anti``: tests/test_nonselfadjoint_controls.py), by a third generator of its own.  ``--short-grids`` (sweeps level) cuts
 every drawn problem's grid to nt = 2 or 3 with update shapes, guess pulses and step widths of ``helpers.grid_ends`` (the
 drawn ones vanish at both ends of the grid: tests/test_grid_ends.py), decided by a fourth generator of its own.
+``--bounded-constrained`` (sweeps level) gives every drawn problem random pulse parametrizations with bounds from its guess
+and a random Hermitian D with a linear shape, and runs one parametrized update sweep and one backward sweep with the
+source against the two restatements (tests/parametrization_cases.py, tests/constraint_cases.py), by a fifth generator of
+its own (tests/test_bounded_constrained_axes.py).
 """
 import argparse
 import os
@@ -265,6 +270,108 @@ def run_case(spec, fmt):
         eng.close()
 
 
+def draw_kinds(rng_bc, pulses):
+    """``--bounded-constrained``: a random kind (tests/parametrization_cases.py) per control with bounds from its guess --
+    ``tanh`` bounds that hold the guess with a margin of 10 ... 100 % of max|guess|, not symmetric; ``tanhsq`` where the
+    guess is >= 0, ``square`` where it is > 0."""
+    out = []
+    for p in pulses:
+        p = np.asarray(p, dtype=np.float64)
+        m = float(np.abs(p).max()) or 1.0
+        kind = str(rng_bc.choice(['none', 'linear', 'tanh', 'tanh'] + (['tanhsq'] if p.min() >= 0.0 else []) +
+                                 (['square'] if p.min() > 0.0 else [])))
+        margin, where = 1.1 + 0.9 * rng_bc.random(), 2.0 * rng_bc.random() - 1.0
+        if kind == 'tanh':
+            shift = 0.9 * (margin - 1.0) * where
+            out.append(('tanh', (shift - margin) * m, (shift + margin) * m))
+        elif kind == 'tanhsq':
+            out.append(('tanhsq', margin * m))
+        elif kind == 'linear':
+            out.append(('linear', (1.0 if where >= 0.0 else -1.0) * (0.5 + margin), 0.3 * m * where))
+        else:
+            out.append(None if kind == 'none' else ('square',))
+    return out
+
+
+def bounded_constrained_inputs(rng_bc, spec):
+    """``--bounded-constrained``, host side: the drawn kinds, u and f' under the guess, lambda_a in u, the source of a random
+    Hermitian D with the shape s_b(t) = c_0 + c_1 t / T on the states of a "previous iteration", norms != 1, and the two
+    restated sweeps.  ``rng_bc`` is NOT the generator of :func:`draw`."""
+    import constraint_cases as cc
+    import parametrization_cases as pc
+
+    prob = spec_to_oracle(spec)
+    gp, S, lam = oracle_controls(spec)
+    kinds = draw_kinds(rng_bc, gp)
+    u_guess = [pc.inverse(k, p) for k, p in zip(kinds, gp)]
+    dfdu = [pc.dfdu(k, u) for k, u in zip(kinds, u_guess)]
+    # (the update moves the pulse by about f'^2 S / lambda Im D: lambda_a in u keeps it what the drawn problem was made for)
+    lam_u = [x * max(1.0, float(np.abs(c).max()) ** 2) for x, c in zip(lam, dfdu)]
+    chi_T = spec.target / np.linalg.norm(spec.target, axis=1)[:, None]
+    norms = np.full(spec.K, 0.3 * min(1.0, 8.0 / spec.K) * min(1.0, 4.0 / spec.L))  # (run_case)
+    if spec.is_super:
+        norms *= 0.02
+    D = configs.herm(rng_bc, prob.N, 1.0)
+    lambda_b, c0, c1 = -(0.5 + 2.0 * rng_bc.random()), 0.3 + rng_bc.random(), 2.0 * rng_bc.random() - 1.0
+    t0, t1 = spec.tlist[0], spec.tlist[-1]
+    older = [p * (1.0 + 0.1 * rng_bc.standard_normal(np.shape(p))) for p in gp]
+    src_norms = 0.2 + 0.7 * rng_bc.random(spec.K)
+    with hp.MemoExpm():
+        states = ko.forward_propagation(prob, older, store=True)[1]
+        W = cc.source(D, cc.factors(lambda_b, spec.tlist, lambda t: c0 + c1 * (t - t0) / (t1 - t0)), states)
+        ref_chi = ko.backward_sweep(prob, chi_T, gp)
+        opt, u, psi_T, g_a = pc.update_sweep(prob, ref_chi, norms, u_guess, kinds, S, lam_u)
+        src_chi = cc.backward_sweep(prob, chi_T, gp, W, src_norms)
+    return dict(prob=prob, gp=gp, S=S, lam=lam_u, kinds=kinds, u_guess=np.array(u_guess), dfdu=np.array(dfdu), chi_T=chi_T,
+                norms=norms, W=W, src_norms=src_norms, chi=ref_chi, opt=np.array(opt), u=np.array(u), psi_T=psi_T,
+                g_a=np.array(g_a), src_chi=src_chi)
+
+
+def run_bounded_constrained_case(rng_bc, spec, fmt):
+    """``--bounded-constrained``: largest deviations of one parametrized update sweep (pulses, u, final states, g_a) and of
+    one backward sweep with a source from the restatements; an engine that takes no parametrization says so in the kernel
+    tag and runs nothing."""
+    import scipy.sparse as sp
+    import torch
+
+    import parametrization_cases as pc
+    from krotov_amd import _lib
+    from krotov_amd.engine import HipKrotovEngine
+    from krotov_amd.parametrization import PulseParameters
+
+    r = bounded_constrained_inputs(rng_bc, spec)
+    ops = [[spec.H0[k]] + [spec.Hc[k][l] for l in range(spec.L)] for k in range(spec.K)]
+    if fmt == 'csr':
+        ops = [[None if o is None else sp.csr_matrix(o) for o in row] for row in ops]
+    eng = HipKrotovEngine(ops, np.diff(spec.tlist), is_super=spec.is_super)
+    try:
+        pulses = np.array(r['gp'])
+        kind, a, b = PulseParameters([pc.to_product(k) for k in r['kinds']], r['gp']).device_kinds
+        u_opt = torch.full(pulses.shape, float('nan'), dtype=torch.float64, device=eng.device)
+        try:
+            eng.set_parametrization(kind, a, b, r['u_guess'], r['dfdu'], u_opt)
+        except _lib.KrotovHipError as exc:
+            if exc.code != _lib.KH_ERR_UNSUPPORTED:
+                raise
+            return eng.kernel + ' (no parametrization)', {'skipped': 0.0}
+        chi = eng.backward(r['chi_T'], pulses)
+        opt, psi_T, g_a = eng.forward_update(chi, r['norms'], spec.init, pulses, np.array(r['S']), np.array(r['lam']))
+        eng.check()
+        src = eng.backward_source(r['chi_T'], pulses, r['W'], r['src_norms'])
+        eng.check()
+        kinds = ','.join('none' if k is None else k[0] for k in r['kinds'])
+        return '%s [%s]' % (eng.kernel, kinds), {
+            'chi': np.abs(chi.cpu().numpy() - r['chi']).max(),
+            'opt': np.abs(opt.cpu().numpy() - r['opt']).max() / max(1.0, np.abs(r['opt']).max()),
+            'u': np.abs(u_opt.cpu().numpy() - r['u']).max() / max(1.0, np.abs(r['u']).max()),
+            'psi_T': np.abs(psi_T.cpu().numpy() - r['psi_T']).max(),
+            'g_a': np.abs(g_a.cpu().numpy() - r['g_a']).max() / max(1.0, np.abs(r['g_a']).max()),
+            'src': np.abs(src.cpu().numpy() - r['src_chi']).max() / max(1.0, np.abs(r['src_chi']).max()),
+        }
+    finally:
+        eng.close()
+
+
 def run_optimize_case(spec, fmt, rng):
     """Two iterations of ``krotov_amd.optimize_pulses`` on the GPU against ``oracle.optimize``: a random chi constructor
     (``chis_re / ss / sm``; ``chis_hs`` for density matrices), first or second order (the reference's notebook-07 sigma with
@@ -301,7 +408,7 @@ def run_optimize_case(spec, fmt, rng):
 
 
 def fuzz(seed, seconds=None, cases=None, verbose=True, level='sweeps', regimes=False, drop_any=False, stats=None,
-         nonselfadjoint=False, short_grids=False):
+         nonselfadjoint=False, short_grids=False, bounded_constrained=False):
     """Run random cases until `seconds` have passed or `cases` are done; returns (number run, list of failures).
     ``stats``: a dict that receives how many cases had an absent control (``'absent'``) and how many of those had one
     control (``'absent_L1'``), and how many a control that is not self-adjoint (``'nonselfadjoint'``)."""
@@ -310,9 +417,12 @@ def fuzz(seed, seconds=None, cases=None, verbose=True, level='sweeps', regimes=F
     rng_drop = np.random.default_rng([int(seed), 0xd709]) if drop_any and level == 'sweeps' else None  # (likewise)
     rng_nsa = np.random.default_rng([int(seed), 0x5ad1]) if nonselfadjoint and level == 'sweeps' else None  # (likewise)
     rng_short = np.random.default_rng([int(seed), 0x2e9d]) if short_grids and level == 'sweeps' else None  # (likewise)
+    rng_bc = np.random.default_rng([int(seed), 0xbc0d]) if bounded_constrained and level == 'sweeps' else None  # (likewise)
     counts = {'absent': 0, 'absent_L1': 0}
     if rng_nsa is not None:  # (the key only where it was asked for: the older tests compare the whole dict)
         counts['nonselfadjoint'] = 0
+    if rng_bc is not None:  # (likewise: the engines that took no parametrization, whose case ran nothing)
+        counts['no_parametrization'] = 0
     t0 = time.time()
     done, failures, by_kernel = 0, [], {}
     while True:
@@ -343,6 +453,9 @@ def fuzz(seed, seconds=None, cases=None, verbose=True, level='sweeps', regimes=F
                 liouville = obj.fmt == 'lindblad' or bool(np.any(obj.is_super))
                 tol = 1e-11 if liouville or ' ramp ' in tag else 1e-12  # (as tests/test_series_regimes.py)
                 kernel, dev = run_regime_case(obj, theta_max)
+            elif rng_bc is not None:
+                kernel, dev = run_bounded_constrained_case(rng_bc, spec, fmt)
+                counts['no_parametrization'] += 1 if kernel.endswith('(no parametrization)') else 0
             elif level == 'optimize':
                 kernel, dev = run_optimize_case(spec, fmt, rng)
             else:
@@ -386,7 +499,12 @@ if __name__ == '__main__':
     ap.add_argument('--short-grids', action='store_true',
                     help="every drawn problem on nt = 2 or 3 grid points with shapes, pulses and step widths that do not vanish "
                          "at the ends (helpers.grid_ends); decided by a separate generator (sweeps level)")
+    ap.add_argument('--bounded-constrained', action='store_true',
+                    help="every drawn problem gets random pulse parametrizations (bounds from its guess) and a random Hermitian D "
+                         "with a linear shape: one parametrized update sweep and one backward sweep with the source against the "
+                         "restatements; decided by a separate generator (sweeps level)")
     a = ap.parse_args()
     n, bad = fuzz(a.seed, seconds=None if a.cases else a.seconds, cases=a.cases or None, level=a.level, regimes=a.regimes,
-                  drop_any=a.drop_any, nonselfadjoint=a.nonselfadjoint, short_grids=a.short_grids)
+                  drop_any=a.drop_any, nonselfadjoint=a.nonselfadjoint, short_grids=a.short_grids,
+                  bounded_constrained=a.bounded_constrained)
     sys.exit(1 if bad else 0)
