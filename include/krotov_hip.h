@@ -37,12 +37,12 @@
  *     workgroup without an objective writes nothing.  CSR: indptr [N+1], indices [nnz], data [nnz]; every index read
  *     from them must be a valid column.  Memory next to an extent may hold anything, NaN included, and may be unmapped.
  *   Inputs are never written: operator arrays, CSR arrays, expectation operators, pulses, shapes, lambda, norms,
- *     sigma, init, targets, chi_T, fw_prev_dev, u_guess_dev, dfdu_dev, src_store_dev and chi_norms_dev of
+ *     sigma, init, targets, bell_dev, invariants_dev, chi_T, fw_prev_dev, u_guess_dev, dfdu_dev, src_store_dev and chi_norms_dev of
  *     kh_backward_store_source, ops_table_dev (and the operators it points to), factors_dev and in_store_dev of
  *     kh_apply_store -- and chi_store_dev in the update sweeps (kh_forward_update, kh_update_*), which only
  *     kh_backward_store / kh_backward_store_source write.  Outputs are the arguments marked OUT
  *     (and states_dev, psi_T_dev, chi_store_dev of the plain sweeps, tau_dev, out_dev, chi_T_dev, chi_norms_dev,
- *     partial_dev); fw_store_dev and u_opt_dev are outputs of the update sweeps while set.  A sweep writes its outputs
+ *     J_dev, partial_dev); fw_store_dev and u_opt_dev are outputs of the update sweeps while set.  A sweep writes its outputs
  *     in full (replica engines: the active replicas' slices only, kh_set_active_replicas) and never reads what they
  *     held before it (kh_update_begin ... kh_update_end count as one sweep: opt_dev and g_a_dev are carried from
  *     call to call).
@@ -499,6 +499,40 @@ int kh_chi_boundary(kh_engine *engine, const kh_cdouble *targets_dev,
                     const kh_cdouble *psi_T_dev, const kh_cdouble *c_dev,
                     const kh_cdouble *d_dev, kh_cdouble *chi_T_dev,
                     double *chi_norms_dev, void *stream);
+
+/* Boundary co-states of the two gate functionals in the LOCAL INVARIANTS of a two-qubit gate, normalised for the backward
+ * sweep: the perfect-entangler functional and the distance to a target gate up to single-qubit gates (the
+ * chi_constructors the reference's notebook 07 and its how-tos take from the weylchamber package, run per iteration on
+ * the host; krotov_amd/functionals.py: PerfectEntanglerChi, LocalInvariantsChi).  A gate is 4 consecutive objectives
+ * k = 4 g ... 4 g + 3, the propagated Bell states; M = K / 4 gates (an ensemble, or one per replica).  With the Bell
+ * states B_i and U[i][k] = <B_i|psi_{4g+k}(T)> (4 x 4):
+ *   m = U^T U,  t = tr m,  d = det U,  G = t^2 / (16 d),  H = (t^2 - tr m^2) / (4 d),  g3 = Re H
+ *   KH_LI_PE:  F = g3 |G| - Re G                  J_G = g3 conj(G) / (2 |G|) - 1/2 (the first term 0 at |G| = 0),  J_H = |G| / 2
+ *   KH_LI_LI:  F = |G - G_O|^2 + (g3 - g3_O)^2    J_G = conj(G - G_O),  J_H = g3 - g3_O
+ *   J = (1 - w) F + w (1 - tr(U^+ U) / 4)                                              (w = unitarity_weight in [0, 1])
+ *   dG/dU = t U / (4 d) - G U^-T,   dH/dU = (t U - U m) / d - H U^-T
+ *   D = dJ / d conj U = (1 - w) conj(J_G dG/dU + J_H dH/dU) - (w / 4) U
+ *   v_k = -scale sum_i D[i][k] B_i,   chi_T[4g+k] = v_k / ||v_k||_2,   chi_norms[4g+k] = ||v_k||_2,   J[g] = J
+ * (scale: the 1/M of a functional that is the mean over an ensemble of M gates; 1 for independent gates).  J is the raw
+ * value: negative inside the polyhedron of perfect entanglers.  A zero v_k gives a zero row and norm 0.  A singular U --
+ * |d| <= 1e-10 (||U||_F / 2)^4, or not a number -- gives zero rows, norms 0 and J[g] = NaN.
+ *   psi_T_dev       [K][N]
+ *   bell_dev        [4][N] shared by all gates, or [K/4][4][N] with bell_per_gate != 0
+ *   mode            KH_LI_PE or KH_LI_LI
+ *   invariants_dev  KH_LI_LI: (Re G_O, Im G_O, g3_O) as [3] doubles, or [K/4][3] with invariants_per_gate != 0;
+ *                   KH_LI_PE: not read, may be NULL
+ *   chi_T_dev [K][N], chi_norms_dev [K], J_dev [K/4]  OUT
+ * One wavefront per gate, every sum in a fixed order: results are bitwise repeatable and do not depend on where in the
+ * batch a gate sits.  Any engine of kh_engine_create, _csr or _replicas in Hilbert space (K, N come from the engine; the
+ * kernel family does not matter); a replica engine needs K_r divisible by 4 and honours kh_set_active_replicas: an
+ * inactive replica's slices of all three outputs keep what they held.  Decided before any HIP call: KH_ERR_INVALID for a
+ * NULL argument, K (K_r) not divisible by 4, an unknown mode, w outside [0, 1]; KH_ERR_UNSUPPORTED for Liouville-space
+ * engines (is_super), kh_engine_create_lindblad and kh_engine_create_mixed -- those keep the host constructor. */
+enum kh_li_mode { KH_LI_PE = 0, KH_LI_LI = 1 };
+int kh_chi_local_invariants(kh_engine *engine, const kh_cdouble *psi_T_dev, const kh_cdouble *bell_dev,
+                            int32_t bell_per_gate, int32_t mode, const double *invariants_dev,
+                            int32_t invariants_per_gate, double unitarity_weight, double scale,
+                            kh_cdouble *chi_T_dev, double *chi_norms_dev, double *J_dev, void *stream);
 
 /* After synchronising the stream: returns KH_ERR_TIMEOUT if an in-kernel
  * exchange gave up since the last call (outputs are then invalid), else 0. */

@@ -22,13 +22,13 @@ from .conversions import pulse_onto_tlist
 from .info_hooks import chain
 from .mixed import layout_of
 from .mu import derivative_wrt_pulse
-from .propagators import HipExpm, LindbladExpm, expm
+from .propagators import HipExpm, expm
 from .result import Result
 
 __all__ = ['optimize_pulses_batch']
 
-# the limits of the replica kernels (krotov_amd/csrc/kh_mini.h: KH_MINI_N, KH_MINI_MAXK; kh_replica.h: 1..4 controls)
-REPLICA_NMAX, REPLICA_KMAX, REPLICA_LMAX = 16, 8, 4
+# the limits of the replica kernels (defined next to the checks that use them)
+REPLICA_NMAX, REPLICA_KMAX, REPLICA_LMAX = _opt.REPLICA_NMAX, _opt.REPLICA_KMAX, _opt.REPLICA_LMAX
 
 
 def _free_device_bytes():
@@ -93,24 +93,16 @@ def _batch_obstacle(problems, reps, propagator):
         return "the propagator is not expm / HipExpm"
     if any(_opt._parametrizations(r.objectives, r.pulse_options) is not None for r in reps):
         return "a pulse parametrization ('parametrization' in pulse_options)"
-    if isinstance(propagator, LindbladExpm) or any(len(o.c_ops) > 0 for r in reps for o in r.objectives):
-        return "objectives with c_ops"
-    if isinstance(propagator, HipExpm) and getattr(propagator, 'sparse', False):
-        return "sparse propagator"
+    for r in reps:  # (what a single problem must be: shared with optimize_pulses' own use of a one-replica engine)
+        reason = _opt._replica_kind_obstacle(r.objectives, propagator)
+        if reason is not None:
+            return reason
     layouts = [layout_of(r.objectives, propagator) for r in reps]
-    if any(lay.mixed for lay in layouts):
-        return "objectives of mixed dimension or kind"
     shapes = {(len(r.objectives), lay.stride, lay.kinds[0], r.L, len(r.tlist)) for r, lay in zip(reps, layouts)}
     if len(shapes) > 1:
         return "the problems differ in shape"
     Kr, N, _, L, _ = next(iter(shapes))
-    if N > REPLICA_NMAX:
-        return "N = %d > %d" % (N, REPLICA_NMAX)
-    if Kr > REPLICA_KMAX:
-        return "%d objectives per problem > %d" % (Kr, REPLICA_KMAX)
-    if L < 1 or L > REPLICA_LMAX:
-        return "%d controls (1..%d)" % (L, REPLICA_LMAX)
-    return None
+    return _opt._replica_size_obstacle(N, Kr, L)
 
 
 class _ReplicaBackend:
@@ -161,6 +153,8 @@ class _ReplicaBackend:
             self.fw_next = t.zeros((self.K, self.nt, self.N), dtype=c128, device=dev)
             self.sigma_host = np.zeros((self.B, self.nt - 1))
         self.last_chi = None
+        self.propagator = propagator
+        self.li_out = self.li_J = None  # kh_chi_local_invariants: (chi_T, chi_norms, J) of the batch; J alone
         self._uploads = {}
         self._mask = None
 
@@ -214,14 +208,46 @@ class _ReplicaBackend:
             return None
         return self.engine.tau(self.targets, self.psi_T).cpu().numpy().reshape(self.B, self.Kr)
 
-    def iterate(self, chi_T, chi_norms, chi_coef):
+    def local_invariants_route(self, constructor):
+        """The arguments of ``kh_chi_local_invariants`` for ``constructor`` (a ``PerfectEntanglerChi`` /
+        ``LocalInvariantsChi``) when the batch forms its co-states on the device -- Hilbert space, one gate (K_r = 4) per
+        replica --, else None with the reason logged: the object is then called on the host, replica by replica."""
+        reason = args = None
+        if self.is_super:
+            reason = "super-operators"
+        elif self.Kr != 4:
+            reason = "%d objectives per problem, not one gate of 4" % self.Kr
+        else:
+            for r in self.reps:
+                constructor.check_objectives(self.Kr, r.objectives)  # (ValueError, as the host call would raise)
+            layout = layout_of(self.reps[0].objectives, self.propagator)
+            args = constructor.device_arguments(lambda state: layout.vector(state, 0))
+            if args is None:
+                reason = "the canonical basis does not match the state dimension %d" % self.N
+        if reason is not None:
+            logging.getLogger('krotov').info("%s: co-states on the host (%s)", type(constructor).__name__, reason)
+        return args
+
+    def iterate(self, chi_T, chi_norms, chi_coef, chi_li=None):
         """One backward and one update sweep over the active replicas.  chi_coef = (c, d), (K,) each: the boundary
-        co-states are formed on the device (kh_chi_boundary); else chi_T (K, N) normalised, chi_norms (K,), host."""
+        co-states are formed on the device (kh_chi_boundary); chi_li: what :meth:`local_invariants_route` returned
+        (kh_chi_local_invariants, one gate per replica; the J per replica is left in ``self.li_J``); else chi_T (K, N)
+        normalised, chi_norms (K,), host."""
         t, eng = self.torch, self.engine
         guess = self._pulses('pulses', 'guess_pulses')
         shapes = self._pulses('shapes', 'shape_arrays')
         lambdas = self._cached_upload('lambdas', np.array([np.asarray(r.lambda_vals, dtype=np.float64) for r in self.reps]))
-        if chi_coef is not None:
+        if chi_li is not None:
+            mode, bell, invariants, weight = chi_li
+            if self.li_out is None:  # (persistent: a frozen replica's slices keep their last values)
+                self.li_out = (t.zeros((self.K, self.N), dtype=t.complex128, device=eng.device),
+                               t.zeros((self.K,), dtype=t.float64, device=eng.device),
+                               t.zeros((self.B,), dtype=t.float64, device=eng.device))
+            self.set_active()
+            chi_loc, norms_loc, self.li_J = eng.chi_local_invariants(
+                self.psi_T, self._cached_upload('li_bell', bell, t.complex128), mode,
+                self._cached_upload('li_invariants', invariants), weight, 1.0, out=self.li_out)
+        elif chi_coef is not None:
             c_dev = self._cached_upload('chi_c', np.ascontiguousarray(chi_coef[0], dtype=np.complex128), t.complex128)
             d_dev = self._cached_upload('chi_d', np.ascontiguousarray(chi_coef[1], dtype=np.complex128), t.complex128)
             chi_loc, norms_loc = eng.chi_boundary(self.targets, self.psi_T, c_dev, d_dev)
@@ -305,17 +331,24 @@ def _run_batch(reps, propagator, chi_constructor, check_convergence, info_hook, 
             r.finish()
             r.forward_states0 = None
 
+    # the perfect-entangler / local-invariants functional itself (not a function wrapping it): co-states on the device
+    chi_li = None
+    if isinstance(chi_constructor, _functionals._LocalInvariantsFunctional):
+        chi_li = backend.local_invariants_route(chi_constructor)
+
     # ---- main loop (optimize.py:392-581): one iteration of every active replica per pass
     while any(r.active for r in reps):
         tic = time.time()
         coefs = None
-        if backend.targets is not None:
+        if chi_li is None and backend.targets is not None:
             coefs = [_functionals.chi_coefficients(chi_constructor, r.weights, r.tau_vals, Kr) for r in reps]
             if any(c is None for c in coefs):
                 coefs = None
         chi_T = chi_norms = chi_coef = None
         host_chis = {}  # (second order, a user's chi_constructor: what sigma.refresh gets, per replica)
-        if coefs is not None:
+        if chi_li is not None:
+            pass
+        elif coefs is not None:
             chi_coef = (np.concatenate([c[0] for c in coefs]), np.concatenate([c[1] for c in coefs]))
         else:  # a user's chi_constructor: on the host, per replica, as optimize_pulses does
             chi_T = np.zeros((backend.K, backend.N), dtype=np.complex128)
@@ -332,7 +365,9 @@ def _run_batch(reps, propagator, chi_constructor, check_convergence, info_hook, 
                 chi_T[b * Kr:(b + 1) * Kr] = np.array(vecs)
                 chi_norms[b * Kr:(b + 1) * Kr] = norms
                 host_chis[b] = ([chi / nrm for chi, nrm in zip(chis, norms)], norms)
-        opt_host, psi_host, g_a = backend.iterate(chi_T, chi_norms, chi_coef)
+        opt_host, psi_host, g_a = backend.iterate(chi_T, chi_norms, chi_coef, chi_li=chi_li)
+        if chi_li is not None:  # (a singular U_B of an active replica: ValueError)
+            chi_constructor.set_device_values(backend.li_J.cpu().numpy(), active=[r.active for r in reps])
         tau = backend.tau_vals()
         toc = time.time()
         chi_fetched = None
@@ -429,7 +464,11 @@ def optimize_pulses_batch(problems, *, propagator, chi_constructor, iter_stop=50
     ``Result`` is not touched again; the batch ends when no replica is active.  ``sigma``: None, or a sequence of B
     :class:`~krotov_amd.second_order.Sigma` objects -- the second-order update, replica b under ``sigma[b]``
     (``static_args['sigma']`` of its hooks), which is refreshed after every iteration that replica goes on from;
-    ``info_hook`` then gets ``forward_states`` / ``forward_states0`` of its replica.  A batch whose co-state store
+    ``info_hook`` then gets ``forward_states`` / ``forward_states0`` of its replica.  ``chi_constructor``: one of the four
+    built-in functionals, a :class:`~krotov_amd.functionals.PerfectEntanglerChi` /
+    :class:`~krotov_amd.functionals.LocalInvariantsChi` object (problems of one gate, 4 objectives: the co-states of the
+    whole batch in one ``kh_chi_local_invariants`` launch, ``.values[b]`` the functional of problem b) -- or any callable,
+    which is called on the host, problem by problem.  A batch whose co-state store
     (B K_r nt N 16 bytes; with ``sigma`` three such stores: chi and the two forward trajectories) exceeds a quarter of
     the free device memory is split into consecutive sub-batches of equal size.  Everything else runs the replicas one
     after another through ``optimize_pulses`` (logged once as ``"optimize_pulses_batch: sequential (<reason>)"`` on the

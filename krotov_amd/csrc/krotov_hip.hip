@@ -42,6 +42,7 @@
 #include "kh_ens.h"
 #include "kh_lind.h"
 #include "kh_expect.h"
+#include "kh_chi_li.h"
 // the parallel build (krotov_amd/build.py, -DKH_TU=KH_TU_MAIN): the sweep kernels are instantiated in the family units
 // (kh_tu.hip), here they are `extern template`; compiled by itself this file is the whole library in one unit
 #include "kh_instances.inc"
@@ -3274,6 +3275,42 @@ extern "C" int kh_chi_boundary(kh_engine *e, const kh_cdouble *targets_dev, cons
     kh_chi_kernel<<<blocks, 64 * waves_per_block, 0, (hipStream_t)stream>>>(
         (const cplx *)targets_dev, (const cplx *)psi_T_dev, (const cplx *)c_dev, (const cplx *)d_dev,
         (cplx *)chi_T_dev, chi_norms_dev, e->K, e->N);
+    KH_HIP(hipGetLastError());
+    return KH_OK;
+}
+
+// Boundary co-states of the perfect-entangler / local-invariants functionals (kh_chi_li.h): one wave per gate
+extern "C" int kh_chi_local_invariants(kh_engine *e, const kh_cdouble *psi_T_dev, const kh_cdouble *bell_dev,
+                                       int32_t bell_per_gate, int32_t mode, const double *invariants_dev,
+                                       int32_t invariants_per_gate, double unitarity_weight, double scale,
+                                       kh_cdouble *chi_T_dev, double *chi_norms_dev, double *J_dev, void *stream) {
+    if (e == nullptr || psi_T_dev == nullptr || bell_dev == nullptr || chi_T_dev == nullptr || chi_norms_dev == nullptr ||
+        J_dev == nullptr)
+        return kh_fail(KH_ERR_INVALID, "null argument");
+    if (mode != KH_LI_MODE_PE && mode != KH_LI_MODE_LI) return kh_fail(KH_ERR_INVALID, "mode = %d: KH_LI_PE or KH_LI_LI", mode);
+    if (mode == KH_LI_MODE_LI && invariants_dev == nullptr)
+        return kh_fail(KH_ERR_INVALID, "null argument: KH_LI_LI needs the target gate's invariants");
+    if (!(unitarity_weight >= 0.0 && unitarity_weight <= 1.0))
+        return kh_fail(KH_ERR_INVALID, "unitarity_weight must be in [0, 1]");
+    if (e->mixed || e->lind || e->is_super)
+        return kh_fail(KH_ERR_UNSUPPORTED, "the local-invariants functionals are defined on Hilbert-space states: "
+                                           "Liouville-space, Lindblad-form and mixed engines keep the host constructor");
+    if (e->K % 4 != 0 || (e->replicas > 0 && e->Kr % 4 != 0))
+        return kh_fail(KH_ERR_INVALID, "%d objectives%s: a gate is 4 consecutive objectives", e->replicas > 0 ? e->Kr : e->K,
+                       e->replicas > 0 ? " per replica" : "");
+    KhLiArgs a;
+    a.psi = (const cplx *)psi_T_dev, a.bell = (const cplx *)bell_dev, a.inv = invariants_dev;
+    a.chi = (cplx *)chi_T_dev, a.norms = chi_norms_dev, a.J = J_dev;
+    a.active = e->replicas > 0 ? e->active_mask() : nullptr;
+    a.M = e->K / 4, a.N = e->N;
+    a.gates_per_replica = e->replicas > 0 ? e->Kr / 4 : 1;
+    a.bell_per_gate = bell_per_gate != 0, a.inv_per_gate = invariants_per_gate != 0;
+    a.w = unitarity_weight, a.scale = scale;
+    const dim3 grid((unsigned)((a.M + KH_LI_WAVES - 1) / KH_LI_WAVES)), block(64 * KH_LI_WAVES);
+    if (mode == KH_LI_MODE_PE)
+        launch_plain<kh_chi_li_kernel<KH_LI_MODE_PE>>(grid, block, 0, (hipStream_t)stream, a);
+    else
+        launch_plain<kh_chi_li_kernel<KH_LI_MODE_LI>>(grid, block, 0, (hipStream_t)stream, a);
     KH_HIP(hipGetLastError());
     return KH_OK;
 }

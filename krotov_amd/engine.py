@@ -895,6 +895,43 @@ class HipKrotovEngine:
             norms.data_ptr(), self._stream()))
         return chi, norms
 
+    def chi_local_invariants(self, psi_T, bell, mode, invariants=None, unitarity_weight=0.0, scale=1.0, out=None):
+        """Normalised boundary co-states, their norms and the value J per gate of the perfect-entangler (``mode`` 'PE')
+        or local-invariants ('LI') functional (``kh_chi_local_invariants``; krotov_amd/functionals.py:
+        ``PerfectEntanglerChi``, ``LocalInvariantsChi``): ``(K, N)``, ``(K,)`` and ``(K / 4,)`` device tensors.
+        ``bell``: the Bell states, ``(4, N)`` for all gates or ``(K / 4, 4, N)``; ``invariants`` ('LI'):
+        ``(Re G_O, Im G_O, g3_O)`` of the target gate, ``(3,)`` or ``(K / 4, 3)``; ``scale``: the 1/M of an ensemble
+        mean.  ``out``: the three tensors to write into -- on a replica engine an inactive replica's slices keep what
+        they held.  A singular gate gives zero rows, norms 0 and J = NaN."""
+        M = max(1, self.K // 4)  # (K not divisible by 4: the library refuses, KH_ERR_INVALID)
+        modes = {'PE': 0, 'LI': 1, 0: 0, 1: 1}
+        if mode not in modes:
+            raise ValueError("mode must be 'PE' or 'LI', not %r" % (mode,))
+        psi_T = self._c(psi_T, (self.K, self.N))
+        bell = self.dev(bell, torch.complex128)
+        if tuple(bell.shape) not in ((4, self.N), (M, 4, self.N)):
+            raise ValueError("bell: expected shape %s or %s, got %s" % ((4, self.N), (M, 4, self.N), tuple(bell.shape)))
+        inv = None
+        if modes[mode] == 1:
+            if invariants is None:
+                raise ValueError("mode 'LI' needs the invariants (Re G_O, Im G_O, g3_O) of the target gate")
+            inv = self.dev(invariants, torch.float64)
+            if tuple(inv.shape) not in ((3,), (M, 3)):
+                raise ValueError("invariants: expected shape (3,) or %s, got %s" % ((M, 3), tuple(inv.shape)))
+        if out is None:
+            chi = self._empty((self.K, self.N), torch.complex128)
+            norms = self._empty((self.K,), torch.float64)
+            J = self._empty((M,), torch.float64)
+        else:
+            chi = self._out(out[0], (self.K, self.N), torch.complex128)
+            norms = self._out(out[1], (self.K,), torch.float64)
+            J = self._out(out[2], (M,), torch.float64)
+        _lib.check(self._lib.kh_chi_local_invariants(
+            self._handle, psi_T.data_ptr(), bell.data_ptr(), int(bell.dim() == 3), modes[mode],
+            None if inv is None else inv.data_ptr(), int(inv is not None and inv.dim() == 2), float(unitarity_weight),
+            float(scale), chi.data_ptr(), norms.data_ptr(), J.data_ptr(), self._stream()))
+        return chi, norms, J
+
     def check(self):
         """Synchronise and raise if an in-kernel exchange timed out."""
         torch.cuda.synchronize(self.device)

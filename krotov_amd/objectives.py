@@ -544,15 +544,9 @@ def _rho3(basis):
 def _li_pe_objectives(basis_states, gate, H, c_ops):
     """Bell-basis objectives for local-invariants / perfect-entangler
     optimisation (reference objectives.py:1035-1051)."""
-    if len(basis_states) != 4:
-        raise ValueError("Optimization towards a two-qubit gate requires 4 basis_states")
-    b = basis_states
-    psis = [
-        (b[0] + b[3]) / np.sqrt(2),
-        (1j * b[1] + 1j * b[2]) / np.sqrt(2),
-        (b[1] - b[2]) / np.sqrt(2),
-        (1j * b[0] - 1j * b[3]) / np.sqrt(2),
-    ]
+    from .functionals import bell_basis  # (the chi constructors of these objectives project onto the same states)
+
+    psis = bell_basis(basis_states)
     return [Objective(initial_state=psi, target=gate, H=H, c_ops=c_ops) for psi in psis]
 
 

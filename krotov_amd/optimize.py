@@ -518,19 +518,69 @@ def _operator_rows(objectives, pulses_mapping, L, convert, k0=0, k1=None):
     return ops, c_rows
 
 
+# the limits of the replica kernels (krotov_amd/csrc/kh_mini.h: KH_MINI_N, KH_MINI_MAXK; kh_replica.h: 1..4 controls)
+REPLICA_NMAX, REPLICA_KMAX, REPLICA_LMAX = 16, 8, 4
+
+
+def _replica_kind_obstacle(objectives, propagator):
+    """Why the KIND of one problem does not fit a replica engine (a short reason), or None.  With
+    ``_replica_size_obstacle``: what ``optimize_pulses_batch`` asks of every problem of a batch."""
+    if isinstance(propagator, list) or not (propagator is expm or isinstance(propagator, HipExpm)):
+        return "the propagator is not expm / HipExpm"
+    if isinstance(propagator, LindbladExpm) or any(len(o.c_ops) > 0 for o in objectives):
+        return "objectives with c_ops"
+    if isinstance(propagator, HipExpm) and getattr(propagator, 'sparse', False):
+        return "sparse propagator"
+    if layout_of(objectives, propagator).mixed:
+        return "objectives of mixed dimension or kind"
+    return None
+
+
+def _replica_size_obstacle(N, Kr, L):
+    """Why a problem of dimension N with Kr objectives and L controls exceeds the replica kernels, or None."""
+    if N > REPLICA_NMAX:
+        return "N = %d > %d" % (N, REPLICA_NMAX)
+    if Kr > REPLICA_KMAX:
+        return "%d objectives per problem > %d" % (Kr, REPLICA_KMAX)
+    if L < 1 or L > REPLICA_LMAX:
+        return "%d controls (1..%d)" % (L, REPLICA_LMAX)
+    return None
+
+
+def _one_gate_replica_form(objectives, propagator, n_controls, chi_constructor, process_group, other_features):
+    """Whether ``optimize_pulses`` runs this problem as a batch of one on a replica engine: one gate (4 Hilbert-space
+    objectives) under a ``PerfectEntanglerChi`` / ``LocalInvariantsChi`` object, of a kind and size a replica engine
+    takes, without parametrization, constraint, sharding or a skipped forward sweep
+    (``other_features``).  These are the problems run from many guesses at once; on the same kernels a batch's
+    ``results[b]`` is ``optimize_pulses(**problems[b])`` bit for bit (the one-wave kernels a problem of this size gets
+    under any other constructor round differently in the last bit).  The price: the replica kernels are somewhat slower
+    on a single problem."""
+    if not isinstance(chi_constructor, _functionals._LocalInvariantsFunctional) or len(objectives) != 4:
+        return False
+    if process_group is not None or other_features or _replica_kind_obstacle(objectives, propagator) is not None:
+        return False
+    layout = layout_of(objectives, propagator)
+    if layout.kinds[0]:  # (Liouville space: the co-states are not formed on the device)
+        return False
+    return _replica_size_obstacle(layout.stride, len(objectives), n_controls) is None
+
+
 class _HipBackend:
     """All objectives of this rank resident on one GPU."""
 
     device = True
 
     def __init__(self, objectives, pulses_mapping, tlist, n_controls, propagator, process_group=None,
-                 second_order=False, parametrized=False):
+                 second_order=False, parametrized=False, replica_form=False):
         import torch
 
         from .engine import HipKrotovEngine
 
         self.torch = torch
         self.group = process_group
+        # replica_form: the problem as a batch of ONE on a replica engine (``_one_gate_replica_form``) -- the kernels
+        # ``optimize_pulses_batch`` runs it on, so that a batch is, bit for bit, the loop over its problems
+        self.replica_form = replica_form
         self.objectives = objectives
         K_total = len(objectives)
         self.rank, self.world = 0, 1
@@ -586,6 +636,8 @@ class _HipBackend:
                           and getattr(p, 'row_split', None) is not None), None)
         if self.lindblad is not None:
             self.engine = HipKrotovEngine(ops, np.diff(tlist), c_ops=c_rows)
+        elif replica_form:
+            self.engine = HipKrotovEngine(ops, np.diff(tlist)[None, :], is_super=self.is_super, replicas=1)
         elif row_split is not None:
             self.engine = HipKrotovEngine(ops, np.diff(tlist), is_super=self.is_super, row_split=row_split)
         else:
@@ -637,8 +689,12 @@ class _HipBackend:
         cache[key] = (host.copy(), dev)
         return dev
 
+    def _per_control(self):
+        """Shape of the pulse-like arrays the engine takes: (L, nt - 1), on a replica engine (1, L, nt - 1)."""
+        return (1, self.L, self.nt - 1) if self.replica_form else (self.L, self.nt - 1)
+
     def _pulses(self, pulses, cached=False):
-        host = np.array(pulses, dtype=np.float64).reshape(self.L, self.nt - 1)
+        host = np.array(pulses, dtype=np.float64).reshape(self._per_control())
         if cached:  # (the guess of an iteration is normally the optimized pulse of the one before: still on the device)
             return self._cached_upload('pulses', host)
         return self.engine.dev(host, self.torch.float64)
@@ -728,11 +784,36 @@ class _HipBackend:
         self._src_store.copy_(eng.dev(W, t.complex128))
         return self._src_store
 
+    def local_invariants_route(self, constructor):
+        """``constructor`` (a ``PerfectEntanglerChi`` / ``LocalInvariantsChi``) when this backend forms its co-states on
+        the device (kh_chi_local_invariants: Hilbert space, one GPU, a dense or CSR engine), else None -- the object is
+        then called on the host like any user constructor; the reason is logged once."""
+        cached = self.__dict__.get('_li_route')
+        if cached is not None and cached[0] is constructor:
+            return constructor if cached[1] else None
+        reason = args = None
+        if self.group is not None:
+            reason = "process_group= (objectives sharded over GPUs)"
+        elif self.lindblad is not None or self.layout is not None or self.is_super:
+            reason = "super-operators or objectives of different dimension or kind"
+        elif self.fw_T_dev is None:
+            reason = "no forward propagation on the device (skip_initial_forward_propagation)"
+        else:
+            constructor.check_objectives(self.K_total, self.objectives)  # (ValueError, as the host call would raise)
+            args = constructor.device_arguments(lambda state: self.state_vector(state, 0))
+            if args is None:
+                reason = "the canonical basis does not match the state dimension %d" % self.N
+        if reason is not None:
+            logging.getLogger('krotov').info("%s: co-states on the host (%s)", type(constructor).__name__, reason)
+        self._li_route = (constructor, args)
+        return constructor if args is not None else None
+
     def iterate(self, chi_T, chi_norms, guess_pulses, lambda_vals, shape_arrays, sigma=None, chi_coef=None, par=None,
-                constraint=None):
+                constraint=None, chi_li=None):
         """chi_T: (K_total, N) normalised co-states (host); chi_norms (K_total,) -- or
         ``chi_coef = (c, d)``, (K_total,) each: chi_k(T) = c_k target_k + d_k phi_k(T) is
-        then formed and normalised on the device (kh_chi_boundary)."""
+        then formed and normalised on the device (kh_chi_boundary) -- or ``chi_li``: what
+        :meth:`local_invariants_route` returned (kh_chi_local_invariants)."""
         t = self.torch
         eng = self.engine
         guess = self._pulses(guess_pulses, cached=True)
@@ -740,8 +821,9 @@ class _HipBackend:
         # is ordered behind the kernels already in the stream and blocks the host until it is done -- issued between the
         # two sweeps it kept the update sweep's launch back until the backward sweep had finished (the GPU idled for
         # two copies and a launch per iteration).  Shapes and step widths rarely change: uploaded when they do.
-        shapes = self._cached_upload('shapes', np.array(shape_arrays, dtype=np.float64).reshape(self.L, self.nt - 1))
-        lambdas = self._cached_upload('lambdas', np.asarray(lambda_vals, dtype=np.float64))
+        shapes = self._cached_upload('shapes', np.array(shape_arrays, dtype=np.float64).reshape(self._per_control()))
+        lambdas = self._cached_upload('lambdas', np.asarray(lambda_vals, dtype=np.float64).reshape(
+            (1, self.L) if self.replica_form else (self.L,)))
         if sigma is not None or constraint is not None:
             # sigma at the interval mid-points (optimize.py:451-452); phi under the guess pulses is
             # the trajectory the previous sweep stored, the running one goes to the other buffer
@@ -754,7 +836,10 @@ class _HipBackend:
                 sig = np.array([sigma(tl[n] + 0.5 * (tl[n + 1] - tl[n])) for n in range(self.nt - 1)], dtype=np.float64)
             if self.fw_next is None:
                 self.fw_next = t.empty_like(self.fw_prev)
-            eng.set_second_order(self.fw_prev, self.fw_next, sig)
+            if self.replica_form:
+                eng.set_second_order_replicas(self.fw_prev, self.fw_next, sig[None, :])
+            else:
+                eng.set_second_order(self.fw_prev, self.fw_next, sig)
         u_opt = None
         if par is not None:
             # pulse parametrizations: the update sweep reads u under the guess and f'(u) in place of the guess pulses,
@@ -770,6 +855,12 @@ class _HipBackend:
             c_dev = self._cached_upload('chi_c', np.ascontiguousarray(c[self.k0:self.k1], dtype=np.complex128), t.complex128)
             d_dev = self._cached_upload('chi_d', np.ascontiguousarray(d[self.k0:self.k1], dtype=np.complex128), t.complex128)
             chi_loc, norms_loc = eng.chi_boundary(self.targets, psi, c_dev, d_dev)
+        elif chi_li is not None:
+            # (J stays on the device until the sweeps are launched: fetching it here would idle the GPU for a round trip)
+            mode, bell, invariants, weight = self._li_route[1]
+            chi_loc, norms_loc, li_J = eng.chi_local_invariants(
+                self.fw_T_dev, self._cached_upload('li_bell', bell, t.complex128), mode,
+                self._cached_upload('li_invariants', invariants), weight, 4.0 / self.K_total)
         else:
             chi_loc = eng.dev(chi_T[self.k0:self.k1], t.complex128)
             norms_loc = eng.dev(np.asarray(chi_norms, dtype=np.float64)[self.k0:self.k1], t.float64)
@@ -780,7 +871,15 @@ class _HipBackend:
         else:
             self.chi_store = self._split_guarded(lambda: eng.backward(chi_loc, guess, out=self.chi_store), 'backward')
         done = False
-        if self.group is None:
+        if self.replica_form:
+            # a replica engine's update sweep is one workgroup per problem and waits on no other workgroup (no exchange
+            # slots, no polling, no residency requirement: DESIGN.md 3.9): it cannot time out, and the ladder below --
+            # set_update_workgroups, the per-interval form -- is not written for it (the engine answers
+            # KH_ERR_UNSUPPORTED to both).  Any error here is a real one.
+            opt, psi_T, g_a = eng.forward_update(self.chi_store, norms_loc, self.init, guess, shapes, lambdas)
+            eng.check()
+            done = True
+        elif self.group is None:
             if self._single_launch_ok:
                 # the single-launch sweep needs all its workgroups resident at once; if the GPU could not give it that
                 # (CUs held by another stream or process: its in-kernel exchange times out; or the device cannot hold
@@ -895,9 +994,13 @@ class _HipBackend:
                 self.chi_store, norms_loc, self.init, guess, shapes, lambdas, all_reduce, graph_chunk=chunk)
         self.fw_T_dev = psi_T
         eng.check()
+        if chi_li is not None:
+            chi_li.set_device_values(li_J.cpu().numpy())  # (a singular U_B: ValueError)
         fw_states_T = self._final_states(psi_T)
         opt_host = opt.cpu().numpy()
         self.__dict__.setdefault('_uploads', {})['pulses'] = (opt_host.copy(), opt)  # (the next iteration's guess, if unchanged)
+        if self.replica_form:  # ((1, L, nt - 1) and (1, L): the one replica's rows)
+            opt_host, g_a = opt_host[0], g_a[0]
         optimized = [opt_host[l].copy() for l in range(self.L)]
         if par is not None:
             par.commit(u_opt.cpu().numpy(), optimized)
@@ -1078,7 +1181,10 @@ def optimize_pulses(
 
     if device_path:
         backend = _HipBackend(objectives, pulses_mapping, tlist, len(guess_pulses), propagator, process_group,
-                              second_order=second_order, parametrized=par is not None)
+                              second_order=second_order, parametrized=par is not None,
+                              replica_form=default_norm and _one_gate_replica_form(
+                                  objectives, propagator, len(guess_pulses), chi_constructor, process_group,
+                                  par is not None or constraint is not None or skip_initial_forward_propagation))
     else:
         backend = _PluginBackend(
             objectives, adjoint_objectives, pulses_mapping, tlist, propagators, storage, parallel_map, mu, overlap
@@ -1148,14 +1254,18 @@ def optimize_pulses(
         logger.info("Started Krotov iteration %d", krotov_iteration)
         tic = time.time()
 
-        chi_T = chi_coef = None
-        if device_path and default_norm and backend.targets is not None:
+        chi_T = chi_coef = chi_li = None
+        if device_path and default_norm and isinstance(chi_constructor, _functionals._LocalInvariantsFunctional):
+            # the perfect-entangler / local-invariants functional itself (not a function wrapping it): the 4 x 4
+            # algebra per gate and the co-states on the device
+            chi_li = backend.local_invariants_route(chi_constructor)
+        elif device_path and default_norm and backend.targets is not None:
             # built-in functionals: chi_k(T) is formed and normalised on the device from K scalars
             # (no K-long Python loop, phi_k(T) and chi_k(T) stay in HBM)
             if backend.fw_T_dev is not None or chi_constructor is _functionals.chis_re:
                 chi_coef = _functionals.chi_coefficients(
                     chi_constructor, backend.weights, tau_vals, len(objectives))
-        if chi_coef is not None:
+        if chi_coef is not None or chi_li is not None:
             chi_states = chi_norms = None
         else:
             chi_states = chi_constructor(fw_states_T=fw_states_T, objectives=objectives, tau_vals=tau_vals)
@@ -1177,7 +1287,7 @@ def optimize_pulses(
         if device_path:
             backward_states, optimized_pulses, fw_states_T, g_a, forward_states = backend.iterate(
                 chi_T, chi_norms, guess_pulses, lambda_vals, shape_arrays, sigma=sigma, chi_coef=chi_coef, par=par,
-                constraint=constraint,
+                constraint=constraint, chi_li=chi_li,
             )
         else:
             backward_states, optimized_pulses, fw_states_T, g_a, forward_states = backend.iterate(
