@@ -76,6 +76,7 @@ class _Replica:
         self.forward_states0 = None  # second order: this replica's view of the trajectory under its guess pulses
         self.active = True
         self.iteration = 0
+        self.li_values = None  # PerfectEntanglerChi / LocalInvariantsChi: the J per gate of this problem's last co-states
 
     def finish(self):
         """What ``optimize_pulses`` does behind its loop; the Result is not touched afterwards."""
@@ -275,8 +276,10 @@ class _ReplicaBackend:
         return opt_host, self.psi_T.cpu().numpy(), self.g_a.cpu().numpy()
 
 
-def _run_batch(reps, propagator, chi_constructor, check_convergence, info_hook, store_all_pulses):
+def _run_batch(reps, propagator, chi_constructor, check_convergence, info_hook, store_all_pulses, first=0):
+    """One (sub-)batch on one replica engine; ``first``: the index of ``reps[0]`` among the caller's problems."""
     logger = logging.getLogger('krotov')
+    li_object = isinstance(chi_constructor, _functionals._LocalInvariantsFunctional)
     second_order = reps[0].sigma is not None
     backend = _ReplicaBackend(reps, propagator, second_order=second_order)
     Kr = backend.Kr
@@ -333,7 +336,7 @@ def _run_batch(reps, propagator, chi_constructor, check_convergence, info_hook, 
 
     # the perfect-entangler / local-invariants functional itself (not a function wrapping it): co-states on the device
     chi_li = None
-    if isinstance(chi_constructor, _functionals._LocalInvariantsFunctional):
+    if li_object:
         chi_li = backend.local_invariants_route(chi_constructor)
 
     # ---- main loop (optimize.py:392-581): one iteration of every active replica per pass
@@ -358,6 +361,8 @@ def _run_batch(reps, propagator, chi_constructor, check_convergence, info_hook, 
                 if not r.active:
                     continue
                 chis = chi_constructor(fw_states_T=r.fw_states_T, objectives=r.objectives, tau_vals=r.tau_vals)
+                if li_object:  # (the object itself on the host: it has just left this problem's J in .values)
+                    r.li_values = np.array(chi_constructor.values, dtype=np.float64)
                 norms = [chi.norm() if hasattr(chi, 'norm') else float(np.linalg.norm(np.asarray(chi))) for chi in chis]
                 vecs = [layout.vector(chi / nrm, k) for k, (chi, nrm) in enumerate(zip(chis, norms))]
                 if any(v is None for v in vecs):
@@ -368,6 +373,9 @@ def _run_batch(reps, propagator, chi_constructor, check_convergence, info_hook, 
         opt_host, psi_host, g_a = backend.iterate(chi_T, chi_norms, chi_coef, chi_li=chi_li)
         if chi_li is not None:  # (a singular U_B of an active replica: ValueError)
             chi_constructor.set_device_values(backend.li_J.cpu().numpy(), active=[r.active for r in reps])
+            for b, r in enumerate(reps):  # (one gate per replica; a frozen one keeps the J of its last co-states)
+                if r.active:
+                    r.li_values = chi_constructor.values[b:b + 1].copy()
         tau = backend.tau_vals()
         toc = time.time()
         chi_fetched = None
@@ -376,7 +384,7 @@ def _run_batch(reps, propagator, chi_constructor, check_convergence, info_hook, 
             if not r.active:
                 continue
             r.iteration += 1
-            logger.info("Finished Krotov iteration %d of problem %d", r.iteration, b)
+            logger.info("Finished Krotov iteration %d of problem %d", r.iteration, first + b)
             r.optimized_pulses = [opt_host[b, l].copy() for l in range(r.L)]
             r.fw_states_T = states_of(psi_host, b)
             r.g_a_integrals[:] = g_a[b]
@@ -468,7 +476,12 @@ def optimize_pulses_batch(problems, *, propagator, chi_constructor, iter_stop=50
     built-in functionals, a :class:`~krotov_amd.functionals.PerfectEntanglerChi` /
     :class:`~krotov_amd.functionals.LocalInvariantsChi` object (problems of one gate, 4 objectives: the co-states of the
     whole batch in one ``kh_chi_local_invariants`` launch, ``.values[b]`` the functional of problem b) -- or any callable,
-    which is called on the host, problem by problem.  A batch whose co-state store
+    which is called on the host, problem by problem.  Under such an object, AFTER THE CALL RETURNS ``.values`` holds the
+    J of every gate of every problem in problem order -- of each problem's last construction of the co-states, a problem
+    that stopped early included (NaN for one that ran no iteration) --, whichever way the batch ran: as one batch, in
+    sub-batches or one problem after another; entry b is what ``optimize_pulses`` on problem b alone leaves.  WHILE A
+    SPLIT OR SEQUENTIAL BATCH IS STILL RUNNING, a hook sees in ``.values`` the running part only: the sub-batch's
+    problems, or the one problem of the sequential loop.  A batch whose co-state store
     (B K_r nt N 16 bytes; with ``sigma`` three such stores: chi and the two forward trajectories) exceeds a quarter of
     the free device memory is split into consecutive sub-batches of equal size.  Everything else runs the replicas one
     after another through ``optimize_pulses`` (logged once as ``"optimize_pulses_batch: sequential (<reason>)"`` on the
@@ -487,14 +500,33 @@ def optimize_pulses_batch(problems, *, propagator, chi_constructor, iter_stop=50
     if B == 0:
         return []
 
+    li_object = isinstance(chi_constructor, _functionals._LocalInvariantsFunctional)
+
+    def publish_values(per_problem):
+        """``.values`` of a ``PerfectEntanglerChi`` / ``LocalInvariantsChi`` object over the whole batch: every
+        problem's J per gate in problem order (NaN for a problem that formed no co-states)."""
+        if li_object and any(v is not None for v in per_problem):
+            chi_constructor.values = np.concatenate([
+                np.full(len(p['objectives']) // 4, np.nan) if v is None else np.asarray(v, dtype=np.float64)
+                for p, v in zip(problems, per_problem)])
+
     def sequential(reason):
         logger.info("optimize_pulses_batch: sequential (%s)", reason)
-        return [_opt.optimize_pulses(
-            p['objectives'], p['pulse_options'], p['tlist'], propagator=propagator, chi_constructor=chi_constructor,
-            iter_stop=iter_stop, check_convergence=check_convergence, info_hook=info_hook,
-            modify_params_after_iter=modify_params_after_iter, store_all_pulses=store_all_pulses, continue_from=prev,
-            sigma=sig)
-            for p, prev, sig in zip(problems, previous, sigmas)]
+        results, values = [], []
+        before = chi_constructor.values if li_object else None
+        for p, prev, sig in zip(problems, previous, sigmas):
+            if li_object:  # (every call leaves its own problem's J there: collected, published together at the end)
+                chi_constructor.values = None
+            results.append(_opt.optimize_pulses(
+                p['objectives'], p['pulse_options'], p['tlist'], propagator=propagator, chi_constructor=chi_constructor,
+                iter_stop=iter_stop, check_convergence=check_convergence, info_hook=info_hook,
+                modify_params_after_iter=modify_params_after_iter, store_all_pulses=store_all_pulses, continue_from=prev,
+                sigma=sig))
+            values.append(None if not li_object or chi_constructor.values is None else np.array(chi_constructor.values))
+        if li_object:
+            chi_constructor.values = before  # (it stays what it was where no problem formed co-states)
+        publish_values(values)
+        return results
 
     if isinstance(propagator, list) or not (propagator is expm or isinstance(propagator, HipExpm)):
         return sequential("the propagator is not expm / HipExpm")
@@ -521,5 +553,6 @@ def optimize_pulses_batch(problems, *, propagator, chi_constructor, iter_stop=50
             logger.info("optimize_pulses_batch: %d sub-batches of %d problems (the co-state store of all %d would take "
                         "%d bytes, a quarter of the free device memory is %d)", B // size, size, B, B * per_replica, free // 4)
     for i in range(0, B, size):
-        _run_batch(reps[i:i + size], propagator, chi_constructor, check_convergence, info_hook, store_all_pulses)
+        _run_batch(reps[i:i + size], propagator, chi_constructor, check_convergence, info_hook, store_all_pulses, first=i)
+    publish_values([r.li_values for r in reps])
     return [r.result for r in reps]

@@ -373,7 +373,12 @@ class _LocalInvariantsFunctional:
     fill it) -- that is, of the states an iteration STARTS from: after ``optimize_pulses`` returns it holds J of the
     states before the last update, one iteration behind what an ``info_hook`` saw.  ``.J_T(fw_states_T, ...)`` evaluates
     the functional of the states it is given and leaves ``.values`` alone, so a hook cannot overwrite the per-gate
-    (per-problem, in a batch) values of the run with those of the one problem it was called for."""
+    (per-problem, in a batch) values of the run with those of the one problem it was called for.
+
+    IN A BATCH (``optimize_pulses_batch``) ``.values`` holds, after the call returns, the J of every gate of every problem
+    in problem order, whether the problems ran as one batch, in sub-batches or one after another; a problem frozen early
+    keeps the J of its last co-states.  While a split or sequential batch is still running, a hook finds there the
+    running part only -- the problems of the sub-batch on the device, or the one problem of the sequential loop."""
 
     mode = None
 

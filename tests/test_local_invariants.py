@@ -289,7 +289,8 @@ def test_local_invariants_towards_cnot_through_the_oracle():
 # ---------------------------------------------------------------------------
 @pytest.fixture
 def li_double(monkeypatch):
-    """``ReplicaEngineDoubleSO`` with ``chi_local_invariants`` (the host algebra, gate by gate, honouring the mask)."""
+    """``ReplicaEngineDoubleSO`` with ``chi_local_invariants`` (the host algebra, gate by gate, honouring the mask and
+    reporting a singular gate the kernel's way)."""
     import torch
 
     import krotov_amd.engine as engine_mod
@@ -312,8 +313,12 @@ def li_double(monkeypatch):
             for g in range(M):
                 if not mask[g * 4 // (self.Kr if self.replicas else 4)]:
                     continue
-                value, D = functionals._li_gate_terms(bell.conj() @ psi[4 * g:4 * g + 4].T, MODES.index(mode), target,
-                                                      unitarity_weight)
+                try:
+                    value, D = functionals._li_gate_terms(bell.conj() @ psi[4 * g:4 * g + 4].T, MODES.index(mode), target,
+                                                          unitarity_weight)
+                except ValueError:  # a singular U_B, as the kernel reports it: zero rows, norms 0, J NaN
+                    chi[4 * g:4 * g + 4], norms[4 * g:4 * g + 4], J[g] = 0.0, 0.0, float('nan')
+                    continue
                 rows = -scale * (D.T @ bell)
                 nrm = np.linalg.norm(rows, axis=1)
                 chi[4 * g:4 * g + 4] = torch.from_numpy(rows / nrm[:, None])
