@@ -156,20 +156,12 @@ class _ReplicaBackend:
         self.last_chi = None
         self.propagator = propagator
         self.li_out = self.li_J = None  # kh_chi_local_invariants: (chi_T, chi_norms, J) of the batch; J alone
-        self._uploads = {}
+        self._uploads = _opt._UploadCache(eng, t.float64)
         self._mask = None
-
-    def _cached_upload(self, key, host, dtype=None):
-        hit = self._uploads.get(key)
-        if hit is not None and hit[0].shape == host.shape and np.array_equal(hit[0], host):
-            return hit[1]
-        dev = self.engine.dev(host, dtype if dtype is not None else self.torch.float64)
-        self._uploads[key] = (host.copy(), dev)
-        return dev
 
     def _pulses(self, key, which):
         host = np.array([np.array(getattr(r, which), dtype=np.float64).reshape(self.L, self.nt - 1) for r in self.reps])
-        return self._cached_upload(key, host)
+        return self._uploads.get(key, host)
 
     def set_active(self):
         mask = [1 if r.active else 0 for r in self.reps]
@@ -237,7 +229,7 @@ class _ReplicaBackend:
         t, eng = self.torch, self.engine
         guess = self._pulses('pulses', 'guess_pulses')
         shapes = self._pulses('shapes', 'shape_arrays')
-        lambdas = self._cached_upload('lambdas', np.array([np.asarray(r.lambda_vals, dtype=np.float64) for r in self.reps]))
+        lambdas = self._uploads.get('lambdas', np.array([np.asarray(r.lambda_vals, dtype=np.float64) for r in self.reps]))
         if chi_li is not None:
             mode, bell, invariants, weight = chi_li
             if self.li_out is None:  # (persistent: a frozen replica's slices keep their last values)
@@ -246,11 +238,11 @@ class _ReplicaBackend:
                                t.zeros((self.B,), dtype=t.float64, device=eng.device))
             self.set_active()
             chi_loc, norms_loc, self.li_J = eng.chi_local_invariants(
-                self.psi_T, self._cached_upload('li_bell', bell, t.complex128), mode,
-                self._cached_upload('li_invariants', invariants), weight, 1.0, out=self.li_out)
+                self.psi_T, self._uploads.get('li_bell', bell, t.complex128), mode,
+                self._uploads.get('li_invariants', invariants), weight, 1.0, out=self.li_out)
         elif chi_coef is not None:
-            c_dev = self._cached_upload('chi_c', np.ascontiguousarray(chi_coef[0], dtype=np.complex128), t.complex128)
-            d_dev = self._cached_upload('chi_d', np.ascontiguousarray(chi_coef[1], dtype=np.complex128), t.complex128)
+            c_dev = self._uploads.get('chi_c', np.ascontiguousarray(chi_coef[0], dtype=np.complex128), t.complex128)
+            d_dev = self._uploads.get('chi_d', np.ascontiguousarray(chi_coef[1], dtype=np.complex128), t.complex128)
             chi_loc, norms_loc = eng.chi_boundary(self.targets, self.psi_T, c_dev, d_dev)
         else:
             chi_loc = eng.dev(chi_T, t.complex128)
@@ -272,7 +264,7 @@ class _ReplicaBackend:
         eng.forward_update(self.chi_store, norms_loc, self.init, guess, shapes, lambdas, out=(self.opt, self.psi_T, self.g_a))
         eng.check()
         opt_host = self.opt.cpu().numpy()
-        self._uploads['pulses'] = (opt_host.copy(), self.opt.clone())  # (the next guess of the replicas that go on)
+        self._uploads.record('pulses', opt_host, self.opt.clone())  # (the next guess of the replicas that go on)
         return opt_host, self.psi_T.cpu().numpy(), self.g_a.cpu().numpy()
 
 

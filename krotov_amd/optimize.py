@@ -47,10 +47,10 @@ from .conversions import (
     pulse_options_dict_to_list,
 )
 from ._lib import KrotovHipError as _KrotovHipError
-from ._lib import KH_ERR_TIMEOUT as _KH_ERR_TIMEOUT, KH_ERR_UNSUPPORTED as _KH_ERR_UNSUPPORTED
+from ._lib import KH_ERR_TIMEOUT as _KH_ERR_TIMEOUT
+from ._update_ladder import UpdateLadder as _UpdateLadder, leave_row_split as _leave_row_split
 
 _KH_MAX_CONTROLS = 32  # KH_GEN_MAX_L of krotov_amd/csrc/kh_common.h (the register-resident kernel families: 8)
-_FULL_GRID_PROBE_EVERY = 16  # update sweeps in a row on a reduced grid before the full one is tried again
 from .info_hooks import chain
 from .mixed import Layout, LindbladLayout, layout_of, lindblad_layout_of
 from .mu import derivative_wrt_pulse
@@ -565,6 +565,28 @@ def _one_gate_replica_form(objectives, propagator, n_controls, chi_constructor, 
     return _replica_size_obstacle(layout.stride, len(objectives), n_controls) is None
 
 
+class _UploadCache:
+    """Device copies of small host arrays that are usually the same from one iteration to the next (every upload from
+    pageable memory blocks the host for ~30 us with the GPU idle)."""
+
+    def __init__(self, engine, dtype):
+        self.engine, self.dtype = engine, dtype  # (dtype: the one of an upload that names none)
+        self._held = {}  # key -> (host array as uploaded, its device copy)
+
+    def get(self, key, host, dtype=None):
+        hit = self._held.get(key)
+        if hit is not None and hit[0].shape == host.shape and np.array_equal(hit[0], host):
+            return hit[1]
+        dev = self.engine.dev(host, dtype if dtype is not None else self.dtype)
+        self._held[key] = (host.copy(), dev)
+        return dev
+
+    def record(self, key, host, dev):
+        """``dev`` is already the device copy of ``host`` (a sweep's output that was fetched): no upload if the caller
+        comes back with the same values."""
+        self._held[key] = (host.copy(), dev)
+
+
 class _HipBackend:
     """All objectives of this rank resident on one GPU."""
 
@@ -663,13 +685,13 @@ class _HipBackend:
         self.fw_T_dev = None
         self.fw_prev = self.fw_next = None  # second order: phi(t_n) of the last / the running iteration
         self.last_chi = None
+        self._uploads = _UploadCache(self.engine, torch.float64)
+        self._src_store = None  # W_k(t_n) of a state-dependent constraint (_constraint_source)
+        self._li_route = None  # (constructor, its device arguments or None): local_invariants_route, decided once
+        self._ladder = _UpdateLadder(self.engine)  # (one GPU) the single-launch update sweep's retries
         # device-side exchange over peer-mapped windows (xGMI) when every rank can set it up;
         # otherwise (or after a failed sweep) one RCCL all-reduce per interval
-        self._single_launch_ok = True  # (one GPU) until the single-launch update sweep has failed for good
-        self._single_launch_failures = 0
-        self._update_grid = None  # workgroups of the single-launch update sweep after a retry (None: the engine's choice)
-        self._reduced_in_a_row = 0
-        self._last_good_grid = None  # the reduced grid that got through the last time the full one timed out
+        self._p2p_synced = False  # until the ranks have been lined up before the first peer-window sweep
         self.p2p = False
         self.engine.p2p_why = "KH_P2P=0" if self.world > 1 else None
         if self.world > 1 and os.environ.get('KH_P2P', '1') != '0':
@@ -678,17 +700,6 @@ class _HipBackend:
                 "cross-GPU exchange: %s", "peer windows" if self.p2p else "RCCL all-reduce per interval")
 
     # -- helpers -----------------------------------------------------------
-    def _cached_upload(self, key, host, dtype=None):
-        """Device copy of a small host array that is usually the same from one iteration to the next (every upload from
-        pageable memory blocks the host for ~30 us with the GPU idle)."""
-        cache = self.__dict__.setdefault('_uploads', {})
-        hit = cache.get(key)
-        if hit is not None and hit[0].shape == host.shape and np.array_equal(hit[0], host):
-            return hit[1]
-        dev = self.engine.dev(host, dtype if dtype is not None else self.torch.float64)
-        cache[key] = (host.copy(), dev)
-        return dev
-
     def _per_control(self):
         """Shape of the pulse-like arrays the engine takes: (L, nt - 1), on a replica engine (1, L, nt - 1)."""
         return (1, self.L, self.nt - 1) if self.replica_form else (self.L, self.nt - 1)
@@ -696,7 +707,7 @@ class _HipBackend:
     def _pulses(self, pulses, cached=False):
         host = np.array(pulses, dtype=np.float64).reshape(self._per_control())
         if cached:  # (the guess of an iteration is normally the optimized pulse of the one before: still on the device)
-            return self._cached_upload('pulses', host)
+            return self._uploads.get('pulses', host)
         return self.engine.dev(host, self.torch.float64)
 
     def state_vector(self, state, k):
@@ -720,10 +731,7 @@ class _HipBackend:
         except _KrotovHipError as exc:
             if exc.code != _KH_ERR_TIMEOUT:
                 raise
-            logging.getLogger('krotov').info(
-                "row split %d: the %s sweep timed out (%s); redoing it, and going on, with one workgroup per objective",
-                eng.row_split, what, exc)
-            eng.set_row_split(1)
+            _leave_row_split(eng, what, exc)
             return sweep()
 
     def _gather_rows(self, local):
@@ -767,7 +775,7 @@ class _HipBackend:
         tensor: formed on the device (kh_apply_store) for the built-in quadratic cost, on the host from the fetched
         trajectory for a ``source()`` of the user's own."""
         t, eng = self.torch, self.engine
-        if self.__dict__.get('_src_store') is None:
+        if self._src_store is None:
             self._src_store = t.empty_like(self.fw_prev)
         if isinstance(constraint, QuadraticStateConstraint) and type(constraint).source is QuadraticStateConstraint.source:
             ops = constraint.operators(self.objectives)
@@ -775,7 +783,7 @@ class _HipBackend:
                 if op is not None and op.shape != (self.N, self.N):
                     raise ValueError("state_dependent_constraint: D of objective %d has shape %s, the states have "
                                      "dimension %d" % (k, op.shape, self.N))
-            factors = self._cached_upload('sdc_factors', np.asarray(constraint.factors(self.tlist_host), dtype=np.float64))
+            factors = self._uploads.get('sdc_factors', np.asarray(constraint.factors(self.tlist_host), dtype=np.float64))
             return eng.apply_store(ops, factors, self.fw_prev, out=self._src_store)
         W = np.asarray(constraint.source(self.fw_prev.cpu().numpy(), self.tlist_host), dtype=np.complex128)
         if W.shape != tuple(self.fw_prev.shape):
@@ -788,7 +796,7 @@ class _HipBackend:
         """``constructor`` (a ``PerfectEntanglerChi`` / ``LocalInvariantsChi``) when this backend forms its co-states on
         the device (kh_chi_local_invariants: Hilbert space, one GPU, a dense or CSR engine), else None -- the object is
         then called on the host like any user constructor; the reason is logged once."""
-        cached = self.__dict__.get('_li_route')
+        cached = self._li_route
         if cached is not None and cached[0] is constructor:
             return constructor if cached[1] else None
         reason = args = None
@@ -814,191 +822,157 @@ class _HipBackend:
         ``chi_coef = (c, d)``, (K_total,) each: chi_k(T) = c_k target_k + d_k phi_k(T) is
         then formed and normalised on the device (kh_chi_boundary) -- or ``chi_li``: what
         :meth:`local_invariants_route` returned (kh_chi_local_invariants)."""
-        t = self.torch
-        eng = self.engine
+        second_order = sigma is not None or constraint is not None
         guess = self._pulses(guess_pulses, cached=True)
         # every upload of the iteration BEFORE the first sweep is launched: a host-to-device copy from pageable memory
         # is ordered behind the kernels already in the stream and blocks the host until it is done -- issued between the
         # two sweeps it kept the update sweep's launch back until the backward sweep had finished (the GPU idled for
         # two copies and a launch per iteration).  Shapes and step widths rarely change: uploaded when they do.
-        shapes = self._cached_upload('shapes', np.array(shape_arrays, dtype=np.float64).reshape(self._per_control()))
-        lambdas = self._cached_upload('lambdas', np.asarray(lambda_vals, dtype=np.float64).reshape(
+        shapes = self._uploads.get('shapes', np.array(shape_arrays, dtype=np.float64).reshape(self._per_control()))
+        lambdas = self._uploads.get('lambdas', np.asarray(lambda_vals, dtype=np.float64).reshape(
             (1, self.L) if self.replica_form else (self.L,)))
-        if sigma is not None or constraint is not None:
-            # sigma at the interval mid-points (optimize.py:451-452); phi under the guess pulses is
-            # the trajectory the previous sweep stored, the running one goes to the other buffer
-            # (a state-dependent constraint without sigma: sigma = 0 -- the second-order kernels are the ones that store
-            # phi(t_n), which the next iteration's source is formed from)
-            tl = np.asarray(self.tlist_host)
-            if sigma is None:
-                sig = np.zeros(self.nt - 1)
-            else:
-                sig = np.array([sigma(tl[n] + 0.5 * (tl[n + 1] - tl[n])) for n in range(self.nt - 1)], dtype=np.float64)
-            if self.fw_next is None:
-                self.fw_next = t.empty_like(self.fw_prev)
-            if self.replica_form:
-                eng.set_second_order_replicas(self.fw_prev, self.fw_next, sig[None, :])
-            else:
-                eng.set_second_order(self.fw_prev, self.fw_next, sig)
-        u_opt = None
-        if par is not None:
-            # pulse parametrizations: the update sweep reads u under the guess and f'(u) in place of the guess pulses,
-            # writes u_new next to the pulses f(u_new) it propagates with (kh_set_parametrization)
-            kind, a, b = par.device_kinds
-            u_guess = eng.dev(np.array(par.u, dtype=np.float64).reshape(self.L, self.nt - 1), t.float64)
-            dfdu = eng.dev(par.dfdu().reshape(self.L, self.nt - 1), t.float64)
-            u_opt = t.empty_like(u_guess)
-            eng.set_parametrization(kind, a, b, u_guess, dfdu, u_opt)
+        if second_order:
+            self._set_second_order(sigma)
+        u_opt = self._set_parametrization(par) if par is not None else None
+        chi_loc, norms_loc, li_J = self._boundary_costates(chi_T, chi_norms, chi_coef, chi_li)
+        self.last_chi = (chi_loc, norms_loc)
+        self._backward(chi_loc, norms_loc, guess, constraint)
+        opt, psi_T, g_a = self._update((self.chi_store, norms_loc, self.init, guess, shapes, lambdas))
+        self.fw_T_dev = psi_T
+        self.engine.check()
+        if chi_li is not None:
+            chi_li.set_device_values(li_J.cpu().numpy())  # (a singular U_B: ValueError)
+        return self._results(opt, psi_T, g_a, par, u_opt, second_order)
+
+    # -- the steps of an iteration, in the order ``iterate`` takes them (uploads: none after ``_backward`` has begun its sweep) --
+    def _set_second_order(self, sigma):
+        """sigma at the interval mid-points (optimize.py:451-452); phi under the guess pulses is the trajectory the
+        previous sweep stored, the running one goes to the other buffer.  (A state-dependent constraint without sigma:
+        sigma = 0 -- the second-order kernels are the ones that store phi(t_n), which the next iteration's source is
+        formed from.)"""
+        tl = np.asarray(self.tlist_host)
+        if sigma is None:
+            sig = np.zeros(self.nt - 1)
+        else:
+            sig = np.array([sigma(tl[n] + 0.5 * (tl[n + 1] - tl[n])) for n in range(self.nt - 1)], dtype=np.float64)
+        if self.fw_next is None:
+            self.fw_next = self.torch.empty_like(self.fw_prev)
+        if self.replica_form:
+            self.engine.set_second_order_replicas(self.fw_prev, self.fw_next, sig[None, :])
+        else:
+            self.engine.set_second_order(self.fw_prev, self.fw_next, sig)
+
+    def _set_parametrization(self, par):
+        """Pulse parametrizations: the update sweep reads u under the guess and f'(u) in place of the guess pulses,
+        writes u_new -- the tensor returned -- next to the pulses f(u_new) it propagates with (kh_set_parametrization)."""
+        t, eng = self.torch, self.engine
+        kind, a, b = par.device_kinds
+        u_guess = eng.dev(np.array(par.u, dtype=np.float64).reshape(self.L, self.nt - 1), t.float64)
+        dfdu = eng.dev(par.dfdu().reshape(self.L, self.nt - 1), t.float64)
+        u_opt = t.empty_like(u_guess)
+        eng.set_parametrization(kind, a, b, u_guess, dfdu, u_opt)
+        return u_opt
+
+    def _boundary_costates(self, chi_T, chi_norms, chi_coef, chi_li):
+        """This rank's normalised chi_k(T) and their norms on the device, from whichever of the three forms ``iterate``
+        was given, and the functional's value J of the local-invariants form (a device tensor; else None)."""
+        t, eng = self.torch, self.engine
         if chi_coef is not None:
             c, d = chi_coef
             psi = self.fw_T_dev if self.fw_T_dev is not None else self.init  # (d == 0 without phi(T))
-            c_dev = self._cached_upload('chi_c', np.ascontiguousarray(c[self.k0:self.k1], dtype=np.complex128), t.complex128)
-            d_dev = self._cached_upload('chi_d', np.ascontiguousarray(d[self.k0:self.k1], dtype=np.complex128), t.complex128)
+            c_dev = self._uploads.get('chi_c', np.ascontiguousarray(c[self.k0:self.k1], dtype=np.complex128), t.complex128)
+            d_dev = self._uploads.get('chi_d', np.ascontiguousarray(d[self.k0:self.k1], dtype=np.complex128), t.complex128)
             chi_loc, norms_loc = eng.chi_boundary(self.targets, psi, c_dev, d_dev)
-        elif chi_li is not None:
+            return chi_loc, norms_loc, None
+        if chi_li is not None:
             # (J stays on the device until the sweeps are launched: fetching it here would idle the GPU for a round trip)
             mode, bell, invariants, weight = self._li_route[1]
-            chi_loc, norms_loc, li_J = eng.chi_local_invariants(
-                self.fw_T_dev, self._cached_upload('li_bell', bell, t.complex128), mode,
-                self._cached_upload('li_invariants', invariants), weight, 4.0 / self.K_total)
-        else:
-            chi_loc = eng.dev(chi_T[self.k0:self.k1], t.complex128)
-            norms_loc = eng.dev(np.asarray(chi_norms, dtype=np.float64)[self.k0:self.k1], t.float64)
-        self.last_chi = (chi_loc, norms_loc)
+            return eng.chi_local_invariants(
+                self.fw_T_dev, self._uploads.get('li_bell', bell, t.complex128), mode,
+                self._uploads.get('li_invariants', invariants), weight, 4.0 / self.K_total)
+        chi_loc = eng.dev(chi_T[self.k0:self.k1], t.complex128)
+        norms_loc = eng.dev(np.asarray(chi_norms, dtype=np.float64)[self.k0:self.k1], t.float64)
+        return chi_loc, norms_loc, None
+
+    def _backward(self, chi_loc, norms_loc, guess, constraint):
+        """The backward sweep into ``self.chi_store``, with the source term of a state-dependent constraint if there is
+        one.  The last place of an iteration that may upload anything: see ``iterate``."""
+        eng = self.engine
         if constraint is not None:
             src = self._constraint_source(constraint)
             self.chi_store = eng.backward_source(chi_loc, guess, src, norms_loc, out=self.chi_store)
         else:
             self.chi_store = self._split_guarded(lambda: eng.backward(chi_loc, guess, out=self.chi_store), 'backward')
-        done = False
+
+    def _update(self, args):
+        """The update sweep over ``args``, the six tensors of ``forward_update``, by the transport this backend is on;
+        returns ``(opt, psi_T, g_a)``."""
         if self.replica_form:
             # a replica engine's update sweep is one workgroup per problem and waits on no other workgroup (no exchange
-            # slots, no polling, no residency requirement: DESIGN.md 3.9): it cannot time out, and the ladder below --
+            # slots, no polling, no residency requirement: DESIGN.md 3.9): it cannot time out, and the retry ladder --
             # set_update_workgroups, the per-interval form -- is not written for it (the engine answers
             # KH_ERR_UNSUPPORTED to both).  Any error here is a real one.
-            opt, psi_T, g_a = eng.forward_update(self.chi_store, norms_loc, self.init, guess, shapes, lambdas)
-            eng.check()
-            done = True
-        elif self.group is None:
-            if self._single_launch_ok:
-                # the single-launch sweep needs all its workgroups resident at once; if the GPU could not give it that
-                # (CUs held by another stream or process: its in-kernel exchange times out; or the device cannot hold
-                # the grid at all), redo it on HALF the workgroups, each walking through twice the objectives (about
-                # twice the time: kh_set_update_workgroups), then on an eighth, and only then interval by interval -- one
-                # launch each, nothing waits inside a kernel, ten times the time -- like the sharded path does.  A
-                # reduced grid that got through stays (INTEGRATION.md 4).
-                # Anything else than a timeout / "cannot be resident" is a real error.
-                grid = self._update_grid  # (None: the engine's own choice)
-                if grid is not None and self._reduced_in_a_row >= _FULL_GRID_PROBE_EVERY:
-                    # a co-tenant may have gone away: one sweep on the full grid again (at worst one more timeout)
-                    eng.set_update_workgroups(0)
-                    grid, self._reduced_in_a_row = None, 0
-                rungs = 0
-                while not done:
-                    try:
-                        opt, psi_T, g_a = eng.forward_update(self.chi_store, norms_loc, self.init, guess, shapes, lambdas)
-                        eng.check()
-                        done = True
-                    except _KrotovHipError as exc:
-                        if exc.code not in (_KH_ERR_TIMEOUT, _KH_ERR_UNSUPPORTED):
-                            raise
-                        if exc.code == _KH_ERR_TIMEOUT and getattr(eng, 'row_split', 1) > 1:
-                            # first rung: one workgroup per objective again (kept from here on); then the ladder below
-                            logging.getLogger('krotov').info(
-                                "row split %d: the update sweep timed out (%s); redoing it, and going on, with one "
-                                "workgroup per objective", eng.row_split, exc)
-                            eng.set_row_split(1)
-                            continue
-                        try:
-                            # every rung costs a timed-out sweep (KH_TIMEOUT_MS, 1 s by default): two of them at most --
-                            # half the workgroups (what gets through next to a stream holding half of the device), then
-                            # an eighth -- before the form that cannot time out
-                            rungs += 1
-                            if rungs > 2:
-                                raise _KrotovHipError("two reduced grids timed out", _KH_ERR_UNSUPPORTED)
-                            full = eng.set_update_workgroups(0)
-                            if grid is None and self._last_good_grid is not None and self._last_good_grid < full:
-                                nxt = self._last_good_grid  # (what got through the last time this happened)
-                            else:
-                                nxt = (grid if grid is not None else full) // (2 if rungs == 1 else 4)
-                            if nxt < 1:
-                                raise _KrotovHipError("no smaller grid", _KH_ERR_UNSUPPORTED)
-                            grid = eng.set_update_workgroups(nxt)
-                            logging.getLogger('krotov').warning(
-                                "single-launch update sweep failed (%s); repeating it on %d workgroups", exc, grid)
-                        except _KrotovHipError as exc2:
-                            if exc2.code != _KH_ERR_UNSUPPORTED:
-                                raise
-                            # back to the engine's own grid, in the engine AND in what this object remembers of it
-                            grid = None
-                            eng.set_update_workgroups(0)
-                            self._update_grid, self._reduced_in_a_row, self._last_good_grid = None, 0, None
-                            self._single_launch_failures += 1
-                            # a co-tenant may go away, but not after three sweeps in a row
-                            if exc.code == _KH_ERR_UNSUPPORTED or self._single_launch_failures >= 3:
-                                self._single_launch_ok = False
-                            logging.getLogger('krotov').warning(
-                                "single-launch update sweep failed (%s); repeating it with one launch per interval%s", exc,
-                                "" if self._single_launch_ok else " (and staying with that form)")
-                            break
-                if done:
-                    self._single_launch_failures = 0
-                    if grid is not None:
-                        # a reduced grid got through: it is KEPT (trying the full one first would cost a timed-out sweep
-                        # per iteration for as long as the co-tenant stays); the full grid gets its chance again after
-                        # _FULL_GRID_PROBE_EVERY sweeps in a row on the reduced one
-                        self._reduced_in_a_row += 1
-                        self._last_good_grid = grid
-                    else:
-                        self._reduced_in_a_row = 0
-                    self._update_grid = grid
-            if not done:
-                opt, psi_T, g_a = eng.forward_update_sharded(
-                    self.chi_store, norms_loc, self.init, guess, shapes, lambdas, lambda x: None, graph_chunk=0)
-                done = True
-        elif self.p2p:
-            # one persistent launch per rank; the per-GPU sums cross the node inside the kernel
-            failed = 0
-            if not self.__dict__.get('_p2p_synced', False):
-                # the ranks' kernels wait for each other INSIDE the sweep (bounded by KH_TIMEOUT_MS): before the first
-                # one, line the ranks up -- set-up time (imports, engine creation, operator norms) differs by more than
-                # that bound between ranks; afterwards they stay within a sweep's jitter of each other
-                t.cuda.synchronize(eng.device)
-                self.dist.barrier(group=self.group)
-                self._p2p_synced = True
-            try:
-                opt, psi_T, g_a = eng.forward_update(self.chi_store, norms_loc, self.init, guess, shapes, lambdas)
-                eng.check()
-            except Exception as exc:  # exchange timeout: every rank falls back together
-                logging.getLogger('krotov').warning("cross-GPU exchange failed (%s)", exc)
-                eng.p2p_why = "peer windows dropped after a failed sweep on this rank: %s" % exc
-                failed = 1
-            flag = t.tensor([failed], dtype=t.int32, device=eng.device)
-            self.dist.all_reduce(flag, op=self.dist.ReduceOp.MAX, group=self.group)
-            if int(flag.item()) == 0:
-                done = True
-                eng._p2p_used = True
-            else:
-                self.p2p = False
-                eng.disable_p2p()
-                eng._p2p_fell_back = True  # (stays with the per-interval transport from here on)
-                if not failed:
-                    eng.p2p_why = "peer windows dropped: the sweep failed on another rank"
-        if not done:
-            def all_reduce(x):
-                self.dist.all_reduce(x, op=self.dist.ReduceOp.SUM, group=self.group)
+            return self._single_launch(args)
+        if self.group is None:
+            # the single-launch sweep needs all its workgroups resident at once; when the GPU could not give it that, the
+            # ladder redoes it on smaller grids and in the end interval by interval (_update_ladder.py, INTEGRATION.md 4)
+            return self._ladder.run(lambda: self._single_launch(args), lambda: self._update_per_interval(args))
+        out = self._update_peer_windows(args) if self.p2p else None
+        return out if out is not None else self._update_all_reduce(args)
 
-            # HIP-graph replay of the interval loop needs a capturable collective (RCCL)
-            chunk = None if self.dist.get_backend(self.group) == 'nccl' else 0
-            opt, psi_T, g_a = eng.forward_update_sharded(
-                self.chi_store, norms_loc, self.init, guess, shapes, lambdas, all_reduce, graph_chunk=chunk)
-        self.fw_T_dev = psi_T
-        eng.check()
-        if chi_li is not None:
-            chi_li.set_device_values(li_J.cpu().numpy())  # (a singular U_B: ValueError)
+    def _single_launch(self, args):
+        out = self.engine.forward_update(*args)
+        self.engine.check()
+        return out
+
+    def _update_per_interval(self, args):
+        """(One GPU) one launch per interval: nothing waits inside a kernel."""
+        return self.engine.forward_update_sharded(*args, lambda x: None, graph_chunk=0)
+
+    def _update_peer_windows(self, args):
+        """One persistent launch per rank; the per-GPU sums cross the node inside the kernel.  None when the sweep failed
+        on any rank: all of them then drop the peer windows together, and the caller goes on with the all-reduce."""
+        t, eng = self.torch, self.engine
+        if not self._p2p_synced:
+            # the ranks' kernels wait for each other INSIDE the sweep (bounded by KH_TIMEOUT_MS): before the first
+            # one, line the ranks up -- set-up time (imports, engine creation, operator norms) differs by more than
+            # that bound between ranks; afterwards they stay within a sweep's jitter of each other
+            t.cuda.synchronize(eng.device)
+            self.dist.barrier(group=self.group)
+            self._p2p_synced = True
+        out, failed = None, 0
+        try:
+            out = self._single_launch(args)
+        except Exception as exc:  # exchange timeout: every rank falls back together
+            logging.getLogger('krotov').warning("cross-GPU exchange failed (%s)", exc)
+            eng.p2p_why = "peer windows dropped after a failed sweep on this rank: %s" % exc
+            failed = 1
+        flag = t.tensor([failed], dtype=t.int32, device=eng.device)
+        self.dist.all_reduce(flag, op=self.dist.ReduceOp.MAX, group=self.group)
+        if int(flag.item()) == 0:
+            eng._p2p_used = True
+            return out
+        self.p2p = False
+        eng.disable_p2p()
+        eng._p2p_fell_back = True  # (stays with the per-interval transport from here on)
+        if not failed:
+            eng.p2p_why = "peer windows dropped: the sweep failed on another rank"
+        return None
+
+    def _update_all_reduce(self, args):
+        """One launch and one all-reduce of the L update sums per interval."""
+        def all_reduce(x):
+            self.dist.all_reduce(x, op=self.dist.ReduceOp.SUM, group=self.group)
+
+        # HIP-graph replay of the interval loop needs a capturable collective (RCCL)
+        chunk = None if self.dist.get_backend(self.group) == 'nccl' else 0
+        return self.engine.forward_update_sharded(*args, all_reduce, graph_chunk=chunk)
+
+    def _results(self, opt, psi_T, g_a, par, u_opt, second_order):
+        """What ``iterate`` returns, fetched from the update sweep's outputs."""
         fw_states_T = self._final_states(psi_T)
         opt_host = opt.cpu().numpy()
-        self.__dict__.setdefault('_uploads', {})['pulses'] = (opt_host.copy(), opt)  # (the next iteration's guess, if unchanged)
+        self._uploads.record('pulses', opt_host, opt)  # (the next iteration's guess, if unchanged)
         if self.replica_form:  # ((1, L, nt - 1) and (1, L): the one replica's rows)
             opt_host, g_a = opt_host[0], g_a[0]
         optimized = [opt_host[l].copy() for l in range(self.L)]
@@ -1006,7 +980,7 @@ class _HipBackend:
             par.commit(u_opt.cpu().numpy(), optimized)
         backward_states = _DeviceTrajectories(self.chi_store, self.likes, self.k0, layout=self.layout)
         forward_states = None
-        if sigma is not None or constraint is not None:
+        if second_order:
             forward_states = _DeviceTrajectories(self.fw_next, self.likes, self.k0, final=fw_states_T._array,
                                                  layout=self.layout, engine=self.engine)
         return backward_states, optimized, fw_states_T, g_a.cpu().numpy(), forward_states

@@ -488,7 +488,7 @@ def test_update_sweep_retry_ladder_on_the_host(monkeypatch, caplog):
 
     # ... and after _FULL_GRID_PROBE_EVERY sweeps in a row on it the full grid gets one more chance (the co-tenant may
     # be gone); the reduced grid of the last time is then asked for directly
-    import krotov_amd.optimize as optimize_mod
+    import krotov_amd._update_ladder as optimize_mod
 
     monkeypatch.setattr(optimize_mod, '_FULL_GRID_PROBE_EVERY', 2)
     script.update(fits=4, calls=[])
@@ -508,6 +508,175 @@ def test_update_sweep_retry_ladder_on_the_host(monkeypatch, caplog):
     assert script['stepwise'] == 5
     assert caplog.text.count('one launch per interval') == 3 and 'staying with that form' in caplog.text
     assert script['calls'] == [0, 4, 0, 1, 0] * 3  # (4 is tried and times out, 1 is refused: reset) -- then never again
+
+
+def _ladder_rig(K, fits, code=None, floor=1, invalid=(), row_split=None):
+    """``krotov_amd._update_ladder.UpdateLadder`` on a scripted engine of K workgroups that refuses grids below ``floor``
+    (KH_ERR_UNSUPPORTED) or in ``invalid`` (KH_ERR_INVALID), and a sweep that answers ``code`` (KH_ERR_TIMEOUT if None)
+    while more than ``script['fits']`` workgroups are in force or the rows are still split.  Returns the engine -- its
+    ``calls`` are the arguments of ``set_update_workgroups``, ``splits`` those of ``set_row_split`` --, the script and
+    ``run()``: 'single' if the single launch got through, 'intervals' if the per-interval form ran."""
+    from krotov_amd import _lib
+    from krotov_amd._update_ladder import UpdateLadder
+
+    class Engine:
+        grid = None  # None: the engine's own (K workgroups)
+
+        def __init__(self):
+            self.calls, self.splits = [], []
+            if row_split is not None:  # (the engine double has no such attribute: the ladder must not need it)
+                self.row_split = row_split
+
+        def set_update_workgroups(self, g=0):
+            self.calls.append(g)
+            if g == 0:
+                self.grid = None
+                return K
+            if g in invalid:
+                raise _lib.KrotovHipError("no such argument", _lib.KH_ERR_INVALID)
+            if g < floor:
+                raise _lib.KrotovHipError("no such grid", _lib.KH_ERR_UNSUPPORTED)
+            self.grid = g
+            return g
+
+        def set_row_split(self, S):
+            self.splits.append(S)
+            self.row_split = S
+
+    eng = Engine()
+    script = {'fits': fits, 'code': _lib.KH_ERR_TIMEOUT if code is None else code, 'sweeps': 0}
+
+    def sweep():
+        script['sweeps'] += 1
+        if getattr(eng, 'row_split', 1) > 1 or (eng.grid or K) > script['fits']:
+            raise _lib.KrotovHipError("did not get through", script['code'])
+        return 'single'
+
+    ladder = UpdateLadder(eng)
+    return eng, script, lambda: ladder.run(sweep, lambda: 'intervals')
+
+
+def test_update_ladder_sweep_that_cannot_be_resident(caplog):
+    """A sweep that answers KH_ERR_UNSUPPORTED (the device cannot hold the grid at all) walks the same rungs as one that
+    timed out; if no grid gets through, the single launch is given up for good AT ONCE -- no strike count, no further
+    engine call, no further attempt --; a grid that gets through is kept like any other."""
+    import logging
+
+    from krotov_amd import _lib
+
+    caplog.set_level(logging.WARNING, logger='krotov')
+    eng, script, run = _ladder_rig(8, fits=0, code=_lib.KH_ERR_UNSUPPORTED)
+    assert run() == 'intervals'
+    assert eng.calls == [0, 4, 0, 1, 0] and script['sweeps'] == 3
+    assert caplog.text.count('one launch per interval (and staying with that form)') == 1
+    assert [run(), run()] == ['intervals'] * 2
+    assert eng.calls == [0, 4, 0, 1, 0] and script['sweeps'] == 3
+
+    eng, script, run = _ladder_rig(8, fits=4, code=_lib.KH_ERR_UNSUPPORTED)
+    assert [run(), run(), run()] == ['single'] * 3
+    assert eng.calls == [0, 4] and eng.grid == 4 and script['sweeps'] == 4
+
+
+def test_update_ladder_passes_real_errors_on():
+    """Codes other than KH_ERR_TIMEOUT / KH_ERR_UNSUPPORTED are not the ladder's: from the sweep they propagate with no
+    engine call and nothing remembered, from ``set_update_workgroups`` after the calls made so far."""
+    from krotov_amd import _lib
+
+    eng, script, run = _ladder_rig(8, fits=0, code=_lib.KH_ERR_HIP)
+    with pytest.raises(_lib.KrotovHipError) as err:
+        run()
+    assert err.value.code == _lib.KH_ERR_HIP and eng.calls == [] and script['sweeps'] == 1
+    script.update(fits=8, code=_lib.KH_ERR_TIMEOUT)
+    assert run() == 'single' and eng.calls == []
+    script.update(fits=4)  # ... and the first timeout after it is a first one: half the full grid
+    assert run() == 'single' and eng.calls == [0, 4]
+
+    eng, script, run = _ladder_rig(8, fits=0, invalid=(4,))
+    with pytest.raises(_lib.KrotovHipError) as err:
+        run()
+    assert err.value.code == _lib.KH_ERR_INVALID and eng.calls == [0, 4] and script['sweeps'] == 1
+
+
+def test_update_ladder_second_rung_below_the_engine_floor():
+    """TODAY'S BEHAVIOUR, AS RECORDED -- and the finding of ADVICE.md (first item): 16 workgroups, the engine refuses
+    fewer than 4, and 4 would fit.  Half (8) times out, the second rung asks for 8 // 4 = 2, which is refused, and the
+    sweep goes to one launch per interval in every run; the grid of 4 that would have got through is never asked for.
+    This is the one case that a change of the policy will edit."""
+    eng, script, run = _ladder_rig(16, fits=4, floor=4)
+    assert [run(), run(), run()] == ['intervals'] * 3
+    assert eng.calls == [0, 8, 0, 2, 0] * 3 and 4 not in eng.calls
+    assert script['sweeps'] == 2 * 3  # (the refused rung costs no sweep)
+
+
+def test_update_ladder_strikes_are_consecutive():
+    """Three sweeps IN A ROW that needed one launch per interval make that form permanent: one that got through in
+    between starts the count again."""
+    eng, script, run = _ladder_rig(8, fits=0)
+    assert [run(), run()] == ['intervals'] * 2
+    script.update(fits=8)
+    assert run() == 'single'
+    script.update(fits=0)
+    assert [run(), run()] == ['intervals'] * 2
+    before = script['sweeps']
+    assert run() == 'intervals' and script['sweeps'] == before + 3  # (still tried: the third strike in a row)
+    calls = list(eng.calls)
+    assert run() == 'intervals' and script['sweeps'] == before + 3 and eng.calls == calls  # ... and now for good
+
+
+def test_update_ladder_leaves_the_row_split_first(caplog):
+    """A timed-out update sweep of an engine with ``row_split`` > 1: one workgroup per objective again -- once, logged at
+    INFO, no grid asked for, no rung used up --; a timeout after that goes on to the rungs."""
+    import logging
+
+    caplog.set_level(logging.INFO, logger='krotov')
+    eng, script, run = _ladder_rig(8, fits=8, row_split=2)
+    assert run() == 'single' and eng.splits == [1] and eng.calls == [] and script['sweeps'] == 2
+    info = [rec for rec in caplog.records if 'row split 2: the update sweep timed out' in rec.getMessage()]
+    assert len(info) == 1 and info[0].levelno == logging.INFO and len(caplog.records) == 1
+
+    eng, script, run = _ladder_rig(8, fits=4, row_split=2)
+    assert run() == 'single' and eng.splits == [1] and eng.calls == [0, 4] and script['sweeps'] == 3
+    assert run() == 'single' and eng.splits == [1] and eng.calls == [0, 4]
+
+
+@pytest.mark.parametrize('second_order', [False, True])
+def test_no_upload_between_the_backward_and_the_update_sweep(monkeypatch, second_order):
+    """Every host-to-device upload of an iteration is issued BEFORE the backward sweep is launched (a copy from pageable
+    memory is ordered behind the kernels in the stream and would keep the update sweep's launch back): between the
+    return of ``engine.backward`` and the entry of ``engine.forward_update`` the backend hands no host array to
+    ``engine.dev``, in three iterations of a first- and of a second-order run on the engine double (what the double
+    uploads to itself inside its own methods happens outside that window)."""
+    import torch
+
+    import krotov_amd.engine as engine_mod
+    from helpers import product_sigma
+    from oracle_engine_double import OracleEngineDouble
+
+    seen = {'window': False, 'uploads': [], 'sweeps': 0}
+
+    class Watched(OracleEngineDouble):
+        def dev(self, x, dtype):
+            if seen['window'] and not isinstance(x, torch.Tensor):
+                seen['uploads'].append(np.shape(x))
+            return super().dev(x, dtype)
+
+        def backward(self, *a, **kw):
+            out = super().backward(*a, **kw)
+            seen['window'] = True
+            return out
+
+        def forward_update(self, *a):
+            seen['window'] = False
+            seen['sweeps'] += 1
+            return super().forward_update(*a)
+
+    monkeypatch.setattr(engine_mod, 'HipKrotovEngine', Watched)
+    spec = configs.config_c5(K=3, N=4, nt=9, L=2, distinct=True)
+    objectives, pulse_options = configs.spec_to_objectives(spec, krotov_amd)
+    krotov_amd.optimize_pulses(objectives, pulse_options, spec.tlist, propagator=krotov_amd.propagators.expm,
+                               chi_constructor=krotov_amd.functionals.chis_re, iter_stop=3,
+                               sigma=product_sigma() if second_order else None)
+    assert seen['sweeps'] == 3 and seen['uploads'] == []
 
 
 def test_bench_leg_traffic_is_keyed_on_the_build_and_scaled_per_interval(tmp_path, monkeypatch):
