@@ -18,12 +18,10 @@ import numpy as np
 
 from . import functionals as _functionals
 from . import optimize as _opt
-from .conversions import pulse_onto_tlist
-from .info_hooks import chain
+from ._run import RunRecord, chained_hook, default_norm, host_costates
 from .mixed import layout_of
 from .mu import derivative_wrt_pulse
 from .propagators import HipExpm, expm
-from .result import Result
 
 __all__ = ['optimize_pulses_batch']
 
@@ -40,10 +38,12 @@ def _free_device_bytes():
     return int(torch.cuda.mem_get_info()[0])
 
 
-class _Replica:
-    """One problem of the batch: what ``optimize_pulses`` keeps in local variables, per replica."""
+class _Replica(RunRecord):
+    """One problem of the batch: its run record, what ``optimize_pulses`` keeps in local variables next to its own, and
+    what only a batch needs (``active``, ``li_values``, ``midpoints``; the backend adds ``likes`` and ``weights``)."""
 
-    def __init__(self, problem, propagator, chi_constructor, iter_stop, store_all_pulses, continue_from, sigma=None):
+    def __init__(self, problem, propagator, chi_constructor, iter_stop, store_all_pulses, continue_from, sigma=None,
+                 info_hook=None, check_convergence=None):
         self.objectives = problem['objectives']
         self.pulse_options = problem['pulse_options']
         self.tlist = problem['tlist']
@@ -53,21 +53,14 @@ class _Replica:
         if continue_from is not None:
             self.guess_controls, self.guess_pulses = _opt._restore_from_previous_result(
                 continue_from, self.objectives, self.tlist, store_all_pulses)
-        self.continue_from = continue_from
         self.L = len(self.guess_pulses)
         self.g_a_integrals = np.zeros(self.L)
-        self.iter_start = 0
-        self.range_stop = iter_stop  # (the driver's loop bound is fixed at the start; a hook changes static_args only)
-        if continue_from is None:
-            self.result = Result()
-            self.result.start_local_time = time.localtime()
-        else:
-            self.result = copy.deepcopy(continue_from)
-        self.static_args = dict(
+        static_args = dict(
             objectives=self.objectives, adjoint_objectives=self.adjoint_objectives, lambda_vals=self.lambda_vals,
             shape_arrays=self.shape_arrays, tlist=self.tlist, propagator=propagator, chi_constructor=chi_constructor,
             mu=derivative_wrt_pulse, sigma=sigma, iter_start=0, iter_stop=iter_stop,
         )
+        super().__init__(static_args, continue_from, store_all_pulses, info_hook, check_convergence)
         self.sigma = sigma
         self.midpoints = None  # (second order: the interval mid-points sigma is evaluated at)
         self.optimized_pulses = copy.deepcopy(self.guess_pulses)
@@ -78,14 +71,11 @@ class _Replica:
         self.iteration = 0
         self.li_values = None  # PerfectEntanglerChi / LocalInvariantsChi: the J per gate of this problem's last co-states
 
-    def finish(self):
-        """What ``optimize_pulses`` does behind its loop; the Result is not touched afterwards."""
+    def stop(self):
+        """The run is over: the Result is finished and this replica holds no device reference any more."""
         self.active = False
-        res = self.result
-        res.end_local_time = time.localtime()
-        res.optimized_controls = [pulse_onto_tlist(np.asarray(p)) for p in self.optimized_pulses]
-        if isinstance(res.states, _opt._LazyStates):
-            res.states = list(res.states)
+        self.forward_states0 = None
+        self.finish(self.optimized_pulses)
 
 
 def _batch_obstacle(problems, reps, propagator):
@@ -268,7 +258,7 @@ class _ReplicaBackend:
         return opt_host, self.psi_T.cpu().numpy(), self.g_a.cpu().numpy()
 
 
-def _run_batch(reps, propagator, chi_constructor, check_convergence, info_hook, store_all_pulses, first=0):
+def _run_batch(reps, propagator, chi_constructor, first=0):
     """One (sub-)batch on one replica engine; ``first``: the index of ``reps[0]`` among the caller's problems."""
     logger = logging.getLogger('krotov')
     li_object = isinstance(chi_constructor, _functionals._LocalInvariantsFunctional)
@@ -292,39 +282,11 @@ def _run_batch(reps, propagator, chi_constructor, check_convergence, info_hook, 
         r.tau_vals = taus_of(tau, b)
         if second_order:  # (in iteration 0 the states under "optimized" and guess pulses coincide)
             r.forward_states0 = backend.trajectories(backend.fw_prev, b, r.likes, psi_host)
-        info = None
-        if info_hook is not None:
-            info = info_hook(
-                backward_states=None, forward_states=r.forward_states0, forward_states0=r.forward_states0,
-                guess_pulses=r.guess_pulses,
-                optimized_pulses=r.optimized_pulses, g_a_integrals=r.g_a_integrals, fw_states_T=r.fw_states_T,
-                tau_vals=r.tau_vals, start_time=tic, stop_time=toc, iteration=0, info_vals=[], shared_data={},
-                **r.static_args,
-            )
-        res = r.result
-        res.tlist = r.tlist
-        res.objectives = r.objectives
-        res.guess_controls = r.guess_controls
-        res.optimized_controls = r.optimized_pulses
-        res.controls_mapping = r.pulses_mapping
-        if r.continue_from is None:
-            if info is not None:
-                res.info_vals.append(info)
-            res.iters.append(0)
-            res.iter_seconds.append(int(toc - tic))
-            if not np.all(r.tau_vals == None):  # noqa: E711
-                res.tau_vals.append(r.tau_vals)
-            if store_all_pulses:
-                res.all_pulses.append(r.guess_pulses)
-        else:
-            r.iter_start = r.continue_from.iters[-1]
-            logger.info("Continuing from previous result, with iteration %d", r.iter_start + 1)
-        res.states = r.fw_states_T
+        r.record_initial(r.guess_controls, r.pulses_mapping, r.guess_pulses, r.optimized_pulses, r.g_a_integrals,
+                         r.fw_states_T, r.tau_vals, r.forward_states0, tic, toc)
         r.iteration = r.iter_start
-        if r.iteration + 1 > r.range_stop:  # (an empty loop: optimize.py's for-else)
-            res.message = "Reached %d iterations" % max(r.iter_start, r.range_stop)
-            r.finish()
-            r.forward_states0 = None
+        if not r.verdict(r.iteration):  # (an empty loop)
+            r.stop()
 
     # the perfect-entangler / local-invariants functional itself (not a function wrapping it): co-states on the device
     chi_li = None
@@ -352,16 +314,13 @@ def _run_batch(reps, propagator, chi_constructor, check_convergence, info_hook, 
             for b, r in enumerate(reps):
                 if not r.active:
                     continue
-                chis = chi_constructor(fw_states_T=r.fw_states_T, objectives=r.objectives, tau_vals=r.tau_vals)
+                chis, norms, vecs = host_costates(chi_constructor, default_norm, layout.vector, fw_states_T=r.fw_states_T,
+                                                  objectives=r.objectives, tau_vals=r.tau_vals)
                 if li_object:  # (the object itself on the host: it has just left this problem's J in .values)
                     r.li_values = np.array(chi_constructor.values, dtype=np.float64)
-                norms = [chi.norm() if hasattr(chi, 'norm') else float(np.linalg.norm(np.asarray(chi))) for chi in chis]
-                vecs = [layout.vector(chi / nrm, k) for k, (chi, nrm) in enumerate(zip(chis, norms))]
-                if any(v is None for v in vecs):
-                    raise ValueError("chi_constructor returned states that do not match the state dimension")
                 chi_T[b * Kr:(b + 1) * Kr] = np.array(vecs)
                 chi_norms[b * Kr:(b + 1) * Kr] = norms
-                host_chis[b] = ([chi / nrm for chi, nrm in zip(chis, norms)], norms)
+                host_chis[b] = (chis, norms)
         opt_host, psi_host, g_a = backend.iterate(chi_T, chi_norms, chi_coef, chi_li=chi_li)
         if chi_li is not None:  # (a singular U_B of an active replica: ValueError)
             chi_constructor.set_device_values(backend.li_J.cpu().numpy(), active=[r.active for r in reps])
@@ -381,62 +340,32 @@ def _run_batch(reps, propagator, chi_constructor, check_convergence, info_hook, 
             r.fw_states_T = states_of(psi_host, b)
             r.g_a_integrals[:] = g_a[b]
             r.tau_vals = taus_of(tau, b)
-            res = r.result
             forward_states = None
             if second_order:
                 forward_states = backend.trajectories(backend.fw_next, b, r.likes, psi_host)
-            info = None
-            if info_hook is not None:
-                info = info_hook(
-                    backward_states=_opt._DeviceTrajectories(backend.chi_store[b * Kr:(b + 1) * Kr], r.likes),
-                    forward_states=forward_states, forward_states0=r.forward_states0, fw_states_T=r.fw_states_T,
-                    guess_pulses=r.guess_pulses,
-                    optimized_pulses=r.optimized_pulses, g_a_integrals=r.g_a_integrals, tau_vals=r.tau_vals,
-                    start_time=tic, stop_time=toc, info_vals=res.info_vals, shared_data={}, iteration=r.iteration,
-                    **r.static_args,
+            backward_states = None
+            if r.info_hook is not None:
+                backward_states = _opt._DeviceTrajectories(backend.chi_store[b * Kr:(b + 1) * Kr], r.likes)
+            r.record_iteration(r.iteration, backward_states, forward_states, r.forward_states0, r.fw_states_T,
+                               r.guess_pulses, r.optimized_pulses, r.g_a_integrals, r.tau_vals, tic, toc)
+            if not r.verdict(r.iteration, r.convergence()):
+                r.stop()
+                continue
+            r.guess_pulses = r.optimized_pulses
+            if second_order:  # (optimize.py:566-577, for the replicas that go on)
+                if b in host_chis:
+                    chi_states, norms = host_chis[b]
+                else:  # co-states formed on the device, in the caller's state type
+                    if chi_fetched is None:
+                        chi_fetched = backend.chi_host()
+                    rows = slice(b * Kr, (b + 1) * Kr)
+                    chi_states, norms = _opt._LazyStates(chi_fetched[0][rows], r.likes), chi_fetched[1][rows]
+                r.sigma.refresh(
+                    forward_states=forward_states, forward_states0=r.forward_states0, chi_states=chi_states,
+                    chi_norms=norms, optimized_pulses=r.optimized_pulses, guess_pulses=r.guess_pulses,
+                    objectives=r.objectives, result=r.result,
                 )
-            res.iters.append(r.iteration)
-            res.iter_seconds.append(int(toc - tic))
-            if info is not None:
-                res.info_vals.append(info)
-            if not np.all(r.tau_vals == None):  # noqa: E711
-                res.tau_vals.append(r.tau_vals)
-            res.optimized_controls = r.optimized_pulses
-            if store_all_pulses:
-                res.all_pulses.append(copy.deepcopy(r.optimized_pulses))
-            res.states = r.fw_states_T
-            msg = None
-            if check_convergence is not None:
-                msg = check_convergence(res)
-            if r.iteration >= r.static_args['iter_stop']:  # a hook may have changed it
-                res.message = "Reached %d iterations" % r.static_args['iter_stop']
-                r.finish()
-            elif bool(msg) is True:
-                res.message = "Reached convergence"
-                if isinstance(msg, str):
-                    res.message += ": " + msg
-                r.finish()
-            elif r.iteration + 1 > r.range_stop:  # (the loop's own end: optimize.py's for-else)
-                res.message = "Reached %d iterations" % max(r.iter_start, r.range_stop)
-                r.finish()
-            else:
-                r.guess_pulses = r.optimized_pulses
-                if second_order:  # (optimize.py:566-577, for the replicas that go on)
-                    if b in host_chis:
-                        chi_states, norms = host_chis[b]
-                    else:  # co-states formed on the device, in the caller's state type
-                        if chi_fetched is None:
-                            chi_fetched = backend.chi_host()
-                        rows = slice(b * Kr, (b + 1) * Kr)
-                        chi_states, norms = _opt._LazyStates(chi_fetched[0][rows], r.likes), chi_fetched[1][rows]
-                    r.sigma.refresh(
-                        forward_states=forward_states, forward_states0=r.forward_states0, chi_states=chi_states,
-                        chi_norms=norms, optimized_pulses=r.optimized_pulses, guess_pulses=r.guess_pulses,
-                        objectives=r.objectives, result=res,
-                    )
-                    r.forward_states0 = forward_states
-            if not r.active:
-                r.forward_states0 = None  # (a finished replica holds no device reference)
+                r.forward_states0 = forward_states
         if second_order:
             backend.advance_second_order()
     backend.engine.close()
@@ -522,13 +451,13 @@ def optimize_pulses_batch(problems, *, propagator, chi_constructor, iter_stop=50
 
     if isinstance(propagator, list) or not (propagator is expm or isinstance(propagator, HipExpm)):
         return sequential("the propagator is not expm / HipExpm")
-    reps = [_Replica(p, propagator, chi_constructor, iter_stop, store_all_pulses, prev, sigma=sig)
+    hook = chained_hook(modify_params_after_iter, info_hook)
+    reps = [_Replica(p, propagator, chi_constructor, iter_stop, store_all_pulses, prev, sigma=sig, info_hook=hook,
+                     check_convergence=check_convergence)
             for p, prev, sig in zip(problems, previous, sigmas)]
     reason = _batch_obstacle(problems, reps, propagator)
     if reason is not None:
         return sequential(reason)
-    if modify_params_after_iter is not None:
-        info_hook = modify_params_after_iter if info_hook is None else chain(modify_params_after_iter, info_hook)
     logger.info("optimize_pulses_batch: %d problems of %d objectives in one batch", B, len(reps[0].objectives))
 
     # the co-state store of the whole batch (second order: and the two forward trajectories) against a quarter of the
@@ -545,6 +474,6 @@ def optimize_pulses_batch(problems, *, propagator, chi_constructor, iter_stop=50
             logger.info("optimize_pulses_batch: %d sub-batches of %d problems (the co-state store of all %d would take "
                         "%d bytes, a quarter of the free device memory is %d)", B // size, size, B, B * per_replica, free // 4)
     for i in range(0, B, size):
-        _run_batch(reps[i:i + size], propagator, chi_constructor, check_convergence, info_hook, store_all_pulses, first=i)
+        _run_batch(reps[i:i + size], propagator, chi_constructor, first=i)
     publish_values([r.li_values for r in reps])
     return [r.result for r in reps]

@@ -34,6 +34,7 @@ from functools import partial
 
 import numpy as np
 
+from . import _run
 from . import functionals as _functionals
 from ._ingest import state_to_vector, to_dense, to_sparse, vector_to_state
 from .constraints import QuadraticStateConstraint, StateDependentConstraint
@@ -51,7 +52,6 @@ from ._lib import KH_ERR_TIMEOUT as _KH_ERR_TIMEOUT
 from ._update_ladder import UpdateLadder as _UpdateLadder, leave_row_split as _leave_row_split
 
 _KH_MAX_CONTROLS = 32  # KH_GEN_MAX_L of krotov_amd/csrc/kh_common.h (the register-resident kernel families: 8)
-from .info_hooks import chain
 from .mixed import Layout, LindbladLayout, layout_of, lindblad_layout_of
 from .mu import derivative_wrt_pulse
 from .parallelization import serial_map
@@ -265,8 +265,6 @@ def _forward_propagation_step(i_state, states, objectives, pulses, pulses_mappin
 class _PluginBackend:
     """Host loop over user callables, call-for-call like the reference."""
 
-    device = False
-
     def __init__(self, objectives, adjoint_objectives, pulses_mapping, tlist, propagators, storage, parallel_map,
                  mu, overlap):
         self.objectives = objectives
@@ -279,7 +277,8 @@ class _PluginBackend:
         self.mu = mu
         self.overlap = overlap
 
-    def initial_forward(self, pulses):
+    def initial_forward(self, pulses, store=False):
+        """(``store``: the trajectories are kept whether or not the caller goes on to use them.)"""
         K = len(self.objectives)
         forward_states = self.pmap[0](
             _forward_propagation, list(range(K)),
@@ -290,8 +289,16 @@ class _PluginBackend:
     def tau_vals(self, fw_states_T):
         return np.array([self.overlap(obj.target, s) for s, obj in zip(fw_states_T, self.objectives)])
 
-    def iterate(self, chi_states, chi_norms, guess_pulses, lambda_vals, shape_arrays, sigma=None,
-                forward_states0=None, par=None, constraint=None):
+    def state_vector(self, state, k):
+        """The user's callables take the states as they are."""
+        return state
+
+    def advance_second_order(self):
+        """``forward_states0`` is the caller's here: nothing to swap."""
+
+    def iterate(self, chi_states, chi_norms, guess_pulses, lambda_vals, shape_arrays, sigma=None, forward_states0=None,
+                chi_coef=None, par=None, constraint=None, chi_li=None):
+        """``_HipBackend.iterate``'s signature; ``chi_coef`` / ``chi_li`` (co-states formed on the device) never come here."""
         objectives, tlist = self.objectives, self.tlist
         K, nt = len(objectives), len(tlist)
         if constraint is not None:
@@ -590,8 +597,6 @@ class _UploadCache:
 class _HipBackend:
     """All objectives of this rank resident on one GPU."""
 
-    device = True
-
     def __init__(self, objectives, pulses_mapping, tlist, n_controls, propagator, process_group=None,
                  second_order=False, parametrized=False, replica_form=False):
         import torch
@@ -816,12 +821,12 @@ class _HipBackend:
         self._li_route = (constructor, args)
         return constructor if args is not None else None
 
-    def iterate(self, chi_T, chi_norms, guess_pulses, lambda_vals, shape_arrays, sigma=None, chi_coef=None, par=None,
-                constraint=None, chi_li=None):
-        """chi_T: (K_total, N) normalised co-states (host); chi_norms (K_total,) -- or
+    def iterate(self, chi_T, chi_norms, guess_pulses, lambda_vals, shape_arrays, sigma=None, forward_states0=None,
+                chi_coef=None, par=None, constraint=None, chi_li=None):
+        """chi_T: the K_total normalised co-states as :meth:`state_vector` rows (host); chi_norms (K_total,) -- or
         ``chi_coef = (c, d)``, (K_total,) each: chi_k(T) = c_k target_k + d_k phi_k(T) is
         then formed and normalised on the device (kh_chi_boundary) -- or ``chi_li``: what
-        :meth:`local_invariants_route` returned (kh_chi_local_invariants)."""
+        :meth:`local_invariants_route` returned (kh_chi_local_invariants).  ``forward_states0``: here ``self.fw_prev``."""
         second_order = sigma is not None or constraint is not None
         guess = self._pulses(guess_pulses, cached=True)
         # every upload of the iteration BEFORE the first sweep is launched: a host-to-device copy from pageable memory
@@ -890,7 +895,7 @@ class _HipBackend:
             return eng.chi_local_invariants(
                 self.fw_T_dev, self._uploads.get('li_bell', bell, t.complex128), mode,
                 self._uploads.get('li_invariants', invariants), weight, 4.0 / self.K_total)
-        chi_loc = eng.dev(chi_T[self.k0:self.k1], t.complex128)
+        chi_loc = eng.dev(np.array(chi_T[self.k0:self.k1]), t.complex128)
         norms_loc = eng.dev(np.asarray(chi_norms, dtype=np.float64)[self.k0:self.k1], t.float64)
         return chi_loc, norms_loc, None
 
@@ -996,6 +1001,64 @@ class _HipBackend:
 # ---------------------------------------------------------------------------
 
 
+def _check_arguments(objectives, pulse_options, propagator, mu, overlap, sigma, storage, process_group, constraint,
+                     skip_initial_forward_propagation):
+    """What ``optimize_pulses`` refuses, decided on the host before any GPU work and any collective (the same verdict on
+    every rank); returns ``(device_path, params)``: whether the arguments select the device path, and
+    :func:`_parametrizations`."""
+    second_order = sigma is not None
+    if second_order and skip_initial_forward_propagation:
+        raise ValueError(
+            "skip_initial_forward_propagation is incompatible with second order Krotov (sigma is not None)"
+        )
+    if constraint is not None:
+        if not isinstance(constraint, StateDependentConstraint):
+            raise ValueError("state_dependent_constraint must be a krotov_amd.constraints.StateDependentConstraint, "
+                             "not %r" % (constraint,))
+        if process_group is not None:
+            raise ValueError("state-dependent constraints run on one GPU: process_group= (sharding) is not supported "
+                             "with state_dependent_constraint")
+        if any(len(obj.c_ops) > 0 for obj in objectives):
+            raise NotImplementedError("state_dependent_constraint is not implemented for objectives with c_ops "
+                                      "(Lindblad form)")
+        if skip_initial_forward_propagation:
+            raise ValueError("skip_initial_forward_propagation is incompatible with state_dependent_constraint (the "
+                             "source term needs the states under the guess pulses)")
+        if layout_of(objectives, propagator).mixed:
+            raise ValueError("state_dependent_constraint needs objectives of one dimension and kind")
+    device_path = _use_device_path(propagator, mu, overlap, sigma, storage, objectives)
+    params = _parametrizations(objectives, pulse_options)
+    if params is not None and process_group is not None:
+        raise ValueError("pulse parametrizations run on one GPU: process_group= (sharding) is not supported with "
+                         "'parametrization' in pulse_options")
+    if process_group is not None and not device_path:
+        raise ValueError("process_group requires the device path (propagator=krotov_amd.propagators.expm)")
+    if device_path and any(len(obj.c_ops) > 0 for obj in objectives):
+        # (a control inside c_ops raises here)
+        if (lindblad_layout_of(objectives, propagator, None, second_order, params is not None).matrix
+                and process_group is not None):
+            raise ValueError("objectives in Lindblad form run on one GPU: process_group= (sharding) is not supported "
+                             "for the matrix-form engine")
+    elif process_group is not None and layout_of(objectives, propagator).mixed:
+        raise ValueError("objectives of different dimension or kind run on one GPU: process_group= (sharding) is "
+                         "not supported for them")
+    return device_path, params
+
+
+def _device_costates(backend, chi_constructor, tau_vals):
+    """``(chi_coef, chi_li)`` for ``_HipBackend.iterate`` where the device forms the boundary co-states itself (both
+    None: ``chi_constructor`` is called on the host)."""
+    if isinstance(chi_constructor, _functionals._LocalInvariantsFunctional):
+        # the perfect-entangler / local-invariants functional itself (not a function wrapping it): the 4 x 4
+        # algebra per gate and the co-states on the device
+        return None, backend.local_invariants_route(chi_constructor)
+    if backend.targets is not None and (backend.fw_T_dev is not None or chi_constructor is _functionals.chis_re):
+        # built-in functionals: chi_k(T) is formed and normalised on the device from K scalars
+        # (no K-long Python loop, phi_k(T) and chi_k(T) stay in HBM)
+        return _functionals.chi_coefficients(chi_constructor, backend.weights, tau_vals, backend.K_total), None
+    return None, None
+
+
 def optimize_pulses(
     objectives,
     pulse_options,
@@ -1055,57 +1118,18 @@ def optimize_pulses(
     logger = logging.getLogger('krotov')
     logger.info("Initializing optimization with Krotov's method")
     second_order = sigma is not None
-    if second_order and skip_initial_forward_propagation:
-        raise ValueError(
-            "skip_initial_forward_propagation is incompatible with second order Krotov (sigma is not None)"
-        )
     constraint = state_dependent_constraint
-    if constraint is not None:
-        # (host-only, before any GPU work and any collective)
-        if not isinstance(constraint, StateDependentConstraint):
-            raise ValueError("state_dependent_constraint must be a krotov_amd.constraints.StateDependentConstraint, "
-                             "not %r" % (constraint,))
-        if process_group is not None:
-            raise ValueError("state-dependent constraints run on one GPU: process_group= (sharding) is not supported "
-                             "with state_dependent_constraint")
-        if any(len(obj.c_ops) > 0 for obj in objectives):
-            raise NotImplementedError("state_dependent_constraint is not implemented for objectives with c_ops "
-                                      "(Lindblad form)")
-        if skip_initial_forward_propagation:
-            raise ValueError("skip_initial_forward_propagation is incompatible with state_dependent_constraint (the "
-                             "source term needs the states under the guess pulses)")
-        if layout_of(objectives, propagator).mixed:
-            raise ValueError("state_dependent_constraint needs objectives of one dimension and kind")
     keeps_states = second_order or constraint is not None  # phi(t_n) of the last two iterations are kept
-    device_path = _use_device_path(propagator, mu, overlap, sigma, storage, objectives)
-    params = _parametrizations(objectives, pulse_options)
-    if params is not None and process_group is not None:
-        # (host-only, the same verdict on every rank, before any collective)
-        raise ValueError("pulse parametrizations run on one GPU: process_group= (sharding) is not supported with "
-                         "'parametrization' in pulse_options")
-    if process_group is not None and not device_path:
-        raise ValueError("process_group requires the device path (propagator=krotov_amd.propagators.expm)")
-    if device_path and any(len(obj.c_ops) > 0 for obj in objectives):
-        # (host-only, before any GPU work and any collective: a control inside c_ops raises here; the same verdict on
-        # every rank)
-        if (lindblad_layout_of(objectives, propagator, None, second_order, params is not None).matrix
-                and process_group is not None):
-            raise ValueError("objectives in Lindblad form run on one GPU: process_group= (sharding) is not supported "
-                             "for the matrix-form engine")
-    elif process_group is not None and layout_of(objectives, propagator).mixed:
-        # (host-only, the same verdict on every rank, before any collective)
-        raise ValueError("objectives of different dimension or kind run on one GPU: process_group= (sharding) is "
-                         "not supported for them")
+    device_path, params = _check_arguments(objectives, pulse_options, propagator, mu, overlap, sigma, storage,
+                                           process_group, constraint, skip_initial_forward_propagation)
     if mu is None:
         mu = derivative_wrt_pulse
     default_norm = norm is None
     if norm is None:
-        def norm(state):
-            return state.norm() if hasattr(state, 'norm') else float(np.linalg.norm(np.asarray(state)))
+        norm = _run.default_norm
     if overlap is None:
         overlap = _overlap
-    if modify_params_after_iter is not None:
-        info_hook = modify_params_after_iter if info_hook is None else chain(modify_params_after_iter, info_hook)
+    info_hook = _run.chained_hook(modify_params_after_iter, info_hook)
     if isinstance(propagator, list):
         propagators = propagator
         assert len(propagators) == len(objectives)
@@ -1134,10 +1158,18 @@ def optimize_pulses(
         # u of the first guess (a value outside the range raises, naming control and interval); a continued run
         # re-derives it from the stored pulses, where rounding may have put a value on a bound
         par = PulseParameters(params, guess_pulses, pull=continue_from is not None)
-        if device_path and par.device_kinds is None:
-            logger.info("pulse parametrization: a user-defined Parametrization (kind None) is evaluated on the host; "
-                        "running the host loop around single-step propagations on the GPU")
-            device_path = False
+    static_args = dict(
+        objectives=objectives, adjoint_objectives=adjoint_objectives, lambda_vals=lambda_vals,
+        shape_arrays=shape_arrays, tlist=tlist, propagator=propagator, chi_constructor=chi_constructor,
+        mu=mu, sigma=sigma, iter_start=iter_start, iter_stop=iter_stop,
+    )
+    run = _run.RunRecord(static_args, continue_from, store_all_pulses, info_hook, check_convergence)
+
+    # ---- the backend: all objectives in the device's sweeps, or the host loop around the user's callables
+    if device_path and par is not None and par.device_kinds is None:
+        logger.info("pulse parametrization: a user-defined Parametrization (kind None) is evaluated on the host; "
+                    "running the host loop around single-step propagations on the GPU")
+        device_path = False
     if device_path and len(guess_pulses) > _KH_MAX_CONTROLS and process_group is None:
         # the sweep kernels are compiled for at most 32 controls (KH_GEN_MAX_L: the generic kernels; the register-resident
         # families take 8); the reference takes any number (optimize.py:33-55, conversions.py:140-254).  More than that
@@ -1146,13 +1178,6 @@ def optimize_pulses(
         logger.warning("%d controls: the device sweeps take at most %d; running the host loop around single-step "
                        "propagations on the GPU", len(guess_pulses), _KH_MAX_CONTROLS)
         device_path = False
-
-    if continue_from is None:
-        result = Result()
-        result.start_local_time = time.localtime()
-    else:
-        result = copy.deepcopy(continue_from)
-
     if device_path:
         backend = _HipBackend(objectives, pulses_mapping, tlist, len(guess_pulses), propagator, process_group,
                               second_order=second_order, parametrized=par is not None,
@@ -1174,82 +1199,34 @@ def optimize_pulses(
                 "You should not use `skip_initial_forward_propagation` unless you are also passing `continue_from`"
             )
             fw_states_T = [None for _ in objectives]
-        if device_path:
-            backend.fw_T_dev = None
+        forward_states = None
         tau_vals = np.array([overlap(obj.target, s) for s, obj in zip(fw_states_T, objectives)])
     else:
-        if device_path:
-            fw_states_T, forward_states = backend.initial_forward(guess_pulses, store=keeps_states)
-        else:
-            fw_states_T, forward_states = backend.initial_forward(guess_pulses)
+        fw_states_T, forward_states = backend.initial_forward(guess_pulses, store=keeps_states)
         tau_vals = backend.tau_vals(fw_states_T)
     toc = time.time()
     # the stored trajectories are only needed by the second-order update (optimize.py:324-329);
     # in iteration 0 the states under "optimized" and guess pulses coincide
     forward_states0 = forward_states = forward_states if keeps_states else None
-
-    info = None
     optimized_pulses = copy.deepcopy(guess_pulses)
-    static_args = dict(
-        objectives=objectives, adjoint_objectives=adjoint_objectives, lambda_vals=lambda_vals,
-        shape_arrays=shape_arrays, tlist=tlist, propagator=propagator, chi_constructor=chi_constructor,
-        mu=mu, sigma=sigma, iter_start=iter_start, iter_stop=iter_stop,
-    )
-    if info_hook is not None:
-        info = info_hook(
-            backward_states=None, forward_states=forward_states, forward_states0=forward_states0,
-            guess_pulses=guess_pulses,
-            optimized_pulses=optimized_pulses, g_a_integrals=g_a_integrals, fw_states_T=fw_states_T,
-            tau_vals=tau_vals, start_time=tic, stop_time=toc, iteration=0, info_vals=[], shared_data={},
-            **static_args,
-        )
-
-    result.tlist = tlist
-    result.objectives = objectives
-    result.guess_controls = guess_controls
-    result.optimized_controls = optimized_pulses
-    result.controls_mapping = pulses_mapping
-    if continue_from is None:
-        if info is not None:
-            result.info_vals.append(info)
-        result.iters.append(0)
-        result.iter_seconds.append(int(toc - tic))
-        if not np.all(tau_vals == None):  # noqa: E711
-            result.tau_vals.append(tau_vals)
-        if store_all_pulses:
-            result.all_pulses.append(guess_pulses)
-    else:
-        iter_start = continue_from.iters[-1]
-        logger.info("Continuing from previous result, with iteration %d", iter_start + 1)
-    result.states = fw_states_T
+    run.record_initial(guess_controls, pulses_mapping, guess_pulses, optimized_pulses, g_a_integrals, fw_states_T,
+                       tau_vals, forward_states, tic, toc)
 
     # ---- main loop (optimize.py:392-581)
-    for krotov_iteration in range(iter_start + 1, iter_stop + 1):
-        logger.info("Started Krotov iteration %d", krotov_iteration)
+    iteration = run.iter_start
+    go_on = run.verdict(iteration)
+    while go_on:
+        iteration += 1
+        logger.info("Started Krotov iteration %d", iteration)
         tic = time.time()
 
-        chi_T = chi_coef = chi_li = None
-        if device_path and default_norm and isinstance(chi_constructor, _functionals._LocalInvariantsFunctional):
-            # the perfect-entangler / local-invariants functional itself (not a function wrapping it): the 4 x 4
-            # algebra per gate and the co-states on the device
-            chi_li = backend.local_invariants_route(chi_constructor)
-        elif device_path and default_norm and backend.targets is not None:
-            # built-in functionals: chi_k(T) is formed and normalised on the device from K scalars
-            # (no K-long Python loop, phi_k(T) and chi_k(T) stay in HBM)
-            if backend.fw_T_dev is not None or chi_constructor is _functionals.chis_re:
-                chi_coef = _functionals.chi_coefficients(
-                    chi_constructor, backend.weights, tau_vals, len(objectives))
-        if chi_coef is not None or chi_li is not None:
-            chi_states = chi_norms = None
-        else:
-            chi_states = chi_constructor(fw_states_T=fw_states_T, objectives=objectives, tau_vals=tau_vals)
-            chi_norms = [norm(chi) for chi in chi_states]
-            chi_states = [chi / nrm for chi, nrm in zip(chi_states, chi_norms)]
-            if device_path:
-                vecs = [backend.state_vector(c, k) for k, c in enumerate(chi_states)]
-                if any(v is None for v in vecs):
-                    raise ValueError("chi_constructor returned states that do not match the state dimension")
-                chi_T = np.array(vecs)
+        chi_coef = chi_li = None
+        if device_path and default_norm:  # (the built-in functionals: co-states formed on the device)
+            chi_coef, chi_li = _device_costates(backend, chi_constructor, tau_vals)
+        chi_states = chi_norms = chi_T = None
+        if chi_coef is None and chi_li is None:
+            chi_states, chi_norms, chi_T = _run.host_costates(
+                chi_constructor, norm, backend.state_vector, fw_states_T=fw_states_T, objectives=objectives, tau_vals=tau_vals)
 
         g_a_integrals[:] = 0.0
         if par is not None:
@@ -1258,50 +1235,19 @@ def optimize_pulses(
             redone = par.sync(guess_pulses)
             if redone:
                 logger.info("pulse parametrization: controls %s were changed after the last sweep; u re-derived", redone)
-        if device_path:
-            backward_states, optimized_pulses, fw_states_T, g_a, forward_states = backend.iterate(
-                chi_T, chi_norms, guess_pulses, lambda_vals, shape_arrays, sigma=sigma, chi_coef=chi_coef, par=par,
-                constraint=constraint, chi_li=chi_li,
-            )
-        else:
-            backward_states, optimized_pulses, fw_states_T, g_a, forward_states = backend.iterate(
-                chi_states, chi_norms, guess_pulses, lambda_vals, shape_arrays, sigma=sigma,
-                forward_states0=forward_states0, par=par, constraint=constraint,
-            )
+        backward_states, optimized_pulses, fw_states_T, g_a, forward_states = backend.iterate(
+            chi_T, chi_norms, guess_pulses, lambda_vals, shape_arrays, sigma=sigma, forward_states0=forward_states0,
+            chi_coef=chi_coef, par=par, constraint=constraint, chi_li=chi_li,
+        )
         g_a_integrals[:] = g_a
         tau_vals = backend.tau_vals(fw_states_T)
         toc = time.time()
 
-        if info_hook is not None:
-            info = info_hook(
-                backward_states=backward_states, forward_states=forward_states, forward_states0=forward_states0,
-                fw_states_T=fw_states_T, guess_pulses=guess_pulses, optimized_pulses=optimized_pulses,
-                g_a_integrals=g_a_integrals, tau_vals=tau_vals, start_time=tic, stop_time=toc,
-                info_vals=result.info_vals, shared_data={}, iteration=krotov_iteration, **static_args,
-            )
-        result.iters.append(krotov_iteration)
-        result.iter_seconds.append(int(toc - tic))
-        if info is not None:
-            result.info_vals.append(info)
-        if not np.all(tau_vals == None):  # noqa: E711
-            result.tau_vals.append(tau_vals)
-        result.optimized_controls = optimized_pulses
-        if store_all_pulses:
-            result.all_pulses.append(copy.deepcopy(optimized_pulses))
-        result.states = fw_states_T
-        logger.info("Finished Krotov iteration %d", krotov_iteration)
-
-        msg = None
-        if check_convergence is not None:
-            msg = check_convergence(result)
-        if krotov_iteration >= static_args['iter_stop']:  # a hook may have changed it
-            iter_stop = static_args['iter_stop']
-            result.message = "Reached %d iterations" % iter_stop
-            break
-        if bool(msg) is True:
-            result.message = "Reached convergence"
-            if isinstance(msg, str):
-                result.message += ": " + msg
+        run.record_iteration(iteration, backward_states, forward_states, forward_states0, fw_states_T, guess_pulses,
+                             optimized_pulses, g_a_integrals, tau_vals, tic, toc)
+        logger.info("Finished Krotov iteration %d", iteration)
+        go_on = run.verdict(iteration, run.convergence())
+        if not go_on:
             break
         guess_pulses = optimized_pulses
         if second_order:
@@ -1311,18 +1257,12 @@ def optimize_pulses(
             sigma.refresh(
                 forward_states=forward_states, forward_states0=forward_states0, chi_states=chi_states,
                 chi_norms=chi_norms, optimized_pulses=optimized_pulses, guess_pulses=guess_pulses,
-                objectives=objectives, result=result,
+                objectives=objectives, result=run.result,
             )
         if keeps_states:
             forward_states0 = forward_states
-            if device_path:
-                backend.advance_second_order()
-    else:
-        result.message = "Reached %d iterations" % max(iter_start, iter_stop)
+            backend.advance_second_order()
 
     # ---- finalize (optimize.py:583-590)
-    result.end_local_time = time.localtime()
-    result.optimized_controls = [pulse_onto_tlist(np.asarray(p)) for p in optimized_pulses]
-    if isinstance(result.states, _LazyStates):
-        result.states = list(result.states)
-    return result
+    run.finish(optimized_pulses)
+    return run.result

@@ -707,3 +707,152 @@ def test_bench_leg_traffic_is_keyed_on_the_build_and_scaled_per_interval(tmp_pat
     t, src = bench.pmc_traffic_leg('K1024', 'kh_ens_forward_update', 4000)
     assert t is None and 'another build' in src
     assert bench.pmc_traffic_leg('config4', 'kh_coop_forward_update', 1000) == (None, 'no profiles/pmc_config4_latest.json')
+
+
+# ---- the run record both drivers keep (krotov_amd/_run.py), under scripted hooks and with no engine ------------------
+
+
+def _record(iter_stop, **kw):
+    from krotov_amd._run import RunRecord
+
+    return RunRecord(dict(
+        objectives=['objective'], adjoint_objectives=['adjoint'], lambda_vals=np.ones(1), shape_arrays=[np.ones(3)],
+        tlist=np.linspace(0.0, 1.0, 4), propagator=None, chi_constructor=None, mu=None, sigma=None, iter_start=0,
+        iter_stop=iter_stop), **kw)
+
+
+def _drive(run, tau=lambda iteration: np.array([0.5 + 0.1j * iteration])):
+    """The drivers' loop around ``run``: every iteration adds 1 to the one pulse; returns the Result."""
+    guess = [np.zeros(3)]
+    optimized = copy.deepcopy(guess)
+    run.record_initial(['control'], 'mapping', guess, optimized, np.zeros(1), ['phi0'], tau(0), None, 0.0, 0.0)
+    iteration = run.iter_start
+    go_on = run.verdict(iteration)
+    while go_on:
+        iteration += 1
+        assert iteration < 50, "the record never ends the run"
+        optimized = [p + 1.0 for p in guess]
+        run.record_iteration(iteration, None, None, None, ['phi%d' % iteration], guess, optimized, np.zeros(1),
+                             tau(iteration), 0.0, 0.0)
+        go_on = run.verdict(iteration, run.convergence())
+        guess = optimized
+    run.finish(optimized)
+    return run.result
+
+
+def test_run_record_lowered_iter_stop_ends_the_run_there():
+    def lower(**kwargs):
+        if kwargs['iteration'] == 1:
+            run.static_args['iter_stop'] = 3
+
+    run = _record(7, info_hook=lower)
+    res = _drive(run)
+    assert res.iters == [0, 1, 2, 3] and res.message == "Reached 3 iterations"
+    assert run.range_stop == 7
+
+    def lift(**kwargs):  # (the loop's own bound is the one fixed at the start, whatever a hook raises static_args to)
+        run.static_args['iter_stop'] = 9
+
+    run = _record(2, info_hook=lift)
+    res = _drive(run)
+    assert res.iters == [0, 1, 2] and res.message == "Reached 2 iterations"
+
+
+@pytest.mark.parametrize('answer, message', [("tau is fine", "Reached convergence: tau is fine"),
+                                             (True, "Reached convergence")])
+def test_run_record_convergence_message(answer, message):
+    res = _drive(_record(7, check_convergence=lambda result: answer if result.iters[-1] == 2 else None))
+    assert res.iters == [0, 1, 2] and res.message == message
+    assert len(res.optimized_controls[0]) == 4 and np.all(res.optimized_controls[0] == 2.0)  # (finish: on the time grid)
+
+
+def test_run_record_iteration_count_goes_before_convergence():
+    calls = []
+
+    def hook(**kwargs):
+        calls.append(('hook', kwargs['iteration']))
+
+    def converged(result):
+        calls.append(('check', result.iters[-1]))
+        return "converged as well" if result.iters[-1] == 2 else None
+
+    res = _drive(_record(2, info_hook=hook, check_convergence=converged))
+    assert res.message == "Reached 2 iterations" and res.iters == [0, 1, 2]
+    assert calls == [('hook', 0), ('hook', 1), ('check', 1), ('hook', 2), ('check', 2)]
+
+
+def test_run_record_empty_loop_of_a_continued_run():
+    first = _drive(_record(3, store_all_pulses=True))
+    assert first.iters == [0, 1, 2, 3] and len(first.all_pulses) == 4
+    seen = []
+
+    def hook(**kwargs):
+        seen.append((kwargs['iteration'], list(kwargs['info_vals'])))
+        return 'never recorded'
+
+    for iter_stop, said in [(3, 3), (2, 3)]:  # (the message: max(iter_start, iter_stop), iter_start the last one run)
+        del seen[:]
+        run = _record(iter_stop, continue_from=first, store_all_pulses=True, info_hook=hook)
+        res = _drive(run)
+        assert run.iter_start == 3 and res.message == "Reached %d iterations" % said
+        assert res.iters == [0, 1, 2, 3] and len(res.all_pulses) == 4 and len(res.iter_seconds) == 4
+        assert res.info_vals == [] and seen == [(0, [])]
+    assert first.message == "Reached 3 iterations" and res is not first  # (the record works on a copy)
+    # ... and one that does go on appends from the iteration after
+    res = _drive(_record(5, continue_from=first, store_all_pulses=True))
+    assert res.iters == [0, 1, 2, 3, 4, 5] and res.message == "Reached 5 iterations"
+
+
+def test_run_record_tau_vals_and_info_vals_skip_none():
+    res = _drive(_record(2, info_hook=lambda **kwargs: None if kwargs['iteration'] == 1 else kwargs['iteration']),
+                 tau=lambda iteration: np.array([None, None]))
+    assert res.tau_vals == [] and res.info_vals == [0, 2] and res.iters == [0, 1, 2]
+    res = _drive(_record(2), tau=lambda iteration: np.array([None, 0.25 * iteration], dtype=object))
+    assert [t[1] for t in res.tau_vals] == [0.0, 0.25, 0.5]  # (only ALL-None values are left out)
+
+
+def test_run_record_store_all_pulses():
+    run = _record(2, store_all_pulses=True)
+    guess, first, second = [np.zeros(3)], [np.ones(3)], [np.full(3, 2.0)]
+    run.record_initial(['control'], 'mapping', guess, copy.deepcopy(guess), np.zeros(1), ['phi'], np.array([0.5]), None,
+                       0.0, 0.0)
+    run.record_iteration(1, None, None, None, ['phi'], guess, first, np.zeros(1), np.array([0.5]), 0.0, 0.0)
+    run.record_iteration(2, None, None, None, ['phi'], first, second, np.zeros(1), np.array([0.5]), 0.0, 0.0)
+    stored = run.result.all_pulses
+    assert len(stored) == 3 and stored[0] is guess  # (iteration 0: the guess itself)
+    assert stored[1] is not first and stored[1][0] is not first[0] and np.array_equal(stored[1][0], first[0])
+    first[0][:] = 7.0
+    assert np.all(stored[1][0] == 1.0) and np.all(stored[2][0] == 2.0)
+    assert run.result.optimized_controls is second
+    assert _drive(_record(2)).all_pulses == []
+
+
+def test_host_costates_norm_and_dimension():
+    from krotov_amd._run import default_norm, host_costates
+
+    asked = []
+
+    def constructor(**kwargs):
+        asked.append(list(kwargs))
+        return [np.array([3.0, 4.0j]), np.array([0.0, 2.0])]
+
+    def to_vector(chi, k):
+        return chi if len(chi) == 2 else None
+
+    chis, norms, vecs = host_costates(constructor, default_norm, to_vector, fw_states_T='phi', objectives='objs',
+                                      tau_vals='tau')
+    assert asked == [['fw_states_T', 'objectives', 'tau_vals']] and norms == [5.0, 2.0]
+    assert np.array_equal(chis[0], np.array([3.0, 4.0j]) / 5.0) and np.array_equal(vecs[1], [0.0, 1.0])
+    assert abs(np.linalg.norm(chis[0]) - 1.0) < 1e-15  # (a handful of roundings at 1.1e-16 each)
+    chis, norms, _ = host_costates(constructor, lambda chi: 2.0, to_vector, fw_states_T='phi', objectives='objs',
+                                   tau_vals='tau')
+    assert norms == [2.0, 2.0] and np.array_equal(chis[0], [1.5, 2.0j])
+    with pytest.raises(ValueError, match="chi_constructor returned states that do not match the state dimension"):
+        host_costates(constructor, default_norm, lambda chi, k: None if k == 1 else chi, fw_states_T='phi',
+                      objectives='objs', tau_vals='tau')
+
+    class WithNorm:  # (a state type that brings its own norm)
+        def norm(self):
+            return 4.0
+
+    assert default_norm(WithNorm()) == 4.0
