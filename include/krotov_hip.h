@@ -391,6 +391,32 @@ enum kh_par_kind {
 int kh_set_parametrization(kh_engine *engine, const int32_t *kind, const double *a, const double *b,
                            const double *u_guess_dev, const double *dfdu_dev, double *u_opt_dev);
 
+/* Non-linear controls: H(eps) = H_0 + sum_j eps_c(j)^p_j H_j.  The engine's L operator slots are J = L TERMS; term j
+ * belongs to control c(j), 0 <= c(j) < C <= J, and has an integer power p_j in 1..4.  At interval n, with D_j the
+ * update sum of slot j as today (second order: with its sigma term),
+ *   w_j     = p_j eps_guess,c(j)[n]^(p_j - 1)          the derivative at the GUESS, formed by the caller: dcde_dev
+ *   D_c     = sum_{j in c} w_j[n] D_j
+ *   eps_c[n]= eps_guess,c[n] + (S_c[n] / lambda_c) D_c
+ *   g_a,c  += (S_c[n] / lambda_c) D_c^2 dt_n
+ *   c_j     = eps_c[n]^p_j                             by repeated multiplication; what interval n is propagated with
+ *                                                      (theta of the series: sum_j |c_j| ||H_j||, as today)
+ * The weights are applied after the exchange: the exchanged and the stepwise sums stay per term.
+ * While set, the update sweeps (kh_forward_update, kh_update_begin / _step / _step_dev / _end) take guess, shape, lambda,
+ * opt and g_a as arrays of C rows (of eps); partial_dev and D_dev stay J sums.  The plain, backward and source-term
+ * sweeps and kh_expect are not touched: they take J rows of term coefficients c_j[n] = eps_c(j)[n]^p_j as before.
+ *   C             number of controls
+ *   term_control  [J] host array (copied); NULL: non-linear controls off, the other arguments are ignored
+ *   term_power    [J] host array (copied)
+ *   dcde_dev      [J][nt-1] w_j under the guess pulses; must stay valid while set
+ * Routes: as kh_set_parametrization's -- the whole sweep of a register-tile engine (N <= 64, 1..4 terms, its K > 1
+ * workgroups resident) runs kh_tile_forward_update_nl; everything else runs kh_gen_forward_update_nl on min(K, compute
+ * units) workgroups (up to 32 terms; a grid reduced with kh_set_update_workgroups is dropped again with the setting).
+ * KH_ERR_UNSUPPORTED for replica and Lindblad-form engines, sharded engines, a row split above 1 and N beyond the
+ * generic kernels' LDS; KH_ERR_INVALID for a power outside 1..4, a control index outside 0..C-1, a control without a
+ * term, and while a parametrization is set (kh_set_parametrization answers the same while this is set). */
+int kh_set_nonlinear(kh_engine *engine, int32_t C, const int32_t *term_control, const int32_t *term_power,
+                     const double *dcde_dev);
+
 /* The same sweep cut at the cross-objective sum, for objectives sharded over
  * several GPUs: the caller all-reduces `partial` (L doubles, Im parts) across
  * ranks between two calls (RCCL over xGMI).

@@ -13,6 +13,7 @@ from . import (
     functionals,
     info_hooks,
     mu,
+    nonlinear,
     objectives,
     parallelization,
     parametrization,
@@ -24,6 +25,7 @@ from . import (
 from .objectives import Objective, ensemble_objectives, gate_objectives, propagate_objectives
 from .batch import optimize_pulses_batch
 from .constraints import QuadraticStateConstraint, StateDependentConstraint
+from .nonlinear import ControlFunction, Power
 from .optimize import optimize_pulses
 from .parametrization import (
     LinearParametrization,
@@ -37,9 +39,11 @@ from .result import Result
 __version__ = '0.1.0'
 
 __all__ = [
+    'ControlFunction',
     'LinearParametrization',
     'Objective',
     'Parametrization',
+    'Power',
     'QuadraticStateConstraint',
     'Result',
     'SquareParametrization',
@@ -54,6 +58,7 @@ __all__ = [
     'gate_objectives',
     'info_hooks',
     'mu',
+    'nonlinear',
     'objectives',
     'optimize_pulses',
     'optimize_pulses_batch',

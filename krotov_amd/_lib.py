@@ -102,6 +102,7 @@ SYMBOLS = {
     'kh_set_second_order': (ctypes.c_int, [_P, _P, _P, _P]),
     'kh_set_second_order_replicas': (ctypes.c_int, [_P, _P, _P, _P]),
     'kh_set_parametrization': (ctypes.c_int, [_P] * 7),
+    'kh_set_nonlinear': (ctypes.c_int, [_P, ctypes.c_int32, _P, _P, _P]),
     'kh_update_begin': (ctypes.c_int, [_P] * 9),
     'kh_update_step': (ctypes.c_int, [_P, ctypes.c_int32] + [_P] * 9),
     'kh_update_step_dev': (ctypes.c_int, [_P] * 11),

@@ -84,6 +84,8 @@ def _batch_obstacle(problems, reps, propagator):
         return "the propagator is not expm / HipExpm"
     if any(_opt._parametrizations(r.objectives, r.pulse_options) is not None for r in reps):
         return "a pulse parametrization ('parametrization' in pulse_options)"
+    if any(_opt.has_control_function(r.objectives) for r in reps):
+        return "non-linear controls (a ControlFunction in H)"
     for r in reps:  # (what a single problem must be: shared with optimize_pulses' own use of a one-replica engine)
         reason = _opt._replica_kind_obstacle(r.objectives, propagator)
         if reason is not None:

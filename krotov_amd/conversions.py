@@ -3,11 +3,15 @@
 Same public names and semantics as the reference's ``krotov.conversions``
 (reference src/krotov/conversions.py) because these numbers define what every
 sweep consumes: "controls" live on the points of ``tlist``, "pulses" on its
-``nt-1`` intervals.  Controls are identified by object identity.
+``nt-1`` intervals.  Controls are identified by object identity.  A control wrapped in a
+:class:`~krotov_amd.nonlinear.ControlFunction` (``[H2, Power(eps, 2)]``) is the control it wraps: one pulse, one entry of
+``pulse_options``; its pulse value is plugged in through the function.
 """
 import logging
 
 import numpy as np
+
+from .nonlinear import ControlFunction, unwrap
 
 __all__ = [
     'control_onto_interval',
@@ -111,13 +115,14 @@ def extract_controls(objectives):
         for term in objective.H:
             if isinstance(term, list):
                 assert len(term) == 2
-                if _index_of(term[1], controls) < 0:
-                    controls.append(term[1])
+                control = unwrap(term[1])
+                if _index_of(control, controls) < 0:
+                    controls.append(control)
     return controls
 
 
 def _positions(nested, control):
-    return [i for i, term in enumerate(nested) if isinstance(term, list) and term[1] is control]
+    return [i for i, term in enumerate(nested) if isinstance(term, list) and unwrap(term[1]) is control]
 
 
 def extract_controls_mapping(objectives, controls):
@@ -153,11 +158,14 @@ def pulse_options_dict_to_list(pulse_options, controls):
 
 def plug_in_pulse_values(H, pulses, mapping, time_index, conjugate=False):
     """Copy of the nested list ``H`` with every control replaced by its pulse
-    value on interval ``time_index`` (reference conversions.py:288-330)."""
+    value on interval ``time_index`` (reference conversions.py:288-330); a
+    :class:`~krotov_amd.nonlinear.ControlFunction` g by ``g.value`` of it."""
     if isinstance(H, list):
         H = [list(term) if isinstance(term, list) else term for term in H]
     for pulse, positions in zip(pulses, mapping):
         for i in positions:
             value = pulse[time_index]
+            if isinstance(H[i][1], ControlFunction):
+                value = H[i][1].value(value)
             H[i][1] = np.conjugate(value) if conjugate else value
     return H

@@ -1,7 +1,7 @@
 // The body of the generic update kernels (kh_generic.h: kh_gen_forward_update, kh_gen_forward_update_par), included into
 // each of them so that the unparametrized kernel compiles to exactly the code it had as a function of its own (see
-// kh_tile64_update.inc).  Expects MIXED, PAR (constant expressions), the kernel's arguments p, u, ex, mx and pa (KhParArgs;
-// read only where PAR).
+// kh_tile64_update.inc).  Expects MIXED, PAR, NL (constant expressions), the kernel's arguments p, u, ex, mx, pa (KhParArgs;
+// read only where PAR) and na (KhNlArgs; read only where NL).
     extern __shared__ __attribute__((aligned(16))) char smem[];
     if (u.n_dev != nullptr) {
         u.n_begin = *u.n_dev;
@@ -74,7 +74,27 @@
         }
         // ---- pulse update (optimize.py:471-477): thread l takes control l ----
         const double dt = p.dt[n];
-        if (tid < L) {
+        if constexpr (NL) {
+            // non-linear controls: thread c takes control c -- the weighted sum over its terms, the update of eps_c, then
+            // eps_c^p_j (repeated products) into every slot j of the control
+            if (tid < na.C) {
+                const int c = tid;
+                double d1 = 0.0;
+                for (int j = 0; j < L; ++j)
+                    if (na.ctrl[j] == c) d1 += na.dcde[(size_t)j * (nt - 1) + n] * D_sh[j];
+                const double S = u.shape[(size_t)c * (nt - 1) + n];
+                const double lam = u.lambda[c];
+                const double e = u.guess[(size_t)c * (nt - 1) + n] + (S / lam) * d1;
+                s.ga[c] += (S / lam) * (d1 * d1) * dt;
+                if (blockIdx.x == 0) u.opt[(size_t)c * (nt - 1) + n] = e;
+                for (int j = 0; j < L; ++j) {
+                    if (na.ctrl[j] != c) continue;
+                    double v = e;
+                    for (int q = 1; q < na.power[j]; ++q) v *= e;
+                    s.eps[j] = v;
+                }
+            }
+        } else if (tid < L) {
             const int l = tid;
             const double S = u.shape[(size_t)l * (nt - 1) + n];
             const double lam = u.lambda[l];
@@ -115,5 +135,5 @@
         }
     }
     if (!u.internal_exchange && u.n_end < nt - 1 && tid < L) u.wg_partial[(size_t)blockIdx.x * L + tid] = s.part[tid];
-    if (blockIdx.x == 0 && tid < L) u.g_a[tid] = (u.internal_exchange ? 0.0 : u.g_a[tid]) + s.ga[tid];
+    if (blockIdx.x == 0 && tid < (NL ? na.C : L)) u.g_a[tid] = (u.internal_exchange ? 0.0 : u.g_a[tid]) + s.ga[tid];
     if (tid == 0 && p.stats != nullptr) atomicAdd(p.stats, matvecs);

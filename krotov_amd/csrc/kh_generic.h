@@ -394,6 +394,16 @@ struct KhParArgs {
     const double *b;     // [L]
 };
 
+// Non-linear controls (kh_set_nonlinear): the engine's L operator slots are J = L terms eps_c(j)^p_j H_j of C <= J
+// controls.  An argument of its own, as KhParArgs is, taken only by the kernels compiled for it (NL).  While set,
+// KhUpdateArgs::guess / shape / lambda / opt / g_a are C-row arrays of eps; wg_partial and D_in stay J sums.
+struct KhNlArgs {
+    const double *dcde;  // [J][nt-1] w_j = p_j eps_guess,c(j)^(p_j - 1): the derivative at the GUESS
+    const int *ctrl;     // [J] c(j)
+    const int *power;    // [J] p_j, 1..4
+    int C;
+};
+
 // The pulse update of interval n (optimize.py:471-477) as kh_tilen.h and kh_ell.h do it, called by every thread after the
 // exchange (kh_exchange_waves_finish): thread l writes control l's new value to eps_sh[l], adds its share to g_a_sh[l]
 // and, in workgroup 0, stores the value to u.opt.  Returns theta = ||H0|| + sum_l |eps_l| ||H_l|| of objective k.
@@ -598,18 +608,30 @@ __device__ __forceinline__ void kh_gen_partials(const KhSweepArgs &p, const KhUp
 // PAR (kh_gen_forward_update_par): with pulse parametrizations (kh_set_parametrization) -- thread l updates u_l and the
 // interval is propagated with f_l(u_l).  A kernel of its own, so that the unparametrized one keeps its code; both include
 // one body (kh_gen_update.inc).
+// NL (kh_gen_forward_update_nl): with non-linear controls (kh_set_nonlinear) -- thread c updates control c from the
+// weighted sums of its terms and writes eps_c^p_j for each of them; the L slots are the terms.  Again a kernel of its own.
 template <bool MIXED>
 __global__ void __launch_bounds__(KH_GEN_THREADS)
 kh_gen_forward_update(KhSweepArgs p, KhUpdateArgs u, KhExchange ex, KhMixedArgs mx) {
-    constexpr bool PAR = false;
+    constexpr bool PAR = false, NL = false;
     const KhParArgs pa{};
+    const KhNlArgs na{};
 #include "kh_gen_update.inc"
 }
 
 template <bool MIXED>
 __global__ void __launch_bounds__(KH_GEN_THREADS)
 kh_gen_forward_update_par(KhSweepArgs p, KhUpdateArgs u, KhExchange ex, KhMixedArgs mx, KhParArgs pa) {
-    constexpr bool PAR = true;
+    constexpr bool PAR = true, NL = false;
+    const KhNlArgs na{};
+#include "kh_gen_update.inc"
+}
+
+template <bool MIXED>
+__global__ void __launch_bounds__(KH_GEN_THREADS)
+kh_gen_forward_update_nl(KhSweepArgs p, KhUpdateArgs u, KhExchange ex, KhMixedArgs mx, KhNlArgs na) {
+    constexpr bool PAR = false, NL = true;
+    const KhParArgs pa{};
 #include "kh_gen_update.inc"
 }
 

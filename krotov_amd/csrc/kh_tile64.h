@@ -332,8 +332,9 @@ kh_tile_sweep_store_src(KhSweepArgs p, KhSrcArgs sa, const double *__restrict__ 
 template <int RPT, int LT, bool SO, bool SINGLE = false>
 __global__ void __launch_bounds__(512 / RPT, 2)
 kh_tile_forward_update(KhSweepArgs p, KhUpdateArgs u, KhExchange ex) {
-    constexpr bool PAR = false;
+    constexpr bool PAR = false, NL = false;
     const KhParArgs pa{};
+    const KhNlArgs na{};
 #include "kh_tile64_update.inc"
 }
 
@@ -341,6 +342,19 @@ kh_tile_forward_update(KhSweepArgs p, KhUpdateArgs u, KhExchange ex) {
 template <int RPT, int LT, bool SO>
 __global__ void __launch_bounds__(512 / RPT, 2)
 kh_tile_forward_update_par(KhSweepArgs p, KhUpdateArgs u, KhExchange ex, KhParArgs pa) {
-    constexpr bool PAR = true, SINGLE = true;
+    constexpr bool PAR = true, NL = false, SINGLE = true;
+    const KhNlArgs na{};
+#include "kh_tile64_update.inc"
+}
+
+// NL (kh_tile_forward_update_nl): with non-linear controls (kh_set_nonlinear) -- the LT slots are the terms
+// eps_c(l)^p_l H_l of C <= LT controls; the weights w_l are prefetched with the other per-interval scalars, the sums of a
+// control's terms are weighted and added after the exchange, h.build takes the powers.  The whole sweep in one launch on
+// one GPU (SINGLE), and a kernel of its own for the reason above; the PAR note on parked operators holds for it.
+template <int RPT, int LT, bool SO>
+__global__ void __launch_bounds__(512 / RPT, 2)
+kh_tile_forward_update_nl(KhSweepArgs p, KhUpdateArgs u, KhExchange ex, KhNlArgs na) {
+    constexpr bool PAR = false, NL = true, SINGLE = true;
+    const KhParArgs pa{};
 #include "kh_tile64_update.inc"
 }

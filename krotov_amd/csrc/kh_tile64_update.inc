@@ -1,8 +1,8 @@
 // The body of the register-tile update kernels (kh_tile64.h: kh_tile_forward_update, kh_tile_forward_update_par), included
 // into each of them: the two share every line, and the unparametrized kernel, which sits at the register limit, must
 // compile to exactly the code it had as a function of its own -- a shared device function, even a forced-inline one, moved
-// its register allocation.  Expects RPT, LT, SO, SINGLE, PAR (constant expressions), the kernel's arguments p, u, ex and pa
-// (KhParArgs; read only where PAR).
+// its register allocation.  Expects RPT, LT, SO, SINGLE, PAR, NL (constant expressions), the kernel's arguments p, u, ex, pa
+// (KhParArgs; read only where PAR) and na (KhNlArgs; read only where NL: the LT slots are then the terms eps_c(l)^p_l H_l).
     if (u.n_dev != nullptr) {  // graph-replayed stepwise mode: interval index from device memory
         u.n_begin = *u.n_dev;
         u.n_end = u.n_begin + 1;
@@ -124,16 +124,38 @@
     // per-interval scalars, fetched one interval ahead
     // (wave-uniform values are kept in scalar registers: with L = 3, 4 the per-control scalars
     // would otherwise cost ~60 VGPRs next to the operator tiles)
+    // (NL: term l reads the row of its control c(l) -- every per-term array below then holds its control's value, and no
+    // array is indexed by a run-time control number; nl_same[l]: the terms of the same control as a bit mask, l's bit set)
+    int nl_row[LT], nl_pow[LT], nl_same[LT];
+    if constexpr (NL) {
+#pragma unroll
+        for (int l = 0; l < LT; ++l) {
+            nl_row[l] = __builtin_amdgcn_readfirstlane(na.ctrl[l]);
+            nl_pow[l] = __builtin_amdgcn_readfirstlane(na.power[l]);
+        }
+#pragma unroll
+        for (int l = 0; l < LT; ++l) {
+            nl_same[l] = 0;
+#pragma unroll
+            for (int i = 0; i < LT; ++i) nl_same[l] |= (nl_row[i] == nl_row[l]) ? (1 << i) : 0;
+        }
+    }
     double dt_next = kh_uniform(p.dt[u.n_begin]), guess_next[LT], shape_next[LT], lam[LT];
 #pragma unroll
     for (int l = 0; l < LT; ++l) {
-        guess_next[l] = kh_uniform(u.guess[(size_t)l * (nt - 1) + u.n_begin]);
-        shape_next[l] = kh_uniform(u.shape[(size_t)l * (nt - 1) + u.n_begin]);
-        lam[l] = kh_uniform(u.lambda[l]);
+        const int row = NL ? nl_row[l] : l;
+        guess_next[l] = kh_uniform(u.guess[(size_t)row * (nt - 1) + u.n_begin]);
+        shape_next[l] = kh_uniform(u.shape[(size_t)row * (nt - 1) + u.n_begin]);
+        lam[l] = kh_uniform(u.lambda[row]);
     }
     // (PAR: `guess` is u_guess; the derivative travels with it, the kind and its two parameters stay for the sweep)
     double dfdu_next[LT], par_a[LT], par_b[LT];
     int par_kind[LT];
+    // (NL: the same three arrays carry the terms' weights w_l = d(eps^p_l)/d eps at the guess)
+    if constexpr (NL) {
+#pragma unroll
+        for (int l = 0; l < LT; ++l) dfdu_next[l] = kh_uniform(na.dcde[(size_t)l * (nt - 1) + u.n_begin]);
+    }
     if constexpr (PAR) {
 #pragma unroll
         for (int l = 0; l < LT; ++l) {
@@ -197,7 +219,7 @@
         }
         double dt_ld = 0.0, guess_ld[LT], shape_ld[LT];  // in flight across the barrier
         double dfdu[LT], dfdu_ld[LT];
-        if constexpr (PAR) {
+        if constexpr (PAR || NL) {
 #pragma unroll
             for (int l = 0; l < LT; ++l) dfdu[l] = dfdu_next[l];
         }
@@ -205,9 +227,11 @@
             dt_ld = p.dt[n + 1];
 #pragma unroll
             for (int l = 0; l < LT; ++l) {
-                guess_ld[l] = u.guess[(size_t)l * (nt - 1) + n + 1];
-                shape_ld[l] = u.shape[(size_t)l * (nt - 1) + n + 1];
+                const int row = NL ? nl_row[l] : l;
+                guess_ld[l] = u.guess[(size_t)row * (nt - 1) + n + 1];
+                shape_ld[l] = u.shape[(size_t)row * (nt - 1) + n + 1];
                 if constexpr (PAR) dfdu_ld[l] = pa.dfdu[(size_t)l * (nt - 1) + n + 1];
+                if constexpr (NL) dfdu_ld[l] = na.dcde[(size_t)l * (nt - 1) + n + 1];
             }
         }
         __syncthreads();
@@ -220,8 +244,30 @@
         // ---- pulse update (optimize.py:471-477) ----
         double eps[LT];
         double theta = nrm[0];
+        if constexpr (NL) {
+            // D_c = sum_{j in c} w_j D_j, formed once per term of the control (same terms, same order: the same value);
+            // eps_c written from every term of the control (the same value), g_a from its first term
+            double wd[LT];
 #pragma unroll
-        for (int l = 0; l < LT; ++l) {
+            for (int l = 0; l < LT; ++l) wd[l] = dfdu[l] * D_sh[par][l];
+#pragma unroll
+            for (int l = 0; l < LT; ++l) {
+                double d1 = 0.0;
+#pragma unroll
+                for (int i = 0; i < LT; ++i) d1 += ((nl_same[l] >> i) & 1) ? wd[i] : 0.0;
+                const double step = shape[l] / lam[l];
+                const double e = kh_uniform(guess[l] + step * d1);
+                g_a_loc[l] = kh_uniform(g_a_loc[l] + step * (d1 * d1) * dt);
+                if (k == 0 && tid == 0) u.opt[(size_t)nl_row[l] * (nt - 1) + n] = e;
+                double c = e;  // eps_c^p_l by repeated multiplication
+#pragma unroll
+                for (int q = 1; q < 4; ++q) c = q < nl_pow[l] ? c * e : c;
+                eps[l] = kh_uniform(c);
+                theta += fabs(eps[l]) * nrm[1 + l];
+            }
+        }
+#pragma unroll
+        for (int l = 0; !NL && l < LT; ++l) {
             double d1 = D_sh[par][l];
             if constexpr (PAR) d1 *= dfdu[l];  // dH/du = f'(u_guess) dH/d eps
             const double step = shape[l] / lam[l];
@@ -234,7 +280,7 @@
             }
             theta += fabs(eps[l]) * nrm[1 + l];
         }
-        if (k == 0 && tid == 0) {
+        if (!NL && k == 0 && tid == 0) {
 #pragma unroll
             for (int l = 0; l < LT; ++l) u.opt[(size_t)l * (nt - 1) + n] = eps[l];
         }
@@ -255,7 +301,7 @@
             for (int l = 0; l < LT; ++l) {
                 guess_next[l] = kh_uniform(guess_ld[l]);
                 shape_next[l] = kh_uniform(shape_ld[l]);
-                if constexpr (PAR) dfdu_next[l] = kh_uniform(dfdu_ld[l]);
+                if constexpr (PAR || NL) dfdu_next[l] = kh_uniform(dfdu_ld[l]);
             }
         }
         // ---- partial sums of the next interval (state is in buf[cur], barrier passed) ----
@@ -275,6 +321,12 @@
         if (tid == 0)
             for (int l = 0; l < LT; ++l) u.wg_partial[(size_t)k * LT + l] = part[l];
     }
-    if (k == 0 && tid == 0)
+    if constexpr (NL) {
+        if (k == 0 && tid == 0)
+            for (int l = 0; l < LT; ++l)
+                if ((nl_same[l] & ((1 << l) - 1)) == 0)  // (the control's first term)
+                    u.g_a[nl_row[l]] = (u.internal_exchange ? 0.0 : u.g_a[nl_row[l]]) + g_a_loc[l];
+    }
+    if (!NL && k == 0 && tid == 0)
         for (int l = 0; l < LT; ++l) u.g_a[l] = (u.internal_exchange ? 0.0 : u.g_a[l]) + g_a_loc[l];
     if (tid == 0 && p.stats != nullptr) atomicAdd(p.stats, matvecs);

@@ -301,7 +301,12 @@ struct kh_engine {
     double *d_par_ab = nullptr;  // [2][L] a, b
     std::vector<int> par_kind_host;   // what d_par_kind / d_par_ab hold
     std::vector<double> par_ab_host;
-    bool reduced_par = false;    // reduced_G was set while parametrized (kh_set_update_workgroups)
+    bool reduced_par = false;    // reduced_G was set while parametrized or non-linear (kh_set_update_workgroups)
+    // non-linear controls (kh_set_nonlinear); nl_dcde NULL = none.  The L slots are then J terms of nl_C controls
+    const double *nl_dcde = nullptr;
+    int nl_C = 0;
+    int *d_nl_tab = nullptr;          // [2][L] the engine's own copy: term -> control, term -> power
+    std::vector<int> nl_tab_host;     // what d_nl_tab holds
     // cross-GPU exchange (kh_p2p_*): objectives sharded over `p2p_world` ranks
     int p2p_world = 1, p2p_rank = 0;
     kh_u64 *p2p_window = nullptr;            // this rank's window (fine-grained device memory)
@@ -2557,16 +2562,37 @@ static int launch_tile_update_par(kh_engine *e, const KhSweepArgs &p, const KhUp
     });
 }
 
-// PAR: the kernels with pulse parametrizations (kh_set_parametrization) -- every update sweep of a parametrized engine
+static KhNlArgs nl_args(const kh_engine *e) {
+    return KhNlArgs{e->nl_dcde, e->d_nl_tab, e->d_nl_tab + e->L, e->nl_C};
+}
+
+// the register-tile kernel's non-linear form (kh_set_nonlinear): as launch_tile_update_par, with LT = terms
+template <int RPT, int LT>
+static int launch_tile_update_nl(kh_engine *e, const KhSweepArgs &p, const KhUpdateArgs &u, const KhExchange &ex,
+                                 hipStream_t st) {
+    constexpr size_t lds = KhTileLds<RPT, LT>::bytes(KhTileLds<RPT, LT>::UPDATE);
+    const dim3 g(e->K), b(512 / RPT);
+    KhExchange exl = ex;
+    if (LT >= 2 && !e->sw.poll_delay_set) exl.first_poll_delay = 24 + 4 * (LT - 2);  // (as launch_tile_update)
+    e->last_update_grid = e->K;
+    return with_bool(u.sigma != nullptr, [&](auto so) {
+        return launch_persistent_lds<kh_tile_forward_update_nl<RPT, LT, decltype(so)::value>>(e, g, b, lds, st, p, u, exl, nl_args(e));
+    });
+}
+
+// FORM_PAR: the kernels with pulse parametrizations (kh_set_parametrization) -- every update sweep of a parametrized engine
 // comes here, whatever its family: the single launch then runs on min(K, max_wgs) workgroups (or what
-// kh_set_update_workgroups allows), each taking its objectives in turns
-template <bool PAR>
+// kh_set_update_workgroups allows), each taking its objectives in turns.  FORM_NL: the same for non-linear controls
+// (kh_set_nonlinear).
+enum { FORM_LINEAR = 0, FORM_PAR = 1, FORM_NL = 2 };
+template <int FORM>
 static int update_generic(kh_engine *e, const KhSweepArgs &p, const KhUpdateArgs &u, const KhExchange &ex_in, hipStream_t st) {
     if (!e->gen_fits)
         return kh_fail(KH_ERR_UNSUPPORTED, "N=%d: this form of the update sweep needs the generic kernels, whose vectors do not fit LDS", e->N);
     const size_t lds = kh_gen_lds_bytes(e->N, e->d_csr_fw == nullptr);
-    const void *fn = PAR ? (e->mixed ? (const void *)kh_gen_forward_update_par<true> : (const void *)kh_gen_forward_update_par<false>)
-                         : (e->mixed ? (const void *)kh_gen_forward_update<true> : (const void *)kh_gen_forward_update<false>);
+    const void *fn = FORM == FORM_PAR  ? (e->mixed ? (const void *)kh_gen_forward_update_par<true> : (const void *)kh_gen_forward_update_par<false>)
+                     : FORM == FORM_NL ? (e->mixed ? (const void *)kh_gen_forward_update_nl<true> : (const void *)kh_gen_forward_update_nl<false>)
+                                       : (e->mixed ? (const void *)kh_gen_forward_update<true> : (const void *)kh_gen_forward_update<false>);
     int rc = ensure_dynamic_lds(e, fn, lds);
     ensure_gen_scratch(e, e->plan.grid_update);
     if (rc != KH_OK) return rc;
@@ -2587,7 +2613,7 @@ static int update_generic(kh_engine *e, const KhSweepArgs &p, const KhUpdateArgs
     if (e->gen_adj_ready && u.sigma == nullptr) ug.adj_store = e->d_gen_adj;
     KhExchange ex = ex_in;
     int G = e->plan.grid_update;
-    if (PAR && ug.internal_exchange) {
+    if (FORM != FORM_LINEAR && ug.internal_exchange) {
         // (an engine of another family may hold more workgroups than the exchange of this kernel takes, or fewer
         // were asked for: the workgroups walk through the objectives)
         if (G > e->plan.max_wgs) G = e->plan.max_wgs;
@@ -2600,12 +2626,18 @@ static int update_generic(kh_engine *e, const KhSweepArgs &p, const KhUpdateArgs
     return with_bool(e->mixed, [&](auto mixed) {
         constexpr bool MIXED = decltype(mixed)::value;
         const KhMixedArgs mx = MIXED ? e->mixed_fw : KhMixedArgs{};
-        if constexpr (PAR) {
+        if constexpr (FORM == FORM_PAR) {
             if (!ug.internal_exchange) {
                 launch_plain<kh_gen_forward_update_par<MIXED>>(g, b, lds, st, pg, ug, ex, mx, par_args(e));
                 return (int)KH_OK;
             }
             return launch_persistent<kh_gen_forward_update_par<MIXED>>(e, g, b, lds, st, pg, ug, ex, mx, par_args(e));
+        } else if constexpr (FORM == FORM_NL) {
+            if (!ug.internal_exchange) {
+                launch_plain<kh_gen_forward_update_nl<MIXED>>(g, b, lds, st, pg, ug, ex, mx, nl_args(e));
+                return (int)KH_OK;
+            }
+            return launch_persistent<kh_gen_forward_update_nl<MIXED>>(e, g, b, lds, st, pg, ug, ex, mx, nl_args(e));
         } else {
             if (!ug.internal_exchange) {
                 launch_plain<kh_gen_forward_update<MIXED>>(g, b, lds, st, pg, ug, ex, mx);
@@ -2654,9 +2686,9 @@ static int launch_update(kh_engine *e, const KhUpdateArgs &u, hipStream_t st) {
     const bool whole = !stepwise && u.n_begin == 0 && u.n_end == e->nt - 1;
     e->last_update_grid = 0;
     int rc = KH_OK;
-    if (e->par_dfdu != nullptr) {
-        // pulse parametrizations (kh_set_parametrization): the whole sweep of a register-tile engine (q2 kind, mini and
-        // quad included: the kernel they already run stepwise) on the tile kernel's parametrized form while its K workgroups
+    if (e->par_dfdu != nullptr || e->nl_dcde != nullptr) {
+        // pulse parametrizations (kh_set_parametrization) and non-linear controls (kh_set_nonlinear): the whole sweep of a register-tile engine (q2 kind, mini and
+        // quad included: the kernel they already run stepwise) on the tile kernel's form for them while its K workgroups
         // are all resident; everything else -- other families, stepwise launches, reduced grids -- on the generic one
         const KhPlan &pl = e->plan;
         const bool tile_kind = pl.kind == KIND_TILE_Q2 || pl.kind == KIND_TILE_RPT1 || pl.kind == KIND_TILE_RPT2;
@@ -2664,12 +2696,14 @@ static int launch_update(kh_engine *e, const KhUpdateArgs &u, hipStream_t st) {
         if (whole && tile_kind && !pl.ens && !pl.stream && !pl.stepwise_only && pl.grid_update == e->K && e->K > 1 &&
             e->reduced_G == 0 && ex.world == 1 && ex.G == e->K && e->sw.tile_single && !e->mixed && e->d_csr_fw == nullptr &&
             e->N <= KH_TILE_N && e->L >= 1 && e->L <= 4) {
+            const bool nl = e->nl_dcde != nullptr;
             rc = with_tile(pl.kind == KIND_TILE_RPT2, e->L, [&](auto rpt, auto lt) {
+                if (nl) return launch_tile_update_nl<decltype(rpt)::value, decltype(lt)::value>(e, p, u, ex, st);
                 return launch_tile_update_par<decltype(rpt)::value, decltype(lt)::value>(e, p, u, ex, st);
             });
             if (rc != KH_OK && rc != KH_ERR_UNSUPPORTED) return rc;  // (unsupported: the grid cannot be resident)
         }
-        if (rc != KH_OK) rc = update_generic<true>(e, p, u, ex, st);
+        if (rc != KH_OK) rc = e->nl_dcde != nullptr ? update_generic<FORM_NL>(e, p, u, ex, st) : update_generic<FORM_PAR>(e, p, u, ex, st);
         if (rc != KH_OK) return rc;
         KH_HIP(hipGetLastError());
         return KH_OK;
@@ -2695,7 +2729,7 @@ static int launch_update(kh_engine *e, const KhUpdateArgs &u, hipStream_t st) {
             });
             break;
         case ROUTE_TILEX: rc = update_tilex(e, p, u, ex, st); break;
-        case ROUTE_GENERIC: rc = update_generic<false>(e, p, u, ex, st); break;
+        case ROUTE_GENERIC: rc = update_generic<FORM_LINEAR>(e, p, u, ex, st); break;
         case ROUTE_LIND: rc = update_lind(e, p, u, ex, st); break;
     }
     if (rc != KH_OK) return rc;
@@ -2830,8 +2864,8 @@ extern "C" int kh_set_update_workgroups(kh_engine *e, int32_t max_workgroups, in
     if (e->p2p_ready) return kh_fail(KH_ERR_UNSUPPORTED, "sharded sweeps keep their grid (all ranks must agree on the form)");
     const KhPlan &p = e->plan;
     int G = 0;
-    if (e->par_dfdu != nullptr) {
-        // a parametrized engine (kh_set_parametrization): the generic kernels take their objectives in turns on any grid
+    if (e->par_dfdu != nullptr || e->nl_dcde != nullptr) {
+        // a parametrized or non-linear engine (kh_set_parametrization, kh_set_nonlinear): the generic kernels take their objectives in turns on any grid
         G = p.grid_update < p.max_wgs ? p.grid_update : p.max_wgs;
         if (max_workgroups < G) G = max_workgroups;
         e->reduced_par = true;  // (not a grid the engine's own family was asked about: dropped with the parametrization)
@@ -2895,6 +2929,7 @@ extern "C" int kh_set_row_split(kh_engine *e, int workgroups_per_objective) {
         return KH_OK;
     }
     if (e->par_dfdu != nullptr) return kh_fail(KH_ERR_UNSUPPORTED, "a parametrized engine (kh_set_parametrization) keeps one workgroup per objective");
+    if (e->nl_dcde != nullptr) return kh_fail(KH_ERR_UNSUPPORTED, "an engine with non-linear controls (kh_set_nonlinear) keeps one workgroup per objective");
     const int max_wgs = e->plan.max_wgs;  // (what the exchange takes: at most 256, at most one per CU)
     if (S > e->num_cus || S > max_wgs)
         return kh_fail(KH_ERR_UNSUPPORTED, "%d workgroups per objective: this device runs at most %d at once", S, e->num_cus < max_wgs ? e->num_cus : max_wgs);
@@ -2958,6 +2993,7 @@ extern "C" int kh_set_parametrization(kh_engine *e, const int32_t *kind, const d
     if (e->row_split > 1) return kh_fail(KH_ERR_UNSUPPORTED, "a split engine (kh_set_row_split) takes no pulse parametrization: set the row split to 1 first");
     if (!e->gen_fits) return kh_fail(KH_ERR_UNSUPPORTED, "N=%d: pulse parametrizations run on the generic kernels, whose vectors do not fit LDS", e->N);
     if (e->L < 1) return kh_fail(KH_ERR_INVALID, "no controls to parametrize");
+    if (e->nl_dcde != nullptr) return kh_fail(KH_ERR_INVALID, "non-linear controls are set (kh_set_nonlinear): the two are not combined");
     if (a == nullptr || b == nullptr || u_guess_dev == nullptr || dfdu_dev == nullptr || u_opt_dev == nullptr)
         return kh_fail(KH_ERR_INVALID, "null argument");
     if (u_opt_dev == u_guess_dev) return kh_fail(KH_ERR_INVALID, "u_opt_dev must not alias u_guess_dev");
@@ -2982,6 +3018,49 @@ extern "C" int kh_set_parametrization(kh_engine *e, const int32_t *kind, const d
     e->par_u_guess = u_guess_dev;
     e->par_dfdu = dfdu_dev;
     e->par_u_opt = u_opt_dev;
+    return KH_OK;
+}
+
+// Non-linear controls (include/krotov_hip.h): the engine's L slots become terms eps_c^p H_j of C controls; the following
+// update sweeps run kh_tile_forward_update_nl or kh_gen_forward_update_nl, by launch_update's rule
+extern "C" int kh_set_nonlinear(kh_engine *e, int32_t C, const int32_t *term_control, const int32_t *term_power,
+                                const double *dcde_dev) {
+    if (e == nullptr) return kh_fail(KH_ERR_INVALID, "null engine");
+    if (term_control == nullptr) {
+        e->nl_dcde = nullptr;
+        e->nl_C = 0;
+        if (e->reduced_par) e->reduced_G = 0;  // (a reduced grid set while non-linear goes with it)
+        e->reduced_par = false;
+        return KH_OK;
+    }
+    if (e->lind) return kh_fail(KH_ERR_UNSUPPORTED, "Lindblad-form engines (kh_engine_create_lindblad) take no non-linear controls: build the Liouvillian and use kh_engine_create");
+    if (e->replicas > 0) return kh_fail(KH_ERR_UNSUPPORTED, "replica engines (kh_engine_create_replicas) take no non-linear controls");
+    if (e->p2p_ready || e->p2p_window != nullptr) return kh_fail(KH_ERR_UNSUPPORTED, "sharded engines take no non-linear controls (one GPU)");
+    if (e->row_split > 1) return kh_fail(KH_ERR_UNSUPPORTED, "a split engine (kh_set_row_split) takes no non-linear controls: set the row split to 1 first");
+    if (!e->gen_fits) return kh_fail(KH_ERR_UNSUPPORTED, "N=%d: non-linear controls run on the generic kernels, whose vectors do not fit LDS", e->N);
+    if (e->L < 1) return kh_fail(KH_ERR_INVALID, "no terms");
+    if (e->par_dfdu != nullptr) return kh_fail(KH_ERR_INVALID, "a pulse parametrization is set (kh_set_parametrization): the two are not combined");
+    if (term_power == nullptr || dcde_dev == nullptr) return kh_fail(KH_ERR_INVALID, "null argument");
+    if (C < 1 || C > e->L) return kh_fail(KH_ERR_INVALID, "%d controls for %d terms", (int)C, e->L);
+    std::vector<int> tab(term_control, term_control + e->L);
+    tab.insert(tab.end(), term_power, term_power + e->L);
+    std::vector<bool> seen((size_t)C, false);
+    for (int j = 0; j < e->L; ++j) {
+        if (tab[j] < 0 || tab[j] >= C) return kh_fail(KH_ERR_INVALID, "term %d: control %d outside 0..%d", j, tab[j], (int)C - 1);
+        if (tab[e->L + j] < 1 || tab[e->L + j] > 4) return kh_fail(KH_ERR_INVALID, "term %d: power %d outside 1..4", j, tab[e->L + j]);
+        seen[(size_t)tab[j]] = true;
+    }
+    for (int c = 0; c < C; ++c)
+        if (!seen[(size_t)c]) return kh_fail(KH_ERR_INVALID, "control %d has no term", c);
+    if (e->d_nl_tab == nullptr) KH_TRY(dev_alloc(e, &e->d_nl_tab, sizeof(int) * 2 * (size_t)e->L));
+    // (as kh_set_parametrization: the table is uploaded when it changes, behind a device-wide wait)
+    if (tab != e->nl_tab_host) {
+        KH_HIP(hipDeviceSynchronize());
+        KH_HIP(hipMemcpy(e->d_nl_tab, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice));
+        e->nl_tab_host = tab;
+    }
+    e->nl_dcde = dcde_dev;
+    e->nl_C = C;
     return KH_OK;
 }
 
@@ -3014,9 +3093,10 @@ extern "C" int kh_update_begin(kh_engine *e, const kh_cdouble *chi_store_dev, co
     e->guess_dev = guess_dev;
     KH_HIP(hipMemsetAsync(e->d_stats, 0, sizeof(double) * 4, st));
     KH_HIP(hipMemcpyAsync(e->d_phi, init_dev, sizeof(cplx) * (size_t)e->K * e->N, hipMemcpyDeviceToDevice, st));
-    KH_HIP(hipMemcpyAsync(opt_dev, guess_dev, sizeof(double) * (size_t)e->L * (e->nt - 1),
+    const int rows = e->nl_dcde != nullptr ? e->nl_C : e->L;  // (non-linear controls: the pulses are C rows of eps)
+    KH_HIP(hipMemcpyAsync(opt_dev, guess_dev, sizeof(double) * (size_t)rows * (e->nt - 1),
                           hipMemcpyDeviceToDevice, st));
-    KH_HIP(hipMemsetAsync(g_a_dev, 0, sizeof(double) * e->L, st));
+    KH_HIP(hipMemsetAsync(g_a_dev, 0, sizeof(double) * rows, st));
     if (e->par_dfdu != nullptr)
         KH_HIP(hipMemcpyAsync(e->par_u_opt, e->par_u_guess, sizeof(double) * (size_t)e->L * (e->nt - 1), hipMemcpyDeviceToDevice, st));
     const KhUpdateArgs u = update_args(e, chi_store_dev, chi_norms_dev, guess_dev, nullptr, nullptr, opt_dev, g_a_dev);
@@ -3102,6 +3182,7 @@ extern "C" int kh_p2p_create_window(kh_engine *e, int32_t world, int32_t rank, u
     if (e->lind) return kh_fail(KH_ERR_UNSUPPORTED, "Lindblad-form engines (kh_engine_create_lindblad) are not sharded");
     if (e->replicas > 0) return kh_fail(KH_ERR_UNSUPPORTED, "replica engines (kh_engine_create_replicas) are not sharded");
     if (e->par_dfdu != nullptr) return kh_fail(KH_ERR_UNSUPPORTED, "a parametrized engine (kh_set_parametrization) is not sharded");
+    if (e->nl_dcde != nullptr) return kh_fail(KH_ERR_UNSUPPORTED, "an engine with non-linear controls (kh_set_nonlinear) is not sharded");
     const int Lx = e->L > 0 ? e->L : 1;
     if (world * Lx * 2 > 64 || Lx > KH_MAX_L)
         return kh_fail(KH_ERR_UNSUPPORTED, "world * L = %d exceeds the 32 exchange lanes (or more than %d controls)", world * Lx, KH_MAX_L);

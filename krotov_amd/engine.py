@@ -591,6 +591,34 @@ class HipKrotovEngine:
             u_opt.data_ptr()))
         self._par = (u_guess, dfdu, u_opt)  # keep the tensors alive while the engine points at them
 
+    def set_nonlinear(self, term_control=None, term_power=None, dcde=None):
+        """Switch the following update sweeps to non-linear controls (``kh_set_nonlinear``): the engine's L operator slots
+        are terms ``eps_c^p H_j``.  ``term_control``, ``term_power``: (L,) host arrays, the control (0 .. C-1, C its
+        largest entry + 1) and the power (1 .. 4) of every term; ``dcde``: (L, nt-1) ``p eps_guess^(p-1)`` under the
+        guess pulses.  While set, :meth:`forward_update` and :meth:`forward_update_sharded` take ``guess``, ``shape``
+        and ``lambdas`` with C rows and return ``opt`` and ``g_a`` with C rows; every other sweep keeps taking L rows
+        of term coefficients.  No arguments: off again.  ``KrotovHipError``: ``KH_ERR_UNSUPPORTED`` on replica,
+        Lindblad-form and sharded engines, ``KH_ERR_INVALID`` for a bad table or next to a parametrization."""
+        if term_control is None:
+            self._nl = None
+            _lib.check(self._lib.kh_set_nonlinear(self._handle, 0, None, None, None))
+            return
+        L = self.L
+        ctrl = np.ascontiguousarray(term_control, dtype=np.int32).reshape(L)
+        power = np.ascontiguousarray(term_power, dtype=np.int32).reshape(L)
+        C = int(ctrl.max()) + 1 if L else 0
+        if self.replicas or dcde is None:  # (the library's own answer, as set_parametrization)
+            _lib.check(self._lib.kh_set_nonlinear(self._handle, C, ctrl.ctypes.data, power.ctypes.data, None))
+            return
+        dcde = self._f(dcde, (L, self.nt - 1))
+        _lib.check(self._lib.kh_set_nonlinear(self._handle, C, ctrl.ctypes.data, power.ctypes.data, dcde.data_ptr()))
+        self._nl = (C, dcde)  # keep the tensor alive while the engine points at it
+
+    def _update_rows(self):
+        """Rows of the update sweeps' pulse-like arrays: the controls of :meth:`set_nonlinear`, else L."""
+        nl = getattr(self, '_nl', None)
+        return nl[0] if nl is not None else self.L
+
     def set_second_order_replicas(self, fw_prev=None, fw_store=None, sigma_vals=None):
         """Replica engines: switch the following update sweeps to the second-order update with one sigma row per
         replica (``fw_prev``, ``fw_store``: (K, nt, N) device tensors; ``sigma_vals``: (B, nt-1), sigma_b at replica
@@ -644,15 +672,16 @@ class HipKrotovEngine:
     def forward_update(self, chi_store, chi_norms, init, guess, shape, lambdas, out=None):
         """Forward sweep with sequential update; returns ``(opt, psi_T, g_a)``.  Replica engines: ``guess``, ``shape`` and
         ``opt`` are (B, L, nt-1), ``lambdas`` and ``g_a`` (B, L).  ``out``: ``(opt, psi_T, g_a)`` tensors to write into."""
-        per_control = (self.replicas, self.L) if self.replicas else (self.L,)
+        per_control = (self.replicas, self.L) if self.replicas else (self._update_rows(),)
+        pulse_shape = self._pulse_shape() if self.replicas else (self._update_rows(), self.nt - 1)
         chi_store = self._c(chi_store, (self.K, self.nt, self.N))
         chi_norms = self._f(chi_norms, (self.K,))
         init = self._c(init, (self.K, self.N))
-        guess = self._f(guess, self._pulse_shape())
-        shape = self._f(shape, self._pulse_shape())
+        guess = self._f(guess, pulse_shape)
+        shape = self._f(shape, pulse_shape)
         lambdas = self._f(lambdas, per_control)
         out = (None, None, None) if out is None else out
-        opt = self._out(out[0], self._pulse_shape(), torch.float64)
+        opt = self._out(out[0], pulse_shape, torch.float64)
         psi_T = self._out(out[1], (self.K, self.N), torch.complex128)
         g_a = self._out(out[2], per_control, torch.float64)
         with self._timed('update'):
@@ -678,17 +707,18 @@ class HipKrotovEngine:
         """
         if graph_chunk is None:
             graph_chunk = int(os.environ.get('KH_GRAPH_CHUNK', '64'))
-        nt, L, K, N = self.nt, self.L, self.K, self.N
+        nt, K, N = self.nt, self.K, self.N
+        L = self._update_rows()  # (non-linear controls: C rows of eps; the interval's sums stay one per term)
         # persistent buffers: stable addresses let the captured graph be reused
         b = getattr(self, '_sh', None)
-        if b is None:
+        if b is None or b['rows'] != L:
             c128, f64 = torch.complex128, torch.float64
             b = self._sh = dict(
                 chi_norms=self._empty((K,), f64), init=self._empty((K, N), c128), guess=self._empty((L, nt - 1), f64),
                 shape=self._empty((L, nt - 1), f64), lambdas=self._empty((L,), f64), opt=self._empty((L, nt - 1), f64),
-                psi_T=self._empty((K, N), c128), g_a=self._empty((L,), f64), partial=self._empty((L,), f64).zero_(),
+                psi_T=self._empty((K, N), c128), g_a=self._empty((L,), f64), partial=self._empty((self.L,), f64).zero_(),
                 n_dev=self._empty((1,), torch.int32).zero_(),
-                graph=None, graph_key=None,
+                graph=None, graph_key=None, rows=L,
             )
         chi_store = self._c(chi_store, (K, nt, N))
         b['chi_norms'].copy_(self._f(chi_norms, (K,)))
@@ -728,7 +758,9 @@ class HipKrotovEngine:
             done = False
             # (second order: kh_update_step_dev bakes the trajectory / sigma pointers of kh_set_second_order
             # into the captured launches, and those buffers are swapped every iteration -- no replay there)
-            if graph_chunk > 0 and nt - 1 > 2 * graph_chunk and getattr(self, '_so', None) is None:
+            # (non-linear controls: the weights' tensor of set_nonlinear is a new one every iteration, too)
+            if (graph_chunk > 0 and nt - 1 > 2 * graph_chunk and getattr(self, '_so', None) is None
+                    and getattr(self, '_nl', None) is None):
                 try:
                     stepper = _Stepper()
                     stepper.begin()

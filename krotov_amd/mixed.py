@@ -129,7 +129,8 @@ class LindbladLayout:
         return out
 
 
-def lindblad_layout_of(objectives, propagator=None, n_controls=None, second_order=False, parametrized=False):
+def lindblad_layout_of(objectives, propagator=None, n_controls=None, second_order=False, parametrized=False,
+                       nonlinear=False):
     """Decide, on the host, how a list in which some objective carries ``c_ops`` runs (see :class:`LindbladLayout`).
     A control inside ``c_ops`` raises ``NotImplementedError`` (as the reference's ``mu`` does, mu.py:135-139).  Objectives
     without ``c_ops`` are fine in a matrix-form list when they, too, are d x d density matrices under a d x d
@@ -141,6 +142,8 @@ def lindblad_layout_of(objectives, propagator=None, n_controls=None, second_orde
         return LindbladLayout('liouvillian', "second-order update (sigma=)")
     if parametrized:
         return LindbladLayout('liouvillian', "pulse parametrization ('parametrization' in pulse_options)")
+    if nonlinear:
+        return LindbladLayout('liouvillian', "non-linear controls (a ControlFunction in H)")
     ds, n_c = set(), 0
     for k, obj in enumerate(objectives):
         op = _drift(obj, k)

@@ -1,4 +1,6 @@
-"""dH/d(eps) for equations of motion that are linear in the controls.
+"""dH/d(eps): the control operator itself where the equation of motion is linear in the control, and
+sum_i g_i'(eps) H_i, evaluated for the pulses handed in, where terms are written with a
+:class:`~krotov_amd.nonlinear.ControlFunction` g_i.
 
 Same signature as ``krotov.mu.derivative_wrt_pulse`` (reference
 src/krotov/mu.py:74-140).  On the device this operator is never built per
@@ -8,6 +10,7 @@ Liouvillians (csrc/kh_generic.h, KhUpdateArgs::mu_re/mu_im).
 import numpy as np
 
 from ._ingest import obj_type, to_dense
+from .nonlinear import ControlFunction
 
 __all__ = ['derivative_wrt_pulse']
 
@@ -29,9 +32,19 @@ def derivative_wrt_pulse(objectives, i_objective, pulses, pulses_mapping, i_puls
         return lambda state: 0 * state
     first = objective.H[where[0]][0]
     is_super = obj_type(first) == 'super'
-    total = first
-    for i in where[1:]:
-        total = total + objective.H[i][0]
+    if any(isinstance(objective.H[i][1], ControlFunction) for i in where):
+        # non-linear in the control: the derivative at the pulse value of this interval (the guess pulses, where the
+        # update sweep asks: reference docs/07_krotovs_method.rst:339-347)
+        eps = pulses[i_pulse][time_index]
+        total = None
+        for i in where:
+            g = objective.H[i][1]
+            w = g.derivative(eps) if isinstance(g, ControlFunction) else 1.0
+            total = w * objective.H[i][0] if total is None else total + w * objective.H[i][0]
+    else:
+        total = first
+        for i in where[1:]:
+            total = total + objective.H[i][0]
     if is_super:
         total = 1j * total
     if hasattr(total, 'full') or callable(total):

@@ -197,7 +197,10 @@ class Objective:
 
         from .optimize import _HipBackend, _use_device_path  # (imports this module)
 
-        if _use_device_path(propagator, None, None, None, 'array', [system]) and len(tlist) > 1:
+        from .nonlinear import needs_host_loop
+
+        if (_use_device_path(propagator, None, None, None, 'array', [system]) and len(tlist) > 1
+                and not needs_host_loop([system])):
             backend = _HipBackend([system], mapping, tlist, len(controls), propagator)
             _, trajectories = backend.initial_forward(pulses, store=True)
             states = list(trajectories[0])
@@ -446,6 +449,7 @@ def propagate_objectives(objectives, tlist, *, propagator, e_ops=None, args=None
     (or a single grid point) runs the per-objective loop.  One GPU."""
     from ._ingest import state_array, to_dense
     from .conversions import control_onto_interval, discretize, extract_controls, extract_controls_mapping
+    from .nonlinear import needs_host_loop
     from .optimize import _HipBackend, _use_device_path  # (imports this module)
 
     objectives = list(objectives)
@@ -460,7 +464,7 @@ def propagate_objectives(objectives, tlist, *, propagator, e_ops=None, args=None
     systems = [Objective(initial_state=obj.initial_state if initial_states[k] is None else initial_states[k], H=obj.H,
                          target=obj.target, c_ops=obj.c_ops) for k, obj in enumerate(objectives)]
     if K == 0 or len(props) != K or len(tlist) < 2 \
-            or not _use_device_path(propagator, None, None, None, 'array', systems):
+            or not _use_device_path(propagator, None, None, None, 'array', systems) or needs_host_loop(systems):
         return [obj.propagate(tlist, propagator=props[k] if len(props) == K else propagator, rho0=initial_states[k],
                               e_ops=rows[k], args=args, expect=expect) for k, obj in enumerate(objectives)]
 

@@ -54,6 +54,7 @@ from ._update_ladder import UpdateLadder as _UpdateLadder, leave_row_split as _l
 _KH_MAX_CONTROLS = 32  # KH_GEN_MAX_L of krotov_amd/csrc/kh_common.h (the register-resident kernel families: 8)
 from .mixed import Layout, LindbladLayout, layout_of, lindblad_layout_of
 from .mu import derivative_wrt_pulse
+from .nonlinear import has_control_function, term_plan
 from .parallelization import serial_map
 from .parametrization import Parametrization, PulseParameters
 from .propagators import HipExpm, LindbladExpm, Propagator, expm
@@ -628,8 +629,12 @@ class _HipBackend:
         # objectives in Lindblad form (H + c_ops): the matrix-form engine, or -- outside its limits -- the Liouvillian
         # built on the host and today's engines (host-only decision)
         self.lindblad = None
+        nonlinear = has_control_function(objectives, c_ops_too=False)
+        if nonlinear and process_group is not None:
+            raise ValueError("non-linear controls (ControlFunction) run on one GPU: process_group= (sharding) is not "
+                             "supported with them")
         if any(len(obj.c_ops) > 0 for obj in objectives):
-            lind = lindblad_layout_of(objectives, propagator, n_controls, second_order, parametrized)
+            lind = lindblad_layout_of(objectives, propagator, n_controls, second_order, parametrized, nonlinear)
             if lind.matrix:
                 if process_group is not None:
                     raise ValueError("objectives in Lindblad form run on one GPU: process_group= (sharding) is not "
@@ -648,11 +653,19 @@ class _HipBackend:
         self.layout = layout if layout.mixed else None
         self.K_total = K_total
         L = n_controls
+        # non-linear controls (krotov_amd.nonlinear): one operator slot per distinct (control, power) -- the engine's
+        # plain, backward and source sweeps take the J rows of term coefficients eps_c^p, its update sweep the L rows
+        # of eps and the weights p eps_guess^(p-1) (kh_set_nonlinear)
+        self.nl = term_plan(objectives, pulses_mapping, n_controls) if nonlinear else None
+        if self.nl is False:
+            raise ValueError("a ControlFunction that is no integer power (power None) runs the host loop, not the "
+                             "device's sweeps")
+        op_mapping, n_slots = (pulses_mapping, L) if self.nl is None else (self.nl.mapping, self.nl.J)
         props = propagator if isinstance(propagator, list) else [propagator]
         # operators stay in CSR form on the device when the propagator asks for it
         # (DensityMatrixODEPropagator / HipExpm(sparse=True): large sparse Liouvillians)
         self.sparse = any(isinstance(p, HipExpm) and getattr(p, 'sparse', False) for p in props)
-        ops, c_rows = _operator_rows(objectives, pulses_mapping, L, to_sparse if self.sparse else to_dense,
+        ops, c_rows = _operator_rows(objectives, op_mapping, n_slots, to_sparse if self.sparse else to_dense,
                                      self.k0, self.k1)
         N = layout.stride
         self.is_super = layout.kinds[self.k0:self.k1] if layout.mixed else layout.kinds[self.k0]
@@ -691,6 +704,9 @@ class _HipBackend:
         self.fw_prev = self.fw_next = None  # second order: phi(t_n) of the last / the running iteration
         self.last_chi = None
         self._uploads = _UploadCache(self.engine, torch.float64)
+        if self.nl is not None:
+            self._nl_rows = self.engine.dev(self.nl.term_control.astype(np.int64), torch.int64)
+            self._nl_pow = self.engine.dev(self.nl.term_power.astype(np.float64)[:, None], torch.float64)
         self._src_store = None  # W_k(t_n) of a state-dependent constraint (_constraint_source)
         self._li_route = None  # (constructor, its device arguments or None): local_invariants_route, decided once
         self._ladder = _UpdateLadder(self.engine)  # (one GPU) the single-launch update sweep's retries
@@ -714,6 +730,30 @@ class _HipBackend:
         if cached:  # (the guess of an iteration is normally the optimized pulse of the one before: still on the device)
             return self._uploads.get('pulses', host)
         return self.engine.dev(host, self.torch.float64)
+
+    def _terms(self, pulses):
+        """What the plain, backward and source sweeps propagate with: the (L, nt-1) device tensor ``pulses`` itself,
+        or -- non-linear controls -- the (J, nt-1) term coefficients eps_c^p, formed on the device by repeated
+        products (as the update kernels form them)."""
+        if self.nl is None:
+            return pulses
+        t = self.torch
+        rows = pulses.index_select(0, self._nl_rows)
+        coef = rows
+        for q in range(1, 4):
+            coef = t.where(self._nl_pow > q, coef * rows, coef)
+        return coef.contiguous()
+
+    def _set_nonlinear(self, guess):
+        """Non-linear controls: the weights w_j = p_j eps_guess^(p_j - 1) of the update sweep, formed on the device
+        (kh_set_nonlinear); returns the term coefficients under the guess pulses for the backward sweep."""
+        t = self.torch
+        rows = guess.index_select(0, self._nl_rows)
+        dcde = self._nl_pow.expand_as(rows)
+        for q in range(1, 4):
+            dcde = t.where(self._nl_pow - 1 >= q, dcde * rows, dcde)
+        self.engine.set_nonlinear(self.nl.term_control, self.nl.term_power, dcde.contiguous())
+        return self._terms(guess)
 
     def state_vector(self, state, k):
         """``state`` of objective k as the engine's row (zero-padded to the stride on mixed lists), or None."""
@@ -747,9 +787,10 @@ class _HipBackend:
         forward_states = None
         if store:
             self.fw_T_dev, self.fw_prev = self._split_guarded(
-                lambda: self.engine.forward(self._pulses(pulses), self.init, store=True), 'forward')
+                lambda: self.engine.forward(self._terms(self._pulses(pulses)), self.init, store=True), 'forward')
         else:
-            self.fw_T_dev = self._split_guarded(lambda: self.engine.forward(self._pulses(pulses), self.init), 'forward')
+            self.fw_T_dev = self._split_guarded(
+                lambda: self.engine.forward(self._terms(self._pulses(pulses)), self.init), 'forward')
         fw_states_T = self._final_states(self.fw_T_dev)
         if store:
             forward_states = _DeviceTrajectories(self.fw_prev, self.likes, self.k0, final=fw_states_T._array,
@@ -839,9 +880,10 @@ class _HipBackend:
         if second_order:
             self._set_second_order(sigma)
         u_opt = self._set_parametrization(par) if par is not None else None
+        terms = self._set_nonlinear(guess) if self.nl is not None else guess
         chi_loc, norms_loc, li_J = self._boundary_costates(chi_T, chi_norms, chi_coef, chi_li)
         self.last_chi = (chi_loc, norms_loc)
-        self._backward(chi_loc, norms_loc, guess, constraint)
+        self._backward(chi_loc, norms_loc, terms, constraint)
         opt, psi_T, g_a = self._update((self.chi_store, norms_loc, self.init, guess, shapes, lambdas))
         self.fw_T_dev = psi_T
         self.engine.check()
@@ -1031,11 +1073,18 @@ def _check_arguments(objectives, pulse_options, propagator, mu, overlap, sigma, 
     if params is not None and process_group is not None:
         raise ValueError("pulse parametrizations run on one GPU: process_group= (sharding) is not supported with "
                          "'parametrization' in pulse_options")
+    nonlinear = has_control_function(objectives)
+    if nonlinear and params is not None:
+        raise ValueError("a ControlFunction (non-linear control) together with 'parametrization' in pulse_options is "
+                         "not supported")
+    if nonlinear and process_group is not None:
+        raise ValueError("non-linear controls (ControlFunction) run on one GPU: process_group= (sharding) is not "
+                         "supported with them")
     if process_group is not None and not device_path:
         raise ValueError("process_group requires the device path (propagator=krotov_amd.propagators.expm)")
     if device_path and any(len(obj.c_ops) > 0 for obj in objectives):
         # (a control inside c_ops raises here)
-        if (lindblad_layout_of(objectives, propagator, None, second_order, params is not None).matrix
+        if (lindblad_layout_of(objectives, propagator, None, second_order, params is not None, nonlinear).matrix
                 and process_group is not None):
             raise ValueError("objectives in Lindblad form run on one GPU: process_group= (sharding) is not supported "
                              "for the matrix-form engine")
@@ -1106,6 +1155,11 @@ def optimize_pulses(
       u and the control stays inside the range of f (bounded controls).  ``Result``, hooks and dumps hold eps;
       ``g_a_integrals`` is the running cost in u.  The built-in kinds run inside the device's update sweep, a subclass
       of your own through the host loop; not with ``process_group``.
+    * non-linear controls (extension): ``[H2, krotov_amd.Power(eps, 2)]`` in ``H`` is a term eps(t)^2 H2 of the SAME
+      control as ``[H1, eps]`` -- one pulse, one entry of ``pulse_options`` (keyed by ``eps``), one row of ``Result``
+      (:mod:`krotov_amd.nonlinear`).  dH/d eps is evaluated for the guess pulses inside the update; integer powers
+      1..4 run inside the device's update sweep (``kh_set_nonlinear``), any other ``ControlFunction`` through the host
+      loop.  Not with ``process_group`` or ``'parametrization'``; objectives with ``c_ops`` run as Liouvillians.
     * ``state_dependent_constraint`` (extension): a :class:`~krotov_amd.constraints.StateDependentConstraint`, a running
       cost g_b(phi(t)) -- the backward sweep then carries its source term (:mod:`krotov_amd.constraints`), on the device
       (``kh_apply_store`` + ``kh_backward_store_source``) or, with a propagator of your own, in the host loop.  The
@@ -1170,6 +1224,15 @@ def optimize_pulses(
         logger.info("pulse parametrization: a user-defined Parametrization (kind None) is evaluated on the host; "
                     "running the host loop around single-step propagations on the GPU")
         device_path = False
+    plan = term_plan(objectives, pulses_mapping, len(guess_pulses))  # (None: no ControlFunction in any H)
+    if device_path and plan is False:
+        logger.info("non-linear controls: a user-defined ControlFunction (power None) is evaluated on the host; "
+                    "running the host loop around single-step propagations on the GPU")
+        device_path = False
+    if device_path and plan is not None and plan.J > _KH_MAX_CONTROLS:
+        logger.warning("%d terms: the device sweeps take at most %d; running the host loop around single-step "
+                       "propagations on the GPU", plan.J, _KH_MAX_CONTROLS)
+        device_path = False
     if device_path and len(guess_pulses) > _KH_MAX_CONTROLS and process_group is None:
         # the sweep kernels are compiled for at most 32 controls (KH_GEN_MAX_L: the generic kernels; the register-resident
         # families take 8); the reference takes any number (optimize.py:33-55, conversions.py:140-254).  More than that
@@ -1183,7 +1246,8 @@ def optimize_pulses(
                               second_order=second_order, parametrized=par is not None,
                               replica_form=default_norm and _one_gate_replica_form(
                                   objectives, propagator, len(guess_pulses), chi_constructor, process_group,
-                                  par is not None or constraint is not None or skip_initial_forward_propagation))
+                                  par is not None or constraint is not None or skip_initial_forward_propagation
+                                  or plan is not None))
     else:
         backend = _PluginBackend(
             objectives, adjoint_objectives, pulses_mapping, tlist, propagators, storage, parallel_map, mu, overlap

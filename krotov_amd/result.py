@@ -20,6 +20,8 @@ import time
 
 import numpy as np
 
+from .nonlinear import ControlFunction, has_control_function
+
 __all__ = ['Result', 'ControlPlaceholder']
 
 _FIELDS = (
@@ -95,7 +97,9 @@ class Result:
             new = copy.copy(obj)  # nested lists copied, operators shared
             for i_control, control in enumerate(controls):
                 for i in self.controls_mapping[i_obj][0][i_control]:
-                    new.H[i][1] = control
+                    # (a non-linear term keeps its function: the same ControlFunction of the new control)
+                    old = new.H[i][1]
+                    new.H[i][1] = old.with_control(control) if isinstance(old, ControlFunction) else control
                 for i_c, _ in enumerate(new.c_ops):
                     for i in self.controls_mapping[i_obj][i_c + 1][i_control]:
                         new.c_ops[i_c][i][1] = control
@@ -124,6 +128,9 @@ class Result:
         unpickle from other threads at that moment.  Values of ``info_vals``
         that are instances of your own classes are pickled as they are.)"""
         if reference:
+            if has_control_function(self.objectives):
+                raise ValueError("Result.dump(reference=True): the reference cannot express non-linear controls "
+                                 "(a ControlFunction in an objective)")
             return _dump_reference(self, filename)
         clone = copy.copy(self)
         clone.objectives = []
@@ -135,6 +142,9 @@ class Result:
                     for term in lst:
                         if isinstance(term, list) and callable(term[1]):
                             term[1] = ControlPlaceholder(ids.setdefault(id(term[1]), len(ids)))
+                        elif isinstance(term, list) and isinstance(term[1], ControlFunction) and callable(term[1].control):
+                            inner = term[1].control
+                            term[1] = term[1].with_control(ControlPlaceholder(ids.setdefault(id(inner), len(ids))))
             clone.objectives.append(new)
         with open(filename, 'wb') as fh:
             pickle.dump(clone, fh)
