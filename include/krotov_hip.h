@@ -560,6 +560,34 @@ int kh_chi_local_invariants(kh_engine *engine, const kh_cdouble *psi_T_dev, cons
                             int32_t invariants_per_gate, double unitarity_weight, double scale,
                             kh_cdouble *chi_T_dev, double *chi_norms_dev, double *J_dev, void *stream);
 
+/* The exact gradient of the time-discretised final-time functional for the pulse values (what a quasi-Newton method
+ * such as L-BFGS-B takes over with near convergence; Krotov's own update sum is only its first order in dt):
+ *   A_kn = H0_k + sum_l eps_l[n] H_lk,   phi_k(t_{n+1}) = exp(f A_kn dt_n) phi_k(t_n),   f = -i (Hilbert) or 1 (Liouville)
+ *   dJ_T/d eps_l[n] = -2 sum_k ||chi_k|| Re < chi^_k(t_{n+1}) | L_exp(f dt_n A_kn)[ f dt_n H_lk ] | phi_k(t_n) >
+ * with chi_k(T) = -dJ_T/d<phi_k(T)| propagated backward under the SAME pulses and L_exp(X)[E] the Frechet derivative of
+ * the matrix exponential (the top-right block of exp([[X, E], [0, X]])), by a Taylor series of the block matrix one
+ * degree above the sweeps' table at theta_max = 1 (krotov_amd/csrc/kh_grad.h).  The sum over k runs in objective order.
+ *   fw_store_dev      [K][nt][N]   what kh_forward_store stored under `pulses_dev`
+ *   chi_store_dev     [K][nt][N]   what kh_backward_store stored under the same pulses (normalised co-states)
+ *   chi_norms_dev     [K]          ||chi_k(T)|| (kh_chi_boundary), or NULL: all 1
+ *   pulses_dev        [L][nt-1]
+ *   grad_dev          [L][nt-1]    OUT
+ *   per_objective_dev [K][L][nt-1] OUT the terms of the sum over k, or NULL: a workspace of the engine (allocated by the
+ *                                  first such call)
+ * The inputs are only read; of the outputs exactly the documented extents are written, every element once.  A control
+ * absent from an objective (NULL operator) contributes exact zeros.  Operators are neither assumed Hermitian nor
+ * classified.  No atomics: results are bitwise repeatable and do not depend on the launch's grid.
+ * Any dense uniform engine of kh_engine_create with 1 <= L <= 4 and N <= 96, whatever its kernel family.  Decided before
+ * any HIP call: KH_ERR_INVALID for a NULL engine, store, pulses or grad and for L = 0; KH_ERR_UNSUPPORTED for N > 96,
+ * L > 4 and for engines of kh_engine_create_csr, _mixed, _lindblad, _replicas and sharded ones (kh_p2p_*).
+ * kh_pulse_gradient_limits answers the limits for a problem description alone (host only, no GPU needed): KH_OK, or the
+ * code kh_pulse_gradient would return for an engine of that K, N, L, nt, with the same kh_last_error text. */
+int kh_pulse_gradient(kh_engine *engine, const kh_cdouble *fw_store_dev /* [K][nt][N] */,
+                      const kh_cdouble *chi_store_dev /* [K][nt][N] */, const double *chi_norms_dev /* [K] or NULL: 1 */,
+                      const double *pulses_dev /* [L][nt-1] */, double *grad_dev /* OUT [L][nt-1] */,
+                      double *per_objective_dev /* OUT [K][L][nt-1], or NULL: engine workspace */, void *stream);
+int kh_pulse_gradient_limits(const kh_problem *problem);
+
 /* After synchronising the stream: returns KH_ERR_TIMEOUT if an in-kernel
  * exchange gave up since the last call (outputs are then invalid), else 0. */
 int kh_check(kh_engine *engine);

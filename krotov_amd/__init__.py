@@ -25,6 +25,7 @@ from . import (
 from .objectives import Objective, ensemble_objectives, gate_objectives, propagate_objectives
 from .batch import optimize_pulses_batch
 from .constraints import QuadraticStateConstraint, StateDependentConstraint
+from .gradient import PulseGradient
 from .nonlinear import ControlFunction, Power
 from .optimize import optimize_pulses
 from .parametrization import (
@@ -44,6 +45,7 @@ __all__ = [
     'Objective',
     'Parametrization',
     'Power',
+    'PulseGradient',
     'QuadraticStateConstraint',
     'Result',
     'SquareParametrization',

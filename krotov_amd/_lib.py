@@ -116,6 +116,8 @@ SYMBOLS = {
     'kh_chi_boundary': (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
     'kh_chi_local_invariants': (ctypes.c_int, [_P, _P, _P, ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_int32,
                                                ctypes.c_double, ctypes.c_double, _P, _P, _P, _P]),
+    'kh_pulse_gradient': (ctypes.c_int, [_P] * 8),
+    'kh_pulse_gradient_limits': (ctypes.c_int, [ctypes.POINTER(kh_problem)]),
     'kh_check': (ctypes.c_int, [_P]),
     'kh_last_stats': (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double)]),
     'kh_debug_occupy': (ctypes.c_int, [_P, ctypes.c_int32, ctypes.c_double, _P]),

@@ -43,6 +43,7 @@
 #include "kh_lind.h"
 #include "kh_expect.h"
 #include "kh_chi_li.h"
+#include "kh_grad.h"
 // the parallel build (krotov_amd/build.py, -DKH_TU=KH_TU_MAIN): the sweep kernels are instantiated in the family units
 // (kh_tu.hip), here they are `extern template`; compiled by itself this file is the whole library in one unit
 #include "kh_instances.inc"
@@ -86,6 +87,7 @@ struct KhSwitches {
     double ell_cap;
     int ell_split, ell_groups;  // KH_ELL_SPLIT (0: 'auto'), KH_ELL_GROUPS (0: no cap)
     int stream_G, coop_cols, ens, ens_min_k, ens_ncg;
+    int grad_grid;  // KH_GRAD_GRID (0: one workgroup column per objective)
     bool coop_launch, q2_single, tile_single, coop_single, poll_delay_set, timeout_set;
     int poll_delay, adj_poll_delay, coop_poll_delay;  // (s_sleep units of 64 cycles)
     long long timeout_ticks;                          // (100 MHz ticks)
@@ -121,6 +123,7 @@ static KhSwitches read_switches() {
     s.ens = num("KH_ENS", -1);                 // 0: no ensemble kernel; 1: for any K (testing)
     s.ens_min_k = num("KH_ENS_MINK", 257);     // smallest K that takes it
     s.ens_ncg = num("KH_ENS_NCG", 0);          // its column groups, 1 | 2 | 4 | 8 (testing)
+    s.grad_grid = num("KH_GRAD_GRID", 0);      // kh_pulse_gradient: objectives in turns on this many workgroup columns (testing)
     s.ens2 = !off("KH_ENS2");                  // =0: no A^2-chain ensemble kernel (A/B)
     s.gen_adj = !off("KH_GEN_ADJ");            // =0: the generic kernels' update sums stay on the forward side
     s.coop_launch = !off("KH_COOP_LAUNCH");    // =0: plain launches instead of cooperative ones (A/B timing)
@@ -322,6 +325,7 @@ struct kh_engine {
     std::set<const void *> lds_raised;  // kernels whose dynamic-LDS limit was raised on this engine's device
     const cplx **d_expect_tab = nullptr;  // [K * n_e] kh_expect: the last call's operator table (grown on demand)
     size_t expect_tab_entries = 0;
+    double *d_grad_ws = nullptr;  // [K][L][nt-1] kh_pulse_gradient without a caller's per-objective array (first such call)
 };
 
 // Kernels with more than 64 KiB of dynamic LDS need the limit raised once per device: remembered per
@@ -594,6 +598,7 @@ extern "C" void kh_engine_destroy(kh_engine *e) {
     (void)hipFree(e->d_gen_adj);
     (void)hipFree(e->d_coop_adj);
     (void)hipFree((void *)e->d_expect_tab);
+    (void)hipFree((void *)e->d_grad_ws);
     for (void *ptr : e->p2p_opened) (void)hipIpcCloseMemHandle(ptr);
     (void)hipFree(e->p2p_window);
     (void)hipFree((void *)e->d_p2p_peers);
@@ -3392,6 +3397,77 @@ extern "C" int kh_chi_local_invariants(kh_engine *e, const kh_cdouble *psi_T_dev
         launch_plain<kh_chi_li_kernel<KH_LI_MODE_PE>>(grid, block, 0, (hipStream_t)stream, a);
     else
         launch_plain<kh_chi_li_kernel<KH_LI_MODE_LI>>(grid, block, 0, (hipStream_t)stream, a);
+    KH_HIP(hipGetLastError());
+    return KH_OK;
+}
+
+// the limits of kh_pulse_gradient that a problem's sizes decide
+static int grad_limits(int N, int L, int nt) {
+    if (L < 1) return kh_fail(KH_ERR_INVALID, "L = %d: no control to differentiate for", L);
+    if (nt < 2 || N < 1) return kh_fail(KH_ERR_INVALID, "nt = %d, N = %d: at least one interval and one dimension", nt, N);
+    if (N > KH_GRAD_NMAX) return kh_fail(KH_ERR_UNSUPPORTED, "N = %d: the pulse gradient serves N <= %d", N, KH_GRAD_NMAX);
+    if (L > KH_GRAD_MAX_L)
+        return kh_fail(KH_ERR_UNSUPPORTED, "L = %d: the pulse gradient serves L <= %d controls (terms)", L, KH_GRAD_MAX_L);
+    if (((long long)nt - 1 + KH_GRAD_CHUNK - 1) / KH_GRAD_CHUNK > 65535)
+        return kh_fail(KH_ERR_UNSUPPORTED, "nt = %d: more than 65535 chunks of %d intervals", nt, KH_GRAD_CHUNK);
+    return KH_OK;
+}
+
+extern "C" int kh_pulse_gradient_limits(const kh_problem *pr) {
+    if (pr == nullptr) return kh_fail(KH_ERR_INVALID, "null argument");
+    return grad_limits(pr->N, pr->L, pr->nt);
+}
+
+// Exact gradient of J_T for the pulse values (kh_grad.h): one slot per (objective, control, interval), then the sum over
+// the objectives in their order.
+extern "C" int kh_pulse_gradient(kh_engine *e, const kh_cdouble *fw_store_dev, const kh_cdouble *chi_store_dev,
+                                 const double *chi_norms_dev, const double *pulses_dev, double *grad_dev,
+                                 double *per_objective_dev, void *stream) {
+    if (e == nullptr || fw_store_dev == nullptr || chi_store_dev == nullptr || pulses_dev == nullptr || grad_dev == nullptr)
+        return kh_fail(KH_ERR_INVALID, "null argument");
+    if (e->d_csr_fw != nullptr || e->mixed || e->lind || e->replicas > 0 || e->p2p_world > 1)
+        return kh_fail(KH_ERR_UNSUPPORTED, "the pulse gradient serves dense uniform engines on one GPU: not %s engines",
+                       e->d_csr_fw != nullptr ? "sparse (CSR)" : e->mixed ? "mixed" : e->lind ? "Lindblad-form"
+                                                                : e->replicas > 0 ? "replica" : "sharded");
+    KH_TRY(grad_limits(e->N, e->L, e->nt));
+    const long long nI = (long long)e->nt - 1;
+    const long long chunks = (nI + KH_GRAD_CHUNK - 1) / KH_GRAD_CHUNK;
+    hipStream_t st = (hipStream_t)stream;
+    const long long count = (long long)e->L * nI;
+    if (per_objective_dev == nullptr) {
+        if (e->d_grad_ws == nullptr) {
+            void *mem = nullptr;
+            if (hipMalloc(&mem, sizeof(double) * (size_t)e->K * (size_t)count) != hipSuccess) {
+                (void)hipGetLastError();
+                return kh_fail(KH_ERR_NOMEM, "no device memory for the per-objective gradients (%d x %lld doubles)", e->K, count);
+            }
+            e->d_grad_ws = (double *)mem;
+        }
+        per_objective_dev = e->d_grad_ws;
+    }
+    KhGradArgs a;
+    a.ops = e->d_ops_fw, a.norms = e->d_norms, a.dt = e->d_dt, a.deg_theta = e->d_deg_theta;
+    a.fw = (const cplx *)fw_store_dev, a.chi = (const cplx *)chi_store_dev, a.chi_norms = chi_norms_dev;
+    a.pulses = pulses_dev, a.per_obj = per_objective_dev;
+    a.K = e->K, a.N = e->N, a.nt = e->nt, a.is_super = e->is_super;
+    const int gx = e->sw.grad_grid > 0 && e->sw.grad_grid < e->K ? e->sw.grad_grid : e->K;
+    const dim3 grid((unsigned)gx, (unsigned)chunks), block(KH_GRAD_THREADS);
+    const size_t lds = kh_grad_lds_bytes(e->N, e->L);
+    // (row blocks of 16 per wave: one up to N = 64, two beyond)
+    auto launch = [&](auto l, auto ng) {
+        return launch_plain_lds<kh_grad_items<decltype(l)::value, decltype(ng)::value>>(e, grid, block, lds, st, a);
+    };
+    auto by_rows = [&](auto l) {
+        return e->N <= 64 ? launch(l, std::integral_constant<int, 1>{}) : launch(l, std::integral_constant<int, 2>{});
+    };
+    switch (e->L) {
+        case 1: KH_TRY(by_rows(std::integral_constant<int, 1>{})); break;
+        case 2: KH_TRY(by_rows(std::integral_constant<int, 2>{})); break;
+        case 3: KH_TRY(by_rows(std::integral_constant<int, 3>{})); break;
+        default: KH_TRY(by_rows(std::integral_constant<int, 4>{})); break;
+    }
+    launch_plain<kh_grad_reduce>(dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, (const double *)per_objective_dev, grad_dev,
+                                 e->K, count);
     KH_HIP(hipGetLastError());
     return KH_OK;
 }

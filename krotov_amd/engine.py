@@ -964,6 +964,29 @@ class HipKrotovEngine:
             float(scale), chi.data_ptr(), norms.data_ptr(), J.data_ptr(), self._stream()))
         return chi, norms, J
 
+    def pulse_gradient(self, fw_store, chi_store, chi_norms, pulses, out=None, per_objective=None):
+        """The exact gradient of the time-discretised J_T for the pulse values (``kh_pulse_gradient``,
+        krotov_amd/csrc/kh_grad.h): ``fw_store`` and ``chi_store`` are the ``(K, nt, N)`` stores of :meth:`forward`
+        (``store=True``) and :meth:`backward` under the same ``pulses`` (L, nt-1), ``chi_norms`` the ``(K,)`` norms
+        taken out of the boundary co-states (``None``: 1).  Returns the ``(L, nt-1)`` float64 gradient; ``out`` /
+        ``per_objective``: buffers for it and for the ``(K, L, nt-1)`` terms of the sum over the objectives (``None``:
+        a workspace of the library).  Dense uniform engines with 1 <= L <= 4 and N <= 96; ``KrotovHipError``
+        (``KH_ERR_UNSUPPORTED``) beyond."""
+        shape = (self.K, self.nt, self.N)
+        for name, t in (('fw_store', fw_store), ('chi_store', chi_store)):
+            if (not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != torch.complex128
+                    or not t.is_contiguous() or t.device != self.device):
+                raise ValueError("%s must be a contiguous (K, nt, N) = %s complex128 tensor on %s" % (name, shape, self.device))
+        pulses = self._f(pulses, (self.L, self.nt - 1))
+        norms = None if chi_norms is None else self._f(chi_norms, (self.K,))
+        out = self._out(out, (self.L, self.nt - 1), torch.float64)
+        if per_objective is not None:
+            per_objective = self._out(per_objective, (self.K, self.L, self.nt - 1), torch.float64)
+        _lib.check(self._lib.kh_pulse_gradient(
+            self._handle, fw_store.data_ptr(), chi_store.data_ptr(), None if norms is None else norms.data_ptr(),
+            pulses.data_ptr(), out.data_ptr(), None if per_objective is None else per_objective.data_ptr(), self._stream()))
+        return out
+
     def check(self):
         """Synchronise and raise if an in-kernel exchange timed out."""
         torch.cuda.synchronize(self.device)
