@@ -217,6 +217,49 @@ struct KhPlan {
     }
     // the register-tile families, whose update sweep has a form on fewer workgroups (the streaming kernel)
     bool tile_family() const { return (kind == KIND_TILE_Q2 && !mini) || kind == KIND_TILE_RPT1 || kind == KIND_TILE_RPT2; }
+    // ... whose single launch can run the tile kernel's parametrized / non-linear form (q2 kind, mini and quad included:
+    // the kernel they already run stepwise): one resident workgroup per objective, more than one objective
+    bool tile_form(int K) const {
+        const bool tile_kind = kind == KIND_TILE_Q2 || kind == KIND_TILE_RPT1 || kind == KIND_TILE_RPT2;
+        return tile_kind && !ens && !stream && !stepwise_only && grid_update == K && K > 1;
+    }
+};
+
+// The variants of the update sweep an engine is switched to between sweeps.  The form of the pulse update: linear controls,
+// pulse parametrizations eps_l = f_l(u_l) (kh_set_parametrization) or non-linear controls eps_c^p H_j (kh_set_nonlinear)
+enum { FORM_LINEAR = 0, FORM_PAR = 1, FORM_NL = 2 };
+struct KhUpdateForm {
+    int tag = FORM_LINEAR;
+    // FORM_PAR: the caller's device arrays; the engine's own copies of the host arrays kind [L] and a, b [2][L]
+    const double *u_guess = nullptr, *dfdu = nullptr;
+    double *u_opt = nullptr;
+    int *d_kind = nullptr;
+    double *d_ab = nullptr;
+    std::vector<int> kind_host;  // what d_kind / d_ab hold
+    std::vector<double> ab_host;
+    // FORM_NL: the L slots are J terms of C controls; the caller's device array; the engine's own table [2][L]: term ->
+    // control, term -> power
+    const double *dcde = nullptr;
+    int C = 0;
+    int *d_tab = nullptr;
+    std::vector<int> tab_host;  // what d_tab holds
+    bool reduced = false;  // reduced_G was set while a form was (kh_set_update_workgroups): dropped with the form
+    bool set() const { return tag != FORM_LINEAR; }
+};
+// what the refusals call a form: kh_set_parametrization's and kh_set_nonlinear's own (refuse_form), and those of the entry
+// points that take no engine with a form set
+static const struct KhFormWords {
+    const char *noun, *plural, *no_rows, *is_set, *engine;
+} kh_form_words[] = {
+    {},
+    {"pulse parametrization", "pulse parametrizations", "no controls to parametrize", "a pulse parametrization is set (kh_set_parametrization)", "a parametrized engine (kh_set_parametrization)"},
+    {"non-linear controls", "non-linear controls", "no terms", "non-linear controls are set (kh_set_nonlinear)", "an engine with non-linear controls (kh_set_nonlinear)"},
+};
+// second-order update (kh_set_second_order, kh_set_second_order_replicas); all NULL = first order
+struct KhSecondOrder {
+    const cplx *fw_prev = nullptr;
+    cplx *fw_store = nullptr;
+    const double *sigma = nullptr;
 };
 
 struct kh_engine {
@@ -293,23 +336,9 @@ struct kh_engine {
     bool gen_adj_ready = false;       // d_gen_adj holds the store of the sweep in progress (stepwise launches reuse it)
     double adj_sign = 0.0;            // KhFacts::adj_sign (0 with KH_NO_ADJ)
     const double *guess_dev = nullptr;  // remembered by kh_update_begin
-    // second-order update (kh_set_second_order); all NULL = first order
-    const cplx *so_fw_prev = nullptr;
-    cplx *so_fw_store = nullptr;
-    const double *so_sigma = nullptr;
-    // pulse parametrizations (kh_set_parametrization); par_dfdu NULL = none
-    const double *par_u_guess = nullptr, *par_dfdu = nullptr;
-    double *par_u_opt = nullptr;
-    int *d_par_kind = nullptr;   // [L] the engine's own copies of the host arrays
-    double *d_par_ab = nullptr;  // [2][L] a, b
-    std::vector<int> par_kind_host;   // what d_par_kind / d_par_ab hold
-    std::vector<double> par_ab_host;
-    bool reduced_par = false;    // reduced_G was set while parametrized or non-linear (kh_set_update_workgroups)
-    // non-linear controls (kh_set_nonlinear); nl_dcde NULL = none.  The L slots are then J terms of nl_C controls
-    const double *nl_dcde = nullptr;
-    int nl_C = 0;
-    int *d_nl_tab = nullptr;          // [2][L] the engine's own copy: term -> control, term -> power
-    std::vector<int> nl_tab_host;     // what d_nl_tab holds
+    KhSecondOrder so;
+    bool second_order() const { return so.sigma != nullptr; }
+    KhUpdateForm form;
     // cross-GPU exchange (kh_p2p_*): objectives sharded over `p2p_world` ranks
     int p2p_world = 1, p2p_rank = 0;
     kh_u64 *p2p_window = nullptr;            // this rank's window (fine-grained device memory)
@@ -567,6 +596,18 @@ static void ensure_gen_scratch(kh_engine *e, int wgs) {
         return;
     }
     e->gen_scratch_wgs = wgs;
+}
+
+// What a generic kernel is launched with: its grid *grid -- the plain sweeps' workgroups loop over the objectives, no more
+// of them than the device runs at once (each may own a scratch generator); the update sweep's are the plan's -- and the
+// sweep's arguments with the scratch generators of that many workgroups
+static KhSweepArgs gen_sweep_args(kh_engine *e, const KhSweepArgs &p, bool update, int *grid) {
+    *grid = update ? e->plan.grid_update : (e->K < 2 * e->num_cus ? e->K : 2 * e->num_cus);
+    ensure_gen_scratch(e, *grid);
+    KhSweepArgs pg = p;
+    pg.gen_scratch = e->d_gen_scratch;
+    pg.gen_scratch_wgs = e->gen_scratch_wgs;
+    return pg;
 }
 
 // The generic kernels' adjoint-side store [L][K][nt][N]: allocated at the first update sweep that can use it, at most
@@ -1891,7 +1932,7 @@ extern "C" int kh_replica_occupancy(kh_engine *e, int32_t *workgroups_per_cu) {
     if (e == nullptr || workgroups_per_cu == nullptr) return kh_fail(KH_ERR_INVALID, "null argument");
     if (e->replicas < 1) return kh_fail(KH_ERR_UNSUPPORTED, "not a replica engine");
     const void *fn = nullptr;  // (the instantiation the next update sweep launches: kh_set_second_order_replicas)
-    if (e->so_sigma != nullptr)
+    if (e->second_order())
         fn = e->L == 1   ? (const void *)kh_rep_forward_update_so<1>
              : e->L == 2 ? (const void *)kh_rep_forward_update_so<2>
              : e->L == 3 ? (const void *)kh_rep_forward_update_so<3>
@@ -2243,13 +2284,8 @@ static int sweep_store(kh_engine *e, bool backward, const double *pulses, const 
             break;
         default: {
             if (!e->gen_fits) return kh_fail(KH_ERR_UNSUPPORTED, "N=%d: the generic kernels' vectors do not fit LDS", e->N);
-            // (the workgroups loop over the objectives: no more of them than the device runs at once -- each may own an
-            // N x N scratch generator)
-            const int grid = e->K < 2 * e->num_cus ? e->K : 2 * e->num_cus;
-            ensure_gen_scratch(e, grid);
-            KhSweepArgs pg = p;
-            pg.gen_scratch = e->d_gen_scratch;
-            pg.gen_scratch_wgs = e->gen_scratch_wgs;
+            int grid = 0;
+            const KhSweepArgs pg = gen_sweep_args(e, p, false, &grid);
             const size_t lds = kh_gen_lds_bytes(e->N, e->d_csr_fw == nullptr);
             if (e->mixed)
                 rc = launch_plain_lds<kh_gen_sweep_store<true>>(e, dim3(grid), dim3(KH_GEN_THREADS), lds, st, pg,
@@ -2319,11 +2355,8 @@ extern "C" int kh_backward_store_source(kh_engine *e, const kh_cdouble *chi_T_de
             return launch_plain_lds<kh_tile_sweep_store_src<1, LT>>(e, dim3(e->K), dim3(512), lds, st, p, sa, pulses_dev, in, store);
         });
     } else {
-        const int grid = e->K < 2 * e->num_cus ? e->K : 2 * e->num_cus;  // (as the plain generic sweep: sweep_store)
-        ensure_gen_scratch(e, grid);
-        KhSweepArgs pg = p;
-        pg.gen_scratch = e->d_gen_scratch;
-        pg.gen_scratch_wgs = e->gen_scratch_wgs;
+        int grid = 0;
+        const KhSweepArgs pg = gen_sweep_args(e, p, false, &grid);
         rc = launch_plain_lds<kh_gen_sweep_store_src<false>>(e, dim3(grid), dim3(KH_GEN_THREADS), kh_gen_lds_bytes(e->N, e->d_csr_fw == nullptr),
                                                              st, pg, sa, pulses_dev, in, store);
     }
@@ -2352,15 +2385,25 @@ extern "C" int kh_apply_store(kh_engine *e, const kh_cdouble *const *ops_table_d
 
 // ---- the update sweep: one route per call (update_route), one small launcher per family
 
-enum KhRoute { ROUTE_ENS, ROUTE_ENS2, ROUTE_STREAM, ROUTE_QUAD, ROUTE_MINI, ROUTE_Q2, ROUTE_COOP, ROUTE_TILEN, ROUTE_ELL, ROUTE_TILE, ROUTE_TILEX, ROUTE_GENERIC, ROUTE_LIND };
+enum KhRoute { ROUTE_ENS, ROUTE_ENS2, ROUTE_STREAM, ROUTE_QUAD, ROUTE_MINI, ROUTE_Q2, ROUTE_COOP, ROUTE_TILEN, ROUTE_ELL, ROUTE_TILE, ROUTE_TILEX, ROUTE_GENERIC, ROUTE_LIND,
+               ROUTE_TILE_FORM, ROUTE_GENERIC_FORM };
 
-// Which launcher runs an update call.  whole: the single launch over all intervals; stepwise: one interval per launch
-// (host- or device-indexed: the same route); so: second order; reduced_G: kh_set_update_workgroups; world: ranks of the
-// in-kernel exchange; have_sq: the A^2 tables are staged; adj_store(): the adjoint-side store can be had (ensure_gen_adj,
-// asked only where a family would read it -- its allocation happens at the first such call).
+// Which launcher runs an update call of engine e (read only).  whole: the single launch over all intervals; stepwise: one
+// interval per launch (host- or device-indexed: the same route); so: second order; world: ranks of the in-kernel
+// exchange; adj_store(): the adjoint-side store can be had (ensure_gen_adj, asked only where a family would read it -- its
+// allocation happens at the first such call; never with a form set).
 template <class AdjStore>
-static KhRoute update_route(const KhPlan &p, int K, bool stepwise, bool whole, bool so, int reduced_G, int world,
-                            bool have_sq, AdjStore &&adj_store) {
+static KhRoute update_route(const kh_engine *e, bool stepwise, bool whole, bool so, int world, AdjStore &&adj_store) {
+    const KhPlan &p = e->plan;
+    const int K = e->K, reduced_G = e->reduced_G;
+    if (e->form.set()) {
+        // pulse parametrizations and non-linear controls: the whole sweep of a register-tile engine on the tile kernel's
+        // form for them while its K workgroups are all resident (launch_update: else the generic form after all);
+        // everything else -- other families, stepwise launches, reduced grids -- on the generic one
+        const bool own_grid = reduced_G == 0 && world == 1 && e->sw.tile_single;  // (the SINGLE exchange on the plan's grid)
+        const bool tile_operands = !e->mixed && e->d_csr_fw == nullptr && e->N <= KH_TILE_N && e->L >= 1 && e->L <= 4;
+        return whole && p.tile_form(K) && own_grid && tile_operands ? ROUTE_TILE_FORM : ROUTE_GENERIC_FORM;
+    }
     if (p.kind == KIND_LIND) return ROUTE_LIND;
     if (p.ens && whole) {
         // first order, four objectives per workgroup (512 < K <= 1024): the A^2 chain with the update sums on the adjoint
@@ -2368,7 +2411,7 @@ static KhRoute update_route(const KhPlan &p, int K, bool stepwise, bool whole, b
         // column-group counts run -- with one column group it measured 2 % slower, with 4 and 8 its operands do not fit)
         int G = 0;
         const int ncg = p.ens_cols(K, reduced_G, &G);
-        return !so && ncg == 2 && p.ens2 && have_sq && adj_store() ? ROUTE_ENS2 : ROUTE_ENS;
+        return !so && ncg == 2 && p.ens2 && e->d_sq_fw != nullptr && adj_store() ? ROUTE_ENS2 : ROUTE_ENS;
     }
     if (p.kind == KIND_ELL && p.ell_global && !stepwise) return ROUTE_ELL;  // (any grid: kh_ellg.h)
     if ((p.stream || (reduced_G > 0 && reduced_G < p.grid_update && world == 1)) && whole) return ROUTE_STREAM;
@@ -2529,6 +2572,16 @@ static int update_ell(kh_engine *e, const KhSweepArgs &p, const KhUpdateArgs &u,
     });
 }
 
+// The register-tile update kernels' first poll with several controls: L waves gather side by side (kh_tile64.h) and a failed
+// polling round costs L times the loads, so the stores get a longer head start -- measured best on config-5 shapes:
+// 24 / 28 / 32 x 64 cycles for L = 2 / 3 / 4 (update sweep 7.47 / - / 9.86 us per interval against 7.92 / - / 11.21 with 16);
+// KH_POLL_DELAY overrides
+template <int LT>
+static KhExchange tile_exchange(const kh_engine *e, KhExchange ex) {
+    if (LT >= 2 && !e->sw.poll_delay_set) ex.first_poll_delay = 24 + 4 * (LT - 2);
+    return ex;
+}
+
 template <int RPT, int LT>
 static int launch_tile_update(kh_engine *e, const KhSweepArgs &p, const KhUpdateArgs &u, const KhExchange &ex,
                               hipStream_t st) {
@@ -2538,11 +2591,7 @@ static int launch_tile_update(kh_engine *e, const KhSweepArgs &p, const KhUpdate
         constexpr bool SO = decltype(so)::value;
         if (!u.internal_exchange)  // one launch per interval (sharded sweep): nothing waits inside the kernel
             return launch_plain_lds<kh_tile_forward_update<RPT, LT, SO>>(e, g, b, lds, st, p, u, ex);
-        KhExchange exl = ex;
-        // several controls: L waves gather side by side (kh_tile64.h) and a failed polling round costs L times the loads,
-        // so the stores get a longer head start -- measured best on config-5 shapes: 24 / 28 / 32 x 64 cycles for L = 2 / 3 / 4
-        // (update sweep 7.47 / - / 9.86 us per interval against 7.92 / - / 11.21 with 16)
-        if (LT >= 2 && !e->sw.poll_delay_set) exl.first_poll_delay = 24 + 4 * (LT - 2);
+        const KhExchange exl = tile_exchange<LT>(e, ex);
         if (exl.world == 1 && exl.G > 1 && e->sw.tile_single)
             return launch_persistent_lds<kh_tile_forward_update<RPT, LT, SO, true>>(e, g, b, lds, st, p, u, exl);
         return launch_persistent_lds<kh_tile_forward_update<RPT, LT, SO>>(e, g, b, lds, st, p, u, exl);
@@ -2550,60 +2599,42 @@ static int launch_tile_update(kh_engine *e, const KhSweepArgs &p, const KhUpdate
 }
 
 static KhParArgs par_args(const kh_engine *e) {
-    return KhParArgs{e->par_dfdu, e->par_u_opt, e->d_par_kind, e->d_par_ab, e->d_par_ab + e->L};
-}
-
-// the register-tile kernel's parametrized form: one launch over the sweep, one GPU, K > 1 resident workgroups
-template <int RPT, int LT>
-static int launch_tile_update_par(kh_engine *e, const KhSweepArgs &p, const KhUpdateArgs &u, const KhExchange &ex,
-                                  hipStream_t st) {
-    constexpr size_t lds = KhTileLds<RPT, LT>::bytes(KhTileLds<RPT, LT>::UPDATE);
-    const dim3 g(e->K), b(512 / RPT);
-    KhExchange exl = ex;
-    if (LT >= 2 && !e->sw.poll_delay_set) exl.first_poll_delay = 24 + 4 * (LT - 2);  // (as launch_tile_update)
-    e->last_update_grid = e->K;
-    return with_bool(u.sigma != nullptr, [&](auto so) {
-        return launch_persistent_lds<kh_tile_forward_update_par<RPT, LT, decltype(so)::value>>(e, g, b, lds, st, p, u, exl, par_args(e));
-    });
+    return KhParArgs{e->form.dfdu, e->form.u_opt, e->form.d_kind, e->form.d_ab, e->form.d_ab + e->L};
 }
 
 static KhNlArgs nl_args(const kh_engine *e) {
-    return KhNlArgs{e->nl_dcde, e->d_nl_tab, e->d_nl_tab + e->L, e->nl_C};
+    return KhNlArgs{e->form.dcde, e->form.d_tab, e->form.d_tab + e->L, e->form.C};
 }
 
-// the register-tile kernel's non-linear form (kh_set_nonlinear): as launch_tile_update_par, with LT = terms
+// the register-tile kernel's form with pulse parametrizations or non-linear controls (LT: its terms): one launch over the
+// sweep, one GPU, K > 1 resident workgroups (update_route)
 template <int RPT, int LT>
-static int launch_tile_update_nl(kh_engine *e, const KhSweepArgs &p, const KhUpdateArgs &u, const KhExchange &ex,
-                                 hipStream_t st) {
+static int launch_tile_update_form(kh_engine *e, const KhSweepArgs &p, const KhUpdateArgs &u, const KhExchange &ex,
+                                   hipStream_t st) {
     constexpr size_t lds = KhTileLds<RPT, LT>::bytes(KhTileLds<RPT, LT>::UPDATE);
     const dim3 g(e->K), b(512 / RPT);
-    KhExchange exl = ex;
-    if (LT >= 2 && !e->sw.poll_delay_set) exl.first_poll_delay = 24 + 4 * (LT - 2);  // (as launch_tile_update)
+    const KhExchange exl = tile_exchange<LT>(e, ex);
     e->last_update_grid = e->K;
     return with_bool(u.sigma != nullptr, [&](auto so) {
-        return launch_persistent_lds<kh_tile_forward_update_nl<RPT, LT, decltype(so)::value>>(e, g, b, lds, st, p, u, exl, nl_args(e));
+        constexpr bool SO = decltype(so)::value;
+        if (e->form.tag == FORM_NL)
+            return launch_persistent_lds<kh_tile_forward_update_nl<RPT, LT, SO>>(e, g, b, lds, st, p, u, exl, nl_args(e));
+        return launch_persistent_lds<kh_tile_forward_update_par<RPT, LT, SO>>(e, g, b, lds, st, p, u, exl, par_args(e));
     });
 }
 
-// FORM_PAR: the kernels with pulse parametrizations (kh_set_parametrization) -- every update sweep of a parametrized engine
-// comes here, whatever its family: the single launch then runs on min(K, max_wgs) workgroups (or what
-// kh_set_update_workgroups allows), each taking its objectives in turns.  FORM_NL: the same for non-linear controls
-// (kh_set_nonlinear).
-enum { FORM_LINEAR = 0, FORM_PAR = 1, FORM_NL = 2 };
-template <int FORM>
-static int update_generic(kh_engine *e, const KhSweepArgs &p, const KhUpdateArgs &u, const KhExchange &ex_in, hipStream_t st) {
-    if (!e->gen_fits)
-        return kh_fail(KH_ERR_UNSUPPORTED, "N=%d: this form of the update sweep needs the generic kernels, whose vectors do not fit LDS", e->N);
+// The generic update kernel `Kernel` -- update_generic names it -- with the arguments `form_args` of its form behind the
+// shared ones.  With a form set every update sweep that is not the tile kernel's comes here, whatever the engine's family:
+// the single launch then runs on min(K, max_wgs) workgroups (or what kh_set_update_workgroups allows), each taking its
+// objectives in turns.
+template <auto Kernel, class... FormArgs>
+static int launch_gen_update(kh_engine *e, const KhSweepArgs &p, const KhUpdateArgs &u, const KhExchange &ex_in, hipStream_t st,
+                             const KhMixedArgs &mx, FormArgs... form_args) {
     const size_t lds = kh_gen_lds_bytes(e->N, e->d_csr_fw == nullptr);
-    const void *fn = FORM == FORM_PAR  ? (e->mixed ? (const void *)kh_gen_forward_update_par<true> : (const void *)kh_gen_forward_update_par<false>)
-                     : FORM == FORM_NL ? (e->mixed ? (const void *)kh_gen_forward_update_nl<true> : (const void *)kh_gen_forward_update_nl<false>)
-                                       : (e->mixed ? (const void *)kh_gen_forward_update<true> : (const void *)kh_gen_forward_update<false>);
-    int rc = ensure_dynamic_lds(e, fn, lds);
-    ensure_gen_scratch(e, e->plan.grid_update);
+    const int rc = ensure_dynamic_lds(e, (const void *)Kernel, lds);
+    int G = 0;
+    const KhSweepArgs pg = gen_sweep_args(e, p, true, &G);
     if (rc != KH_OK) return rc;
-    KhSweepArgs pg = p;
-    pg.gen_scratch = e->d_gen_scratch;
-    pg.gen_scratch_wgs = e->gen_scratch_wgs;
     // first order, dense operators: V_lk = H_lk^+ chi_k for the whole store in front of the sweep -- at the sweep's first
     // launch (the single launch, or kh_update_begin's); the launches of a stepwise sweep that follow reuse it
     KhUpdateArgs ug = u;
@@ -2617,8 +2648,7 @@ static int update_generic(kh_engine *e, const KhSweepArgs &p, const KhUpdateArgs
     }
     if (e->gen_adj_ready && u.sigma == nullptr) ug.adj_store = e->d_gen_adj;
     KhExchange ex = ex_in;
-    int G = e->plan.grid_update;
-    if (FORM != FORM_LINEAR && ug.internal_exchange) {
+    if (e->form.set() && ug.internal_exchange) {
         // (an engine of another family may hold more workgroups than the exchange of this kernel takes, or fewer
         // were asked for: the workgroups walk through the objectives)
         if (G > e->plan.max_wgs) G = e->plan.max_wgs;
@@ -2628,27 +2658,21 @@ static int update_generic(kh_engine *e, const KhSweepArgs &p, const KhUpdateArgs
         e->last_update_grid = G;
     }
     const dim3 g(G), b(KH_GEN_THREADS);
+    if (ug.internal_exchange) return launch_persistent<Kernel>(e, g, b, lds, st, pg, ug, ex, mx, form_args...);
+    launch_plain<Kernel>(g, b, lds, st, pg, ug, ex, mx, form_args...);
+    return KH_OK;
+}
+
+static int update_generic(kh_engine *e, const KhSweepArgs &p, const KhUpdateArgs &u, const KhExchange &ex, hipStream_t st) {
+    if (!e->gen_fits)
+        return kh_fail(KH_ERR_UNSUPPORTED, "N=%d: this form of the update sweep needs the generic kernels, whose vectors do not fit LDS", e->N);
     return with_bool(e->mixed, [&](auto mixed) {
         constexpr bool MIXED = decltype(mixed)::value;
         const KhMixedArgs mx = MIXED ? e->mixed_fw : KhMixedArgs{};
-        if constexpr (FORM == FORM_PAR) {
-            if (!ug.internal_exchange) {
-                launch_plain<kh_gen_forward_update_par<MIXED>>(g, b, lds, st, pg, ug, ex, mx, par_args(e));
-                return (int)KH_OK;
-            }
-            return launch_persistent<kh_gen_forward_update_par<MIXED>>(e, g, b, lds, st, pg, ug, ex, mx, par_args(e));
-        } else if constexpr (FORM == FORM_NL) {
-            if (!ug.internal_exchange) {
-                launch_plain<kh_gen_forward_update_nl<MIXED>>(g, b, lds, st, pg, ug, ex, mx, nl_args(e));
-                return (int)KH_OK;
-            }
-            return launch_persistent<kh_gen_forward_update_nl<MIXED>>(e, g, b, lds, st, pg, ug, ex, mx, nl_args(e));
-        } else {
-            if (!ug.internal_exchange) {
-                launch_plain<kh_gen_forward_update<MIXED>>(g, b, lds, st, pg, ug, ex, mx);
-                return (int)KH_OK;
-            }
-            return launch_persistent<kh_gen_forward_update<MIXED>>(e, g, b, lds, st, pg, ug, ex, mx);
+        switch (e->form.tag) {
+            case FORM_PAR: return launch_gen_update<kh_gen_forward_update_par<MIXED>>(e, p, u, ex, st, mx, par_args(e));
+            case FORM_NL: return launch_gen_update<kh_gen_forward_update_nl<MIXED>>(e, p, u, ex, st, mx, nl_args(e));
+            default: return launch_gen_update<kh_gen_forward_update<MIXED>>(e, p, u, ex, st, mx);
         }
     });
 }
@@ -2691,30 +2715,7 @@ static int launch_update(kh_engine *e, const KhUpdateArgs &u, hipStream_t st) {
     const bool whole = !stepwise && u.n_begin == 0 && u.n_end == e->nt - 1;
     e->last_update_grid = 0;
     int rc = KH_OK;
-    if (e->par_dfdu != nullptr || e->nl_dcde != nullptr) {
-        // pulse parametrizations (kh_set_parametrization) and non-linear controls (kh_set_nonlinear): the whole sweep of a register-tile engine (q2 kind, mini and
-        // quad included: the kernel they already run stepwise) on the tile kernel's form for them while its K workgroups
-        // are all resident; everything else -- other families, stepwise launches, reduced grids -- on the generic one
-        const KhPlan &pl = e->plan;
-        const bool tile_kind = pl.kind == KIND_TILE_Q2 || pl.kind == KIND_TILE_RPT1 || pl.kind == KIND_TILE_RPT2;
-        rc = KH_ERR_UNSUPPORTED;
-        if (whole && tile_kind && !pl.ens && !pl.stream && !pl.stepwise_only && pl.grid_update == e->K && e->K > 1 &&
-            e->reduced_G == 0 && ex.world == 1 && ex.G == e->K && e->sw.tile_single && !e->mixed && e->d_csr_fw == nullptr &&
-            e->N <= KH_TILE_N && e->L >= 1 && e->L <= 4) {
-            const bool nl = e->nl_dcde != nullptr;
-            rc = with_tile(pl.kind == KIND_TILE_RPT2, e->L, [&](auto rpt, auto lt) {
-                if (nl) return launch_tile_update_nl<decltype(rpt)::value, decltype(lt)::value>(e, p, u, ex, st);
-                return launch_tile_update_par<decltype(rpt)::value, decltype(lt)::value>(e, p, u, ex, st);
-            });
-            if (rc != KH_OK && rc != KH_ERR_UNSUPPORTED) return rc;  // (unsupported: the grid cannot be resident)
-        }
-        if (rc != KH_OK) rc = e->nl_dcde != nullptr ? update_generic<FORM_NL>(e, p, u, ex, st) : update_generic<FORM_PAR>(e, p, u, ex, st);
-        if (rc != KH_OK) return rc;
-        KH_HIP(hipGetLastError());
-        return KH_OK;
-    }
-    switch (update_route(e->plan, e->K, stepwise, whole, u.sigma != nullptr, e->reduced_G, ex.world, e->d_sq_fw != nullptr,
-                         [e] { return ensure_gen_adj(e); })) {
+    switch (update_route(e, stepwise, whole, u.sigma != nullptr, ex.world, [e] { return ensure_gen_adj(e); })) {
         case ROUTE_ENS: rc = update_ens(e, p, u, ex, st, false); break;
         case ROUTE_ENS2: rc = update_ens(e, p, u, ex, st, true); break;
         case ROUTE_STREAM: rc = update_stream(e, p, u, ex, st); break;
@@ -2734,8 +2735,15 @@ static int launch_update(kh_engine *e, const KhUpdateArgs &u, hipStream_t st) {
             });
             break;
         case ROUTE_TILEX: rc = update_tilex(e, p, u, ex, st); break;
-        case ROUTE_GENERIC: rc = update_generic<FORM_LINEAR>(e, p, u, ex, st); break;
         case ROUTE_LIND: rc = update_lind(e, p, u, ex, st); break;
+        case ROUTE_TILE_FORM:
+            rc = with_tile(e->plan.kind == KIND_TILE_RPT2, e->L, [&](auto rpt, auto lt) {
+                return launch_tile_update_form<decltype(rpt)::value, decltype(lt)::value>(e, p, u, ex, st);
+            });
+            if (rc != KH_ERR_UNSUPPORTED) break;  // (unsupported: the grid cannot be resident -- the generic form takes the sweep)
+            [[fallthrough]];
+        case ROUTE_GENERIC_FORM:  // (update_generic takes the form's kernel)
+        case ROUTE_GENERIC: rc = update_generic(e, p, u, ex, st); break;
     }
     if (rc != KH_OK) return rc;
     KH_HIP(hipGetLastError());
@@ -2759,15 +2767,15 @@ static KhUpdateArgs update_args(kh_engine *e, const kh_cdouble *chi_store, const
     u.wg_partial = e->d_wg_partial;
     u.D_in = nullptr;
     u.n_dev = nullptr;
-    u.fw_prev = e->so_fw_prev;
-    u.fw_store = e->so_fw_store;
-    u.sigma = e->so_sigma;
+    u.fw_prev = e->so.fw_prev;
+    u.fw_store = e->so.fw_store;
+    u.sigma = e->so.sigma;
     u.n_begin = 0;
     u.n_end = e->nt - 1;
     u.internal_exchange = 1;
     u.adj_sign = e->adj_sign;
     u.adj_store = nullptr;
-    if (e->par_dfdu != nullptr) u.guess = e->par_u_guess;  // (the sweep updates u; eps = f(u) goes to `opt`)
+    if (e->form.tag == FORM_PAR) u.guess = e->form.u_guess;  // (the sweep updates u; eps = f(u) goes to `opt`)
     return u;
 }
 
@@ -2860,7 +2868,7 @@ extern "C" int kh_set_update_workgroups(kh_engine *e, int32_t max_workgroups, in
     if (e->row_split > 1 && chosen != nullptr) *chosen = e->split_groups * e->row_split;
     if (max_workgroups == 0) {
         e->reduced_G = 0;
-        e->reduced_par = false;
+        e->form.reduced = false;
         return KH_OK;
     }
     if (e->replicas > 0) return kh_fail(KH_ERR_UNSUPPORTED, "replica engines (kh_engine_create_replicas) run one workgroup per replica: no form with fewer workgroups");
@@ -2869,11 +2877,11 @@ extern "C" int kh_set_update_workgroups(kh_engine *e, int32_t max_workgroups, in
     if (e->p2p_ready) return kh_fail(KH_ERR_UNSUPPORTED, "sharded sweeps keep their grid (all ranks must agree on the form)");
     const KhPlan &p = e->plan;
     int G = 0;
-    if (e->par_dfdu != nullptr || e->nl_dcde != nullptr) {
+    if (e->form.set()) {
         // a parametrized or non-linear engine (kh_set_parametrization, kh_set_nonlinear): the generic kernels take their objectives in turns on any grid
         G = p.grid_update < p.max_wgs ? p.grid_update : p.max_wgs;
         if (max_workgroups < G) G = max_workgroups;
-        e->reduced_par = true;  // (not a grid the engine's own family was asked about: dropped with the parametrization)
+        e->form.reduced = true;  // (not a grid the engine's own family was asked about: dropped with the form)
     } else if (p.ens) {
         const int widest = (e->K + 2 * KH_ENS_MAXCG - 1) / (2 * KH_ENS_MAXCG);
         if (max_workgroups < widest)
@@ -2933,8 +2941,7 @@ extern "C" int kh_set_row_split(kh_engine *e, int workgroups_per_objective) {
         e->row_split = 1;
         return KH_OK;
     }
-    if (e->par_dfdu != nullptr) return kh_fail(KH_ERR_UNSUPPORTED, "a parametrized engine (kh_set_parametrization) keeps one workgroup per objective");
-    if (e->nl_dcde != nullptr) return kh_fail(KH_ERR_UNSUPPORTED, "an engine with non-linear controls (kh_set_nonlinear) keeps one workgroup per objective");
+    if (e->form.set()) return kh_fail(KH_ERR_UNSUPPORTED, "%s keeps one workgroup per objective", kh_form_words[e->form.tag].engine);
     const int max_wgs = e->plan.max_wgs;  // (what the exchange takes: at most 256, at most one per CU)
     if (S > e->num_cus || S > max_wgs)
         return kh_fail(KH_ERR_UNSUPPORTED, "%d workgroups per objective: this device runs at most %d at once", S, e->num_cus < max_wgs ? e->num_cus : max_wgs);
@@ -2964,87 +2971,105 @@ extern "C" int kh_set_row_split(kh_engine *e, int workgroups_per_objective) {
     return KH_OK;
 }
 
-extern "C" int kh_set_second_order(kh_engine *e, const kh_cdouble *fw_prev_dev, kh_cdouble *fw_store_dev,
-                                   const double *sigma_dev) {
+// kh_set_second_order, and kh_set_second_order_replicas with one sigma row per replica ([B][nt-1]; kh_replica.h,
+// kh_rep_forward_update_so)
+static int set_second_order(kh_engine *e, const kh_cdouble *fw_prev_dev, kh_cdouble *fw_store_dev, const double *sigma_dev,
+                            bool replicas) {
     if (e == nullptr) return kh_fail(KH_ERR_INVALID, "null engine");
+    if (replicas && e->replicas < 1) return kh_fail(KH_ERR_UNSUPPORTED, "only replica engines (kh_engine_create_replicas) take one sigma row per replica; this one runs %s (kh_set_second_order)", kh_engine_kernel(e));
     const int given = (fw_prev_dev != nullptr) + (fw_store_dev != nullptr) + (sigma_dev != nullptr);
     if (given != 0 && given != 3)
         return kh_fail(KH_ERR_INVALID, "fw_prev, fw_store and sigma must be given together (or all NULL)");
-    if (e->lind && given != 0) return kh_fail(KH_ERR_UNSUPPORTED, "Lindblad-form engines (kh_engine_create_lindblad) run the first-order update only");
-    if (e->replicas > 0 && given != 0) return kh_fail(KH_ERR_UNSUPPORTED, "replica engines (kh_engine_create_replicas) run the first-order update only");
+    if (!replicas && e->lind && given != 0) return kh_fail(KH_ERR_UNSUPPORTED, "Lindblad-form engines (kh_engine_create_lindblad) run the first-order update only");
+    if (!replicas && e->replicas > 0 && given != 0) return kh_fail(KH_ERR_UNSUPPORTED, "replica engines (kh_engine_create_replicas) run the first-order update only");
     if (fw_prev_dev != nullptr && (const void *)fw_prev_dev == (const void *)fw_store_dev)
         return kh_fail(KH_ERR_INVALID, "fw_store must not alias fw_prev");
-    e->so_fw_prev = (const cplx *)fw_prev_dev;
-    e->so_fw_store = (cplx *)fw_store_dev;
-    e->so_sigma = sigma_dev;
+    e->so = KhSecondOrder{(const cplx *)fw_prev_dev, (cplx *)fw_store_dev, sigma_dev};
+    return KH_OK;
+}
+
+extern "C" int kh_set_second_order(kh_engine *e, const kh_cdouble *fw_prev_dev, kh_cdouble *fw_store_dev,
+                                   const double *sigma_dev) {
+    return set_second_order(e, fw_prev_dev, fw_store_dev, sigma_dev, false);
+}
+
+extern "C" int kh_set_second_order_replicas(kh_engine *e, const kh_cdouble *fw_prev_dev, kh_cdouble *fw_store_dev,
+                                            const double *sigma_dev) {
+    return set_second_order(e, fw_prev_dev, fw_store_dev, sigma_dev, true);
+}
+
+// What the two setters of a form refuse alike, in the words of the form asked for (kh_form_words)
+static int refuse_form(const kh_engine *e, int tag) {
+    const KhFormWords &w = kh_form_words[tag];
+    if (e->lind) return kh_fail(KH_ERR_UNSUPPORTED, "Lindblad-form engines (kh_engine_create_lindblad) take no %s: build the Liouvillian and use kh_engine_create", w.noun);
+    if (e->replicas > 0) return kh_fail(KH_ERR_UNSUPPORTED, "replica engines (kh_engine_create_replicas) take no %s", w.noun);
+    if (e->p2p_ready || e->p2p_window != nullptr) return kh_fail(KH_ERR_UNSUPPORTED, "sharded engines take no %s (one GPU)", w.noun);
+    if (e->row_split > 1) return kh_fail(KH_ERR_UNSUPPORTED, "a split engine (kh_set_row_split) takes no %s: set the row split to 1 first", w.noun);
+    if (!e->gen_fits) return kh_fail(KH_ERR_UNSUPPORTED, "N=%d: %s run on the generic kernels, whose vectors do not fit LDS", e->N, w.plural);
+    if (e->L < 1) return kh_fail(KH_ERR_INVALID, "%s", w.no_rows);
+    if (e->form.set() && e->form.tag != tag) return kh_fail(KH_ERR_INVALID, "%s: the two are not combined", kh_form_words[e->form.tag].is_set);
+    return KH_OK;
+}
+
+// a setter's "off": the form `tag` unset, and a reduced grid that was set while a form was on dropped with it
+static void clear_form(kh_engine *e, int tag) {
+    KhUpdateForm &f = e->form;
+    if (f.tag == tag) {
+        f.tag = FORM_LINEAR, f.C = 0;
+        f.u_guess = f.dfdu = f.dcde = nullptr;
+        f.u_opt = nullptr;
+    }
+    if (f.reduced) e->reduced_G = 0;
+    f.reduced = false;
+}
+
+// The engine's own copy of a setter's host table: allocated at the first use, uploaded when it changes (an optimisation
+// sets the same one before every sweep) -- a blocking copy behind a device-wide wait for an earlier sweep that may still
+// read it
+template <class T>
+static int upload_table(kh_engine *e, T **dev, std::vector<T> &mirror, const std::vector<T> &host) {
+    if (*dev == nullptr) KH_TRY(dev_alloc(e, dev, sizeof(T) * host.size()));
+    if (host == mirror) return KH_OK;
+    KH_HIP(hipDeviceSynchronize());
+    KH_HIP(hipMemcpy(*dev, host.data(), sizeof(T) * host.size(), hipMemcpyHostToDevice));
+    mirror = host;
     return KH_OK;
 }
 
 // Pulse parametrizations eps_l = f_l(u_l) (include/krotov_hip.h): the following update sweeps update u and propagate with
-// f(u) -- on the register-tile kernel's parametrized form or the generic kernels', by launch_update's rule
+// f(u) -- on the register-tile kernel's parametrized form or the generic kernels', by update_route's rule
 extern "C" int kh_set_parametrization(kh_engine *e, const int32_t *kind, const double *a, const double *b,
                                       const double *u_guess_dev, const double *dfdu_dev, double *u_opt_dev) {
     if (e == nullptr) return kh_fail(KH_ERR_INVALID, "null engine");
     if (kind == nullptr) {
-        e->par_u_guess = e->par_dfdu = nullptr;
-        e->par_u_opt = nullptr;
-        if (e->reduced_par) e->reduced_G = 0;  // (a reduced grid set while parametrized goes with it)
-        e->reduced_par = false;
+        clear_form(e, FORM_PAR);
         return KH_OK;
     }
-    if (e->lind) return kh_fail(KH_ERR_UNSUPPORTED, "Lindblad-form engines (kh_engine_create_lindblad) take no pulse parametrization: build the Liouvillian and use kh_engine_create");
-    if (e->replicas > 0) return kh_fail(KH_ERR_UNSUPPORTED, "replica engines (kh_engine_create_replicas) take no pulse parametrization");
-    if (e->p2p_ready || e->p2p_window != nullptr) return kh_fail(KH_ERR_UNSUPPORTED, "sharded engines take no pulse parametrization (one GPU)");
-    if (e->row_split > 1) return kh_fail(KH_ERR_UNSUPPORTED, "a split engine (kh_set_row_split) takes no pulse parametrization: set the row split to 1 first");
-    if (!e->gen_fits) return kh_fail(KH_ERR_UNSUPPORTED, "N=%d: pulse parametrizations run on the generic kernels, whose vectors do not fit LDS", e->N);
-    if (e->L < 1) return kh_fail(KH_ERR_INVALID, "no controls to parametrize");
-    if (e->nl_dcde != nullptr) return kh_fail(KH_ERR_INVALID, "non-linear controls are set (kh_set_nonlinear): the two are not combined");
+    KH_TRY(refuse_form(e, FORM_PAR));
     if (a == nullptr || b == nullptr || u_guess_dev == nullptr || dfdu_dev == nullptr || u_opt_dev == nullptr)
         return kh_fail(KH_ERR_INVALID, "null argument");
     if (u_opt_dev == u_guess_dev) return kh_fail(KH_ERR_INVALID, "u_opt_dev must not alias u_guess_dev");
     for (int l = 0; l < e->L; ++l)
         if (kind[l] < KH_PAR_NONE || kind[l] > KH_PAR_TANH) return kh_fail(KH_ERR_INVALID, "control %d: unknown parametrization kind %d", l, (int)kind[l]);
-    if (e->d_par_kind == nullptr) {
-        KH_TRY(dev_alloc(e, &e->d_par_kind, sizeof(int) * (size_t)e->L));
-        KH_TRY(dev_alloc(e, &e->d_par_ab, sizeof(double) * 2 * (size_t)e->L));
-    }
-    // the tables change rarely (an optimisation sets the same ones before every sweep): uploaded when they do -- blocking
-    // copies from the caller's host arrays, behind a device-wide wait for an earlier sweep that may still read them
-    std::vector<int> kinds(kind, kind + e->L);
     std::vector<double> ab(a, a + e->L);
     ab.insert(ab.end(), b, b + e->L);
-    if (kinds != e->par_kind_host || ab != e->par_ab_host) {
-        KH_HIP(hipDeviceSynchronize());
-        KH_HIP(hipMemcpy(e->d_par_kind, kinds.data(), sizeof(int) * kinds.size(), hipMemcpyHostToDevice));
-        KH_HIP(hipMemcpy(e->d_par_ab, ab.data(), sizeof(double) * ab.size(), hipMemcpyHostToDevice));
-        e->par_kind_host = kinds;
-        e->par_ab_host = ab;
-    }
-    e->par_u_guess = u_guess_dev;
-    e->par_dfdu = dfdu_dev;
-    e->par_u_opt = u_opt_dev;
+    KhUpdateForm &f = e->form;
+    KH_TRY(upload_table(e, &f.d_kind, f.kind_host, std::vector<int>(kind, kind + e->L)));
+    KH_TRY(upload_table(e, &f.d_ab, f.ab_host, ab));
+    f.tag = FORM_PAR, f.u_guess = u_guess_dev, f.dfdu = dfdu_dev, f.u_opt = u_opt_dev;
     return KH_OK;
 }
 
 // Non-linear controls (include/krotov_hip.h): the engine's L slots become terms eps_c^p H_j of C controls; the following
-// update sweeps run kh_tile_forward_update_nl or kh_gen_forward_update_nl, by launch_update's rule
+// update sweeps run kh_tile_forward_update_nl or kh_gen_forward_update_nl, by update_route's rule
 extern "C" int kh_set_nonlinear(kh_engine *e, int32_t C, const int32_t *term_control, const int32_t *term_power,
                                 const double *dcde_dev) {
     if (e == nullptr) return kh_fail(KH_ERR_INVALID, "null engine");
     if (term_control == nullptr) {
-        e->nl_dcde = nullptr;
-        e->nl_C = 0;
-        if (e->reduced_par) e->reduced_G = 0;  // (a reduced grid set while non-linear goes with it)
-        e->reduced_par = false;
+        clear_form(e, FORM_NL);
         return KH_OK;
     }
-    if (e->lind) return kh_fail(KH_ERR_UNSUPPORTED, "Lindblad-form engines (kh_engine_create_lindblad) take no non-linear controls: build the Liouvillian and use kh_engine_create");
-    if (e->replicas > 0) return kh_fail(KH_ERR_UNSUPPORTED, "replica engines (kh_engine_create_replicas) take no non-linear controls");
-    if (e->p2p_ready || e->p2p_window != nullptr) return kh_fail(KH_ERR_UNSUPPORTED, "sharded engines take no non-linear controls (one GPU)");
-    if (e->row_split > 1) return kh_fail(KH_ERR_UNSUPPORTED, "a split engine (kh_set_row_split) takes no non-linear controls: set the row split to 1 first");
-    if (!e->gen_fits) return kh_fail(KH_ERR_UNSUPPORTED, "N=%d: non-linear controls run on the generic kernels, whose vectors do not fit LDS", e->N);
-    if (e->L < 1) return kh_fail(KH_ERR_INVALID, "no terms");
-    if (e->par_dfdu != nullptr) return kh_fail(KH_ERR_INVALID, "a pulse parametrization is set (kh_set_parametrization): the two are not combined");
+    KH_TRY(refuse_form(e, FORM_NL));
     if (term_power == nullptr || dcde_dev == nullptr) return kh_fail(KH_ERR_INVALID, "null argument");
     if (C < 1 || C > e->L) return kh_fail(KH_ERR_INVALID, "%d controls for %d terms", (int)C, e->L);
     std::vector<int> tab(term_control, term_control + e->L);
@@ -3057,33 +3082,21 @@ extern "C" int kh_set_nonlinear(kh_engine *e, int32_t C, const int32_t *term_con
     }
     for (int c = 0; c < C; ++c)
         if (!seen[(size_t)c]) return kh_fail(KH_ERR_INVALID, "control %d has no term", c);
-    if (e->d_nl_tab == nullptr) KH_TRY(dev_alloc(e, &e->d_nl_tab, sizeof(int) * 2 * (size_t)e->L));
-    // (as kh_set_parametrization: the table is uploaded when it changes, behind a device-wide wait)
-    if (tab != e->nl_tab_host) {
-        KH_HIP(hipDeviceSynchronize());
-        KH_HIP(hipMemcpy(e->d_nl_tab, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice));
-        e->nl_tab_host = tab;
-    }
-    e->nl_dcde = dcde_dev;
-    e->nl_C = C;
+    KhUpdateForm &f = e->form;
+    KH_TRY(upload_table(e, &f.d_tab, f.tab_host, tab));
+    f.tag = FORM_NL, f.dcde = dcde_dev, f.C = C;
     return KH_OK;
 }
 
-// replica engines: the same switch with one sigma row per replica ([B][nt-1]; kh_replica.h, kh_rep_forward_update_so)
-extern "C" int kh_set_second_order_replicas(kh_engine *e, const kh_cdouble *fw_prev_dev, kh_cdouble *fw_store_dev,
-                                            const double *sigma_dev) {
-    if (e == nullptr) return kh_fail(KH_ERR_INVALID, "null engine");
-    if (e->replicas < 1) return kh_fail(KH_ERR_UNSUPPORTED, "only replica engines (kh_engine_create_replicas) take one sigma row per replica; this one runs %s (kh_set_second_order)", kh_engine_kernel(e));
-    const int given = (fw_prev_dev != nullptr) + (fw_store_dev != nullptr) + (sigma_dev != nullptr);
-    if (given != 0 && given != 3)
-        return kh_fail(KH_ERR_INVALID, "fw_prev, fw_store and sigma must be given together (or all NULL)");
-    if (fw_prev_dev != nullptr && (const void *)fw_prev_dev == (const void *)fw_store_dev)
-        return kh_fail(KH_ERR_INVALID, "fw_store must not alias fw_prev");
-    e->so_fw_prev = (const cplx *)fw_prev_dev;
-    e->so_fw_store = (cplx *)fw_store_dev;
-    e->so_sigma = sigma_dev;
+// what the four kh_update_* entry points refuse
+static int refuse_stepwise(const kh_engine *e) {
+    if (e->lind) return kh_fail(KH_ERR_UNSUPPORTED, "Lindblad-form engines (kh_engine_create_lindblad) have no per-interval update sweep");
+    if (e->replicas > 0) return kh_fail(KH_ERR_UNSUPPORTED, "replica engines (kh_engine_create_replicas) have no per-interval update sweep");
     return KH_OK;
 }
+
+// rows of the update sweep's pulse-like arrays: the C controls of kh_set_nonlinear (the pulses are rows of eps), else L
+static int update_rows(const kh_engine *e) { return e->form.tag == FORM_NL ? e->form.C : e->L; }
 
 extern "C" int kh_update_begin(kh_engine *e, const kh_cdouble *chi_store_dev, const double *chi_norms_dev,
                                const kh_cdouble *init_dev, const double *guess_dev, double *opt_dev,
@@ -3092,18 +3105,17 @@ extern "C" int kh_update_begin(kh_engine *e, const kh_cdouble *chi_store_dev, co
         guess_dev == nullptr || opt_dev == nullptr || g_a_dev == nullptr || partial_dev == nullptr)
         return kh_fail(KH_ERR_INVALID, "null argument");
     if (e->L < 1) return kh_fail(KH_ERR_INVALID, "no controls to update");
-    if (e->lind) return kh_fail(KH_ERR_UNSUPPORTED, "Lindblad-form engines (kh_engine_create_lindblad) have no per-interval update sweep");
-    if (e->replicas > 0) return kh_fail(KH_ERR_UNSUPPORTED, "replica engines (kh_engine_create_replicas) have no per-interval update sweep");
+    KH_TRY(refuse_stepwise(e));
     hipStream_t st = (hipStream_t)stream;
     e->guess_dev = guess_dev;
     KH_HIP(hipMemsetAsync(e->d_stats, 0, sizeof(double) * 4, st));
     KH_HIP(hipMemcpyAsync(e->d_phi, init_dev, sizeof(cplx) * (size_t)e->K * e->N, hipMemcpyDeviceToDevice, st));
-    const int rows = e->nl_dcde != nullptr ? e->nl_C : e->L;  // (non-linear controls: the pulses are C rows of eps)
+    const int rows = update_rows(e);
     KH_HIP(hipMemcpyAsync(opt_dev, guess_dev, sizeof(double) * (size_t)rows * (e->nt - 1),
                           hipMemcpyDeviceToDevice, st));
     KH_HIP(hipMemsetAsync(g_a_dev, 0, sizeof(double) * rows, st));
-    if (e->par_dfdu != nullptr)
-        KH_HIP(hipMemcpyAsync(e->par_u_opt, e->par_u_guess, sizeof(double) * (size_t)e->L * (e->nt - 1), hipMemcpyDeviceToDevice, st));
+    if (e->form.tag == FORM_PAR)
+        KH_HIP(hipMemcpyAsync(e->form.u_opt, e->form.u_guess, sizeof(double) * (size_t)e->L * (e->nt - 1), hipMemcpyDeviceToDevice, st));
     const KhUpdateArgs u = update_args(e, chi_store_dev, chi_norms_dev, guess_dev, nullptr, nullptr, opt_dev, g_a_dev);
     return update_interval(e, u, nullptr, 0, 0, nullptr, partial_dev, true, st);
 }
@@ -3115,8 +3127,7 @@ extern "C" int kh_update_step(kh_engine *e, int32_t n, const double *D_dev, cons
         shape_dev == nullptr || lambda_dev == nullptr || opt_dev == nullptr || g_a_dev == nullptr ||
         partial_dev == nullptr)
         return kh_fail(KH_ERR_INVALID, "null argument");
-    if (e->lind) return kh_fail(KH_ERR_UNSUPPORTED, "Lindblad-form engines (kh_engine_create_lindblad) have no per-interval update sweep");
-    if (e->replicas > 0) return kh_fail(KH_ERR_UNSUPPORTED, "replica engines (kh_engine_create_replicas) have no per-interval update sweep");
+    KH_TRY(refuse_stepwise(e));
     if (e->guess_dev == nullptr) return kh_fail(KH_ERR_INVALID, "kh_update_begin was not called");
     if (n < 0 || n >= e->nt - 1) return kh_fail(KH_ERR_INVALID, "interval %d out of range", n);
     const KhUpdateArgs u = update_args(e, chi_store_dev, chi_norms_dev, e->guess_dev, shape_dev, lambda_dev, opt_dev, g_a_dev);
@@ -3131,8 +3142,7 @@ extern "C" int kh_update_step_dev(kh_engine *e, int32_t *n_dev, const double *D_
         chi_norms_dev == nullptr || shape_dev == nullptr || lambda_dev == nullptr || opt_dev == nullptr ||
         g_a_dev == nullptr || partial_dev == nullptr)
         return kh_fail(KH_ERR_INVALID, "null argument");
-    if (e->lind) return kh_fail(KH_ERR_UNSUPPORTED, "Lindblad-form engines (kh_engine_create_lindblad) have no per-interval update sweep");
-    if (e->replicas > 0) return kh_fail(KH_ERR_UNSUPPORTED, "replica engines (kh_engine_create_replicas) have no per-interval update sweep");
+    KH_TRY(refuse_stepwise(e));
     if (e->guess_dev == nullptr) return kh_fail(KH_ERR_INVALID, "kh_update_begin was not called");
     const KhUpdateArgs u = update_args(e, chi_store_dev, chi_norms_dev, e->guess_dev, shape_dev, lambda_dev, opt_dev, g_a_dev);
     return update_interval(e, u, D_dev, 0, 1, n_dev, partial_dev, true, (hipStream_t)stream);  // (n_begin: overridden on the device)
@@ -3140,8 +3150,7 @@ extern "C" int kh_update_step_dev(kh_engine *e, int32_t *n_dev, const double *D_
 
 extern "C" int kh_update_end(kh_engine *e, kh_cdouble *psi_T_dev, void *stream) {
     if (e == nullptr || psi_T_dev == nullptr) return kh_fail(KH_ERR_INVALID, "null argument");
-    if (e->lind) return kh_fail(KH_ERR_UNSUPPORTED, "Lindblad-form engines (kh_engine_create_lindblad) have no per-interval update sweep");
-    if (e->replicas > 0) return kh_fail(KH_ERR_UNSUPPORTED, "replica engines (kh_engine_create_replicas) have no per-interval update sweep");
+    KH_TRY(refuse_stepwise(e));
     KH_HIP(hipMemcpyAsync(psi_T_dev, e->d_phi, sizeof(cplx) * (size_t)e->K * e->N, hipMemcpyDeviceToDevice,
                           (hipStream_t)stream));
     e->guess_dev = nullptr;
@@ -3186,8 +3195,7 @@ extern "C" int kh_p2p_create_window(kh_engine *e, int32_t world, int32_t rank, u
     if (e->mixed) return kh_fail(KH_ERR_UNSUPPORTED, "mixed engines (kh_engine_create_mixed) are not sharded");
     if (e->lind) return kh_fail(KH_ERR_UNSUPPORTED, "Lindblad-form engines (kh_engine_create_lindblad) are not sharded");
     if (e->replicas > 0) return kh_fail(KH_ERR_UNSUPPORTED, "replica engines (kh_engine_create_replicas) are not sharded");
-    if (e->par_dfdu != nullptr) return kh_fail(KH_ERR_UNSUPPORTED, "a parametrized engine (kh_set_parametrization) is not sharded");
-    if (e->nl_dcde != nullptr) return kh_fail(KH_ERR_UNSUPPORTED, "an engine with non-linear controls (kh_set_nonlinear) is not sharded");
+    if (e->form.set()) return kh_fail(KH_ERR_UNSUPPORTED, "%s is not sharded", kh_form_words[e->form.tag].engine);
     const int Lx = e->L > 0 ? e->L : 1;
     if (world * Lx * 2 > 64 || Lx > KH_MAX_L)
         return kh_fail(KH_ERR_UNSUPPORTED, "world * L = %d exceeds the 32 exchange lanes (or more than %d controls)", world * Lx, KH_MAX_L);

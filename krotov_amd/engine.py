@@ -127,6 +127,9 @@ class HipKrotovEngine:
         self._dt = dt
         self._handle = ctypes.c_void_p()
         self._op_tensors = {}
+        # the tensors the library points at while a variant of the update sweep is set (set_second_order*,
+        # set_parametrization, set_nonlinear), and forward_update_sharded's persistent buffers
+        self._so = self._par = self._nl = self._sh = None
         for k, row in enumerate(ops):
             if len(row) != 1 + self.L:
                 raise ValueError("objective %d has %d operators, expected %d" % (k, len(row), 1 + self.L))
@@ -438,13 +441,13 @@ class HipKrotovEngine:
         """(L, nt-1), or (B, L, nt-1) on a replica engine."""
         return (self.replicas, self.L, self.nt - 1) if self.replicas else (self.L, self.nt - 1)
 
-    def _out(self, t, shape, dtype):
-        """``t`` as an output buffer (written in place), or a new one."""
+    def _out(self, t, shape, dtype, name='output buffer'):
+        """``t`` as an output buffer (written in place: a contiguous tensor of this shape, dtype and device), or a new one."""
         if t is None:
             return torch.empty(shape, dtype=dtype, device=self.device)
         if (not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(shape) or t.dtype != dtype or not t.is_contiguous()
                 or t.device != self.device):
-            raise ValueError("output buffer must be a contiguous %s %s tensor on %s" % (tuple(shape), dtype, self.device))
+            raise ValueError("%s must be a contiguous %s %s tensor on %s" % (name, tuple(shape), dtype, self.device))
         return t
 
     def set_active_replicas(self, mask=None):
@@ -548,18 +551,22 @@ class HipKrotovEngine:
         (``fw_prev``, ``fw_store``: (K, nt, N) device tensors; ``sigma_vals``:
         sigma at the nt-1 interval mid-points), or back to first order (no
         arguments)."""
-        if fw_prev is None:
+        self._set_second_order(self._lib.kh_set_second_order, (self.nt - 1,), fw_prev is None, fw_prev, fw_store, sigma_vals)
+
+    def _set_second_order(self, fn, sigma_shape, off, fw_prev, fw_store, sigma_vals):
+        """``fn`` (``kh_set_second_order`` or ``kh_set_second_order_replicas``) with the three device tensors, or with
+        none (``off``)."""
+        if off:
+            _lib.check(fn(self._handle, None, None, None))
             self._so = None
-            _lib.check(self._lib.kh_set_second_order(self._handle, None, None, None))
             return
+        if fw_prev is None or fw_store is None or sigma_vals is None:
+            raise ValueError("fw_prev, fw_store and sigma_vals must be given together (or none of them)")
         fw_prev = self._c(fw_prev, (self.K, self.nt, self.N))
-        if (not isinstance(fw_store, torch.Tensor) or tuple(fw_store.shape) != (self.K, self.nt, self.N)
-                or fw_store.dtype != torch.complex128 or fw_store.device != self.device or not fw_store.is_contiguous()):
-            raise ValueError("fw_store must be a contiguous (K, nt, N) complex128 device tensor")
-        sig = self._f(sigma_vals, (self.nt - 1,))
+        fw_store = self._out(fw_store, (self.K, self.nt, self.N), torch.complex128, name='fw_store')
+        sig = self._f(sigma_vals, sigma_shape)
+        _lib.check(fn(self._handle, fw_prev.data_ptr(), fw_store.data_ptr(), sig.data_ptr()))
         self._so = (fw_prev, fw_store, sig)  # keep the tensors alive while the engine points at them
-        _lib.check(self._lib.kh_set_second_order(
-            self._handle, fw_prev.data_ptr(), fw_store.data_ptr(), sig.data_ptr()))
 
     def set_parametrization(self, kind=None, a=None, b=None, u_guess=None, dfdu=None, u_opt=None):
         """Switch the following update sweeps to pulse parametrizations eps_l = f_l(u_l) (``kh_set_parametrization``):
@@ -583,9 +590,7 @@ class HipKrotovEngine:
             return
         u_guess = self._f(u_guess, (L, self.nt - 1))
         dfdu = self._f(dfdu, (L, self.nt - 1))
-        if (not isinstance(u_opt, torch.Tensor) or tuple(u_opt.shape) != (L, self.nt - 1) or u_opt.dtype != torch.float64
-                or u_opt.device != self.device or not u_opt.is_contiguous()):
-            raise ValueError("u_opt must be a contiguous (L, nt-1) float64 device tensor")
+        u_opt = self._out(u_opt, (L, self.nt - 1), torch.float64, name='u_opt')
         _lib.check(self._lib.kh_set_parametrization(
             self._handle, kind.ctypes.data, a.ctypes.data, b.ctypes.data, u_guess.data_ptr(), dfdu.data_ptr(),
             u_opt.data_ptr()))
@@ -616,30 +621,18 @@ class HipKrotovEngine:
 
     def _update_rows(self):
         """Rows of the update sweeps' pulse-like arrays: the controls of :meth:`set_nonlinear`, else L."""
-        nl = getattr(self, '_nl', None)
-        return nl[0] if nl is not None else self.L
+        return self._nl[0] if self._nl is not None else self.L
 
     def set_second_order_replicas(self, fw_prev=None, fw_store=None, sigma_vals=None):
         """Replica engines: switch the following update sweeps to the second-order update with one sigma row per
         replica (``fw_prev``, ``fw_store``: (K, nt, N) device tensors; ``sigma_vals``: (B, nt-1), sigma_b at replica
         b's interval mid-points), or back to first order (no arguments).  ``kh_set_second_order_replicas``;
         ``KrotovHipError`` (``KH_ERR_UNSUPPORTED``) on any other engine."""
-        if fw_prev is None and fw_store is None and sigma_vals is None:
-            _lib.check(self._lib.kh_set_second_order_replicas(self._handle, None, None, None))
-            self._so = None
-            return
-        if not self.replicas:  # (the library's own answer, before any shape is looked at)
-            _lib.check(self._lib.kh_set_second_order_replicas(self._handle, None, None, None))
-        if fw_prev is None or fw_store is None or sigma_vals is None:
-            raise ValueError("fw_prev, fw_store and sigma_vals must be given together (or none of them)")
-        fw_prev = self._c(fw_prev, (self.K, self.nt, self.N))
-        if (not isinstance(fw_store, torch.Tensor) or tuple(fw_store.shape) != (self.K, self.nt, self.N)
-                or fw_store.dtype != torch.complex128 or fw_store.device != self.device or not fw_store.is_contiguous()):
-            raise ValueError("fw_store must be a contiguous (K, nt, N) complex128 device tensor")
-        sig = self._f(sigma_vals, (self.replicas, self.nt - 1))
-        _lib.check(self._lib.kh_set_second_order_replicas(
-            self._handle, fw_prev.data_ptr(), fw_store.data_ptr(), sig.data_ptr()))
-        self._so = (fw_prev, fw_store, sig)  # keep the tensors alive while the engine points at them
+        fn = self._lib.kh_set_second_order_replicas
+        off = fw_prev is None and fw_store is None and sigma_vals is None
+        if not off and not self.replicas:  # (the library's own answer, before any shape is looked at)
+            _lib.check(fn(self._handle, None, None, None))
+        self._set_second_order(fn, (self.replicas, self.nt - 1), off, fw_prev, fw_store, sigma_vals)
 
     def set_update_workgroups(self, max_workgroups=0):
         """Run the following single-launch update sweeps on at most ``max_workgroups`` workgroups (0: the engine's own
@@ -710,7 +703,7 @@ class HipKrotovEngine:
         nt, K, N = self.nt, self.K, self.N
         L = self._update_rows()  # (non-linear controls: C rows of eps; the interval's sums stay one per term)
         # persistent buffers: stable addresses let the captured graph be reused
-        b = getattr(self, '_sh', None)
+        b = self._sh
         if b is None or b['rows'] != L:
             c128, f64 = torch.complex128, torch.float64
             b = self._sh = dict(
@@ -759,8 +752,7 @@ class HipKrotovEngine:
             # (second order: kh_update_step_dev bakes the trajectory / sigma pointers of kh_set_second_order
             # into the captured launches, and those buffers are swapped every iteration -- no replay there)
             # (non-linear controls: the weights' tensor of set_nonlinear is a new one every iteration, too)
-            if (graph_chunk > 0 and nt - 1 > 2 * graph_chunk and getattr(self, '_so', None) is None
-                    and getattr(self, '_nl', None) is None):
+            if graph_chunk > 0 and nt - 1 > 2 * graph_chunk and self._so is None and self._nl is None:
                 try:
                     stepper = _Stepper()
                     stepper.begin()
