@@ -7,7 +7,7 @@ scaled and per-objective operators; objectives without one of their controls; Hi
 Test infrastructure (it imports ``oracle/``): run on a GPU box,
 
     python tests/fuzz_parity.py [--seconds 300] [--seed 1] [--cases 0] [--level sweeps|optimize] [--regimes] [--drop-any] [--nonselfadjoint] [--short-grids]
-                                 [--bounded-constrained]
+                                 [--bounded-constrained] [--nonlinear]
 
 prints one line per case (kernel, shape, largest deviation) and a summary; exit code 1 if any case is off by more than
 the tolerance of tests/test_hip_parity.py (1e-12, 1e-11 in Liouville space).  ``tests/test_hip_parity.py::
@@ -24,7 +24,9 @@ drawn ones vanish at both ends of the grid: tests/test_grid_ends.py), decided by
 ``--bounded-constrained`` (sweeps level) gives every drawn problem random pulse parametrizations with bounds from its guess
 and a random Hermitian D with a linear shape, and runs one parametrized update sweep and one backward sweep with the
 source against the two restatements (tests/parametrization_cases.py, tests/constraint_cases.py), by a fifth generator of
-its own (tests/test_bounded_constrained_axes.py).
+its own (tests/test_bounded_constrained_axes.py).  ``--nonlinear`` (sweeps level) runs, per case, a problem with a random term
+table (terms eps_c^p H_j) on a random engine base in a random regime against tests/nonlinear_cases.py, drawn by a sixth
+generator of its own (tests/test_nonlinear_axes.py).
 """
 import argparse
 import os
@@ -372,6 +374,92 @@ def run_bounded_constrained_case(rng_bc, spec, fmt):
         eng.close()
 
 
+NONLINEAR_BASES = {
+    # name: (builder(J, nt), operator form, theta_max): a base of every engine family that takes a term table at small sizes
+    'mini4': (lambda J, nt: configs.config_c5(K=2, N=4, nt=nt, L=J, distinct=True), 'dense', 1.0),
+    'mini16': (lambda J, nt: configs.config_c5(K=6, N=16, nt=nt, L=J, distinct=True), 'dense', 1.0),
+    'tile33': (lambda J, nt: configs.config_c5(K=5, N=33, nt=nt, L=J, distinct=True), 'dense', 1.0),
+    'tile64': (lambda J, nt: configs.config_c5(K=4, N=64, nt=nt, L=J, distinct=True), 'dense', 1.0),
+    'tile128': (lambda J, nt: configs.config_c5(K=3, N=80, nt=nt, L=J), 'dense', 1.0),
+    'coop': (lambda J, nt: configs.config_shared(K=8, N=96, nt=nt, L=J), 'dense', 4.0),
+    'csr33': (lambda J, nt: configs.config_c5(K=5, N=33, nt=nt, L=J, distinct=True), 'csr', 1.0),
+    'csr12': (lambda J, nt: configs.config_c5(K=5, N=12, nt=nt, L=J, distinct=True), 'csr', 1.0),
+}
+NONLINEAR_REGIMES = ('ramp', 'pulse_ramp', 'tiny', 'amplitude', 'ends')
+
+
+def draw_nonlinear(rng_nl):
+    """``--nonlinear``: a problem with a term table (tests/nonlinear_cases.py, ``helpers`` with ``obj.terms``) -- J in 1..6
+    slots, a table that meets ``kh_set_nonlinear``'s rules (1 <= C <= min(J, 3) controls, every control with a term, powers
+    1..4, at least one power above 1, in random order), an engine base, a regime of the series entered under the
+    coefficient pulses (or ``helpers.grid_ends`` on 1..6 intervals) and a sign per control.  ``rng_nl`` is NOT the
+    generator of :func:`draw`.  Returns (problem, tag, theta_max)."""
+    import nonlinear_cases as nc
+
+    J = int(rng_nl.integers(1, 7))
+    C = int(rng_nl.integers(1, min(J, 3) + 1))
+    ctrl = list(range(C)) + [int(c) for c in rng_nl.integers(0, C, J - C)]
+    rng_nl.shuffle(ctrl)
+    power = [int(p) for p in rng_nl.integers(1, 5, J)]
+    if max(power) == 1:
+        power[int(rng_nl.integers(0, J))] = int(rng_nl.integers(2, 5))
+    terms = list(zip(ctrl, power))
+    base = str(rng_nl.choice(sorted(NONLINEAR_BASES)))
+    regime = str(rng_nl.choice(NONLINEAR_REGIMES))
+    signs = rng_nl.choice([-1.0, 1.0], C)
+    build, fmt, theta_max = NONLINEAR_BASES[base]
+    intervals = int(rng_nl.integers(1, 7)) if regime == 'ends' else 33
+    obj = nc.with_terms(hp.explicit(build(J, intervals + 1), fmt), terms)
+    obj = hp.grid_ends(obj, theta_max) if regime == 'ends' else hp.REGIMES[regime](obj, theta_max)
+    obj.pulses = [s * np.asarray(p) for s, p in zip(signs, obj.pulses)]  # (theta sees |eps| only: the regime stays)
+    obj.lambdas = nc.lambdas_in_eps(obj)
+    tag = '%s %s I=%d terms=%s signs=%s' % (base, regime, intervals, ''.join('%d^%d ' % t for t in terms).strip().replace(' ', ','),
+                                          ''.join('+' if s > 0 else '-' for s in signs))
+    return obj, tag, theta_max
+
+
+def nonlinear_inputs(obj):
+    """``--nonlinear``, host side: co-states on the coefficient pulses and the restated non-linear update sweep."""
+    import nonlinear_cases as nc
+
+    view = nc.coefficient_view(obj)
+    prob = hp.regime_oracle(view)
+    chi_T = prob.target / np.linalg.norm(prob.target, axis=1)[:, None]
+    norms = np.full(obj.K, 0.3 * min(1.0, 8.0 / obj.K) * min(1.0, 4.0 / obj.L))  # (run_regime_case)
+    if getattr(obj, 'name', '').startswith('shared'):
+        norms *= 0.02
+    with hp.MemoExpm():
+        chi = ko.backward_sweep(prob, chi_T, view.pulses)
+        opt, psi_T, g_a = nc.update_sweep(prob, chi, norms, obj.pulses, obj.terms, obj.shapes, obj.lambdas)
+    return dict(prob=prob, chi_T=chi_T, norms=norms, coef=np.array(view.pulses), dcde=nc.weights(obj.terms, obj.pulses),
+                chi=chi, opt=np.array(opt), psi_T=psi_T, g_a=np.array(g_a))
+
+
+def run_nonlinear_case(obj, theta_max):
+    """``--nonlinear``: largest deviations of the co-states and of one non-linear update sweep from the restatement."""
+    from krotov_amd import _lib
+
+    r = nonlinear_inputs(obj)
+    eng = hp.regime_engine(obj, theta_max)
+    try:
+        chi = eng.backward(r['chi_T'], r['coef'])
+        eng.set_nonlinear([c for c, _ in obj.terms], [p for _, p in obj.terms], r['dcde'])
+        _lib.forget_launched_kernels()
+        opt, psi_T, g_a = eng.forward_update(chi, r['norms'], r['prob'].init, np.array(obj.pulses), np.array(obj.shapes),
+                                             np.array(obj.lambdas))
+        eng.check()
+        form = [n for n in _lib.kernel_instantiations(launched_only=True) if '_nl<' in n]
+        assert len(form) == 1, form
+        return '%s %s' % (eng.kernel, form[0]), {
+            'chi': np.abs(chi.cpu().numpy() - r['chi']).max(),
+            'opt': np.abs(opt.cpu().numpy() - r['opt']).max() / max(1.0, np.abs(r['opt']).max()),
+            'psi_T': np.abs(psi_T.cpu().numpy() - r['psi_T']).max(),
+            'g_a': np.abs(g_a.cpu().numpy() - r['g_a']).max() / max(1.0, np.abs(r['g_a']).max()),
+        }
+    finally:
+        eng.close()
+
+
 def run_optimize_case(spec, fmt, rng):
     """Two iterations of ``krotov_amd.optimize_pulses`` on the GPU against ``oracle.optimize``: a random chi constructor
     (``chis_re / ss / sm``; ``chis_hs`` for density matrices), first or second order (the reference's notebook-07 sigma with
@@ -408,7 +496,7 @@ def run_optimize_case(spec, fmt, rng):
 
 
 def fuzz(seed, seconds=None, cases=None, verbose=True, level='sweeps', regimes=False, drop_any=False, stats=None,
-         nonselfadjoint=False, short_grids=False, bounded_constrained=False):
+         nonselfadjoint=False, short_grids=False, bounded_constrained=False, nonlinear=False):
     """Run random cases until `seconds` have passed or `cases` are done; returns (number run, list of failures).
     ``stats``: a dict that receives how many cases had an absent control (``'absent'``) and how many of those had one
     control (``'absent_L1'``), and how many a control that is not self-adjoint (``'nonselfadjoint'``)."""
@@ -418,6 +506,7 @@ def fuzz(seed, seconds=None, cases=None, verbose=True, level='sweeps', regimes=F
     rng_nsa = np.random.default_rng([int(seed), 0x5ad1]) if nonselfadjoint and level == 'sweeps' else None  # (likewise)
     rng_short = np.random.default_rng([int(seed), 0x2e9d]) if short_grids and level == 'sweeps' else None  # (likewise)
     rng_bc = np.random.default_rng([int(seed), 0xbc0d]) if bounded_constrained and level == 'sweeps' else None  # (likewise)
+    rng_nl = np.random.default_rng([int(seed), 0x4e11]) if nonlinear and level == 'sweeps' else None  # (likewise)
     counts = {'absent': 0, 'absent_L1': 0}
     if rng_nsa is not None:  # (the key only where it was asked for: the older tests compare the whole dict)
         counts['nonselfadjoint'] = 0
@@ -453,6 +542,10 @@ def fuzz(seed, seconds=None, cases=None, verbose=True, level='sweeps', regimes=F
                 liouville = obj.fmt == 'lindblad' or bool(np.any(obj.is_super))
                 tol = 1e-11 if liouville or ' ramp ' in tag else 1e-12  # (as tests/test_series_regimes.py)
                 kernel, dev = run_regime_case(obj, theta_max)
+            elif rng_nl is not None:  # (a problem of its own; the default stream drew its own above, as always)
+                obj, tag, theta_max = draw_nonlinear(rng_nl)
+                tol = 1e-11 if ' ramp ' in tag or ' amplitude ' in tag else 1e-12  # (as tests/test_nonlinear_axes.py)
+                kernel, dev = run_nonlinear_case(obj, theta_max)
             elif rng_bc is not None:
                 kernel, dev = run_bounded_constrained_case(rng_bc, spec, fmt)
                 counts['no_parametrization'] += 1 if kernel.endswith('(no parametrization)') else 0
@@ -503,8 +596,12 @@ if __name__ == '__main__':
                     help="every drawn problem gets random pulse parametrizations (bounds from its guess) and a random Hermitian D "
                          "with a linear shape: one parametrized update sweep and one backward sweep with the source against the "
                          "restatements; decided by a separate generator (sweeps level)")
+    ap.add_argument('--nonlinear', action='store_true',
+                    help="every case is a problem with a random term table (J in 1..6 slots, powers 1..4) on a random engine base "
+                         "in a random regime with a random sign pattern: one non-linear update sweep against the restatement; "
+                         "drawn from a separate generator (sweeps level)")
     a = ap.parse_args()
     n, bad = fuzz(a.seed, seconds=None if a.cases else a.seconds, cases=a.cases or None, level=a.level, regimes=a.regimes,
                   drop_any=a.drop_any, nonselfadjoint=a.nonselfadjoint, short_grids=a.short_grids,
-                  bounded_constrained=a.bounded_constrained)
+                  bounded_constrained=a.bounded_constrained, nonlinear=a.nonlinear)
     sys.exit(1 if bad else 0)

@@ -288,12 +288,42 @@ def series_bounds(obj, norm=None, factor=1.0):
     return np.array([[bound(obj.H0[k], fn)] + [bound(obj.Hc[k][l], fn) for l in range(obj.L)] for k in range(obj.K)])
 
 
-def theta_sequence(obj, pulses=None, bounds=None):
+def n_pulses(obj):
+    """Rows of ``pulses`` / ``shapes`` / ``lambdas``: the L controls, or -- a problem with a term table ``obj.terms``, L
+    pairs (control, power): slot j carries eps_c(j)^p_j H_j (tests/test_nonlinear_axes.py) -- its C controls."""
+    terms = getattr(obj, 'terms', None)
+    return obj.L if not terms else max(c for c, _ in terms) + 1
+
+
+def theta_sequence(obj, pulses=None, bounds=None, terms=None):
     """theta[k, n] of a regime problem under ``pulses`` (default: its own guess) and the norm bounds ``bounds`` (default:
-    ``series_bounds(obj)``)."""
+    ``series_bounds(obj)``).  With a term table (``terms``, default ``obj.terms``) the pulses are the C pulses eps_c and
+    theta_n = dt_n (n_0 + sum_j |eps_c(j)[n]|^p_j n_j): what the series sees are the coefficient pulses."""
     b = series_bounds(obj) if bounds is None else bounds
-    eps = np.abs(np.array(obj.pulses if pulses is None else pulses, dtype=np.float64)).reshape(obj.L, -1)
+    terms = getattr(obj, 'terms', None) if terms is None else terms
+    eps = np.abs(np.array(obj.pulses if pulses is None else pulses, dtype=np.float64))
+    if terms:
+        eps = eps.reshape(max(c for c, _ in terms) + 1, -1)
+        eps = np.array([eps[c] ** p for c, p in terms])
+    eps = eps.reshape(obj.L, -1)
     return regime_dt(obj)[None, :] * (b[:, :1] + b[:, 1:] @ eps)
+
+
+def _bisect(f, target, iterations=200):
+    """The a >= 0 (an array, like ``target``) with f(a) = target for f monotone rising, f(0) <= target; to rounding."""
+    target = np.asarray(target, dtype=np.float64)
+    lo, hi = np.zeros_like(target), np.ones_like(target)
+    for _ in range(1100):
+        low = f(hi) < target
+        if not np.any(low):
+            break
+        hi = np.where(low, 2.0 * hi, hi)
+    assert not np.any(f(hi) < target), "no bracket: f stays below the target"
+    for _ in range(iterations):
+        mid = 0.5 * (lo + hi)
+        low = f(mid) < target
+        lo, hi = np.where(low, mid, lo), np.where(low, hi, mid)
+    return 0.5 * (lo + hi)
 
 
 def _scale_operators(obj, factor):
@@ -352,8 +382,22 @@ def regime_pulse_ramp(obj, theta_max, periods=1, zeros=True, steps=None):
     if drift * regime_dt(new).max() >= theta_max:
         raise ValueError("the drift alone is beyond theta_max")
     profile = ramp_profile(M, periods)
-    a = (theta_max * profile / regime_dt(new) - drift) / (rate - drift)
-    a = np.maximum(a, PULSE_RAMP_FLOOR * a.max())
+    if getattr(new, 'terms', None):
+        # a term table: dt_n (n_0 + sum_j |a_n e_c(j)[n]|^p_j n_j) = theta_max profile_n is monotone in a_n -- bisection;
+        # the objective whose theta is the largest under the result (it may change with a: looked for again, twice)
+        e = np.abs(np.array(new.pulses))
+        for _ in range(3):
+            b = series_bounds(new)[k]
+            a = _bisect(lambda a: b[0] + sum(b[1 + j] * (a * e[c]) ** p for j, (c, p) in enumerate(new.terms)),
+                        theta_max * profile / regime_dt(new))
+            a = np.maximum(a, PULSE_RAMP_FLOOR * a.max())
+            top = int(np.argmax(theta_sequence(new, a * e).max(axis=1)))
+            if top == k:
+                break
+            k = top
+    else:
+        a = (theta_max * profile / regime_dt(new) - drift) / (rate - drift)
+        a = np.maximum(a, PULSE_RAMP_FLOOR * a.max())
     new.pulses = [a * p for p in new.pulses]
     if zeros:
         falling = [n for n in range(1, M) if profile[n] < 1.0 <= profile[n - 1]]  # (one per period)
@@ -380,8 +424,35 @@ def regime_long(obj, theta_max):
     return regime_pulse_ramp(obj, theta_max, periods=2)
 
 
+AMPLITUDE_COEFFICIENT, AMPLITUDE_LOW = 256.0, 0.4  # largest |eps^p| of a control's highest power; smallest |eps|
+
+
+def regime_amplitude(obj, theta_max):
+    """A ramp whose guess pulses straddle |eps| = 1 (problems with a term table: |eps|^p and |eps| part ways there).
+    Control c keeps the envelope of its guess, rescaled to low_c + (top_c - low_c) |guess| / max |guess| with low_c =
+    0.4 - c / 20 and top_c = (256 - 32 c)^(1 / p), p the highest power of the control's terms (1 without a table): the
+    largest coefficient |eps^p| is the same whatever the table -- |eps| up to 4 with a power 4, up to 16 with a square --,
+    so that a plan formed from |eps| with the powers ignored is short by a factor of several on every table, and where the
+    envelope is above a quarter of its largest value the term eps^p H outweighs a drift of several times its norm.  The
+    controls 0, 2, ... change sign in the middle of the grid.  Then ``regime_ramp``: dt_n such that theta_n follows
+    ``ramp_profile`` under these pulses."""
+    new = explicit(obj)
+    M = len(regime_dt(new))
+    if n_pulses(new) > 3:
+        raise ValueError("the amplitude regime is laid out for up to three controls")
+    terms = getattr(new, 'terms', None) or [(c, 1) for c in range(new.L)]
+    half = np.where(np.arange(M) < M // 2, 1.0, -1.0)
+    out = []
+    for c, p in enumerate(new.pulses):
+        top = (AMPLITUDE_COEFFICIENT - 32.0 * c) ** (1.0 / max(q for cj, q in terms if cj == c))
+        low = AMPLITUDE_LOW - 0.05 * c
+        out.append((half if c % 2 == 0 else 1.0) * (low + (top - low) * np.abs(p) / np.abs(p).max()))
+    new.pulses = out
+    return regime_ramp(new, theta_max)
+
+
 REGIMES = {'ramp': regime_ramp, 'pulse_ramp': regime_pulse_ramp, 'tiny': lambda obj, theta_max: regime_tiny(obj),
-           'long': regime_long}
+           'long': regime_long, 'amplitude': regime_amplitude}
 
 
 # ---- the ends of the interval pipeline (tests/test_grid_ends.py, tests/fuzz_parity.py --short-grids)
@@ -398,8 +469,15 @@ def grid_ends_pulses(obj, M):
     b = series_bounds(obj)
     k = int(np.argmax(b[:, 0]))
     n, out = np.arange(M), []
-    for l in range(obj.L):
-        a = b[k, 0] / (obj.L * b[k, 1 + l]) if b[k, 1 + l] > 0.0 and b[k, 0] > 0.0 else 1.0
+    terms = getattr(obj, 'terms', None)
+    for l in range(n_pulses(obj)):
+        if terms:  # (a term table: the terms of control l together at their share of the drift's bound, sum_j a^p_j n_j)
+            own = [(b[k, 1 + j], p) for j, (c, p) in enumerate(terms) if c == l and b[k, 1 + j] > 0.0]
+            a = 1.0
+            if own and b[k, 0] > 0.0:
+                a = float(_bisect(lambda x: sum(nj * x ** p for nj, p in own), b[k, 0] * len(own) / obj.L))
+        else:
+            a = b[k, 0] / (obj.L * b[k, 1 + l]) if b[k, 1 + l] > 0.0 and b[k, 0] > 0.0 else 1.0
         out.append(a * (-1.0) ** (l + n) * (0.4 + 0.1 * ((3 * l + 5 * n + 1) % 7)))
     return out
 
@@ -422,24 +500,25 @@ def grid_ends(obj, theta_max):
         _set_dt(new, theta_max * np.resize(GRID_ENDS_THETA[min(M, 4)], M) / _largest(new)[1])
     else:
         new = regime_pulse_ramp(new, theta_max, periods=max(1, M // 64), zeros='inner', steps=GRID_ENDS_STEPS)
-    new.shapes = [0.2 + 0.8 * (np.arange(M) + 1.0) / M for _ in range(new.L)]
+    new.shapes = [0.2 + 0.8 * (np.arange(M) + 1.0) / M for _ in range(n_pulses(new))]
     return new
 
 
 def grid_ends_witness(obj, theta_max):
     """Assert the input conditions of a ``grid_ends`` problem (host only); returns theta[k, n]."""
-    pulses, dt = np.array(obj.pulses, dtype=np.float64).reshape(obj.L, -1), regime_dt(obj)
+    C = n_pulses(obj)
+    pulses, dt = np.array(obj.pulses, dtype=np.float64).reshape(C, -1), regime_dt(obj)
     M = len(dt)
     assert all(np.array_equal(s, 0.2 + 0.8 * (np.arange(M) + 1.0) / M) and np.all(s > 0.2) for s in obj.shapes)
-    assert len(obj.shapes) == obj.L and pulses.shape == (obj.L, M)
+    assert len(obj.shapes) == C and pulses.shape == (C, M)
     theta = theta_sequence(obj)
     if M >= 2:
         assert dt.max() / dt.min() >= 1.5
     if M < RAMP_MIN_INTERVALS:
         assert np.all(np.abs(pulses) >= 0.1 * np.abs(pulses).max())
-        for l in range(obj.L):
+        for l in range(C):
             assert len(set(pulses[l].tolist())) == M or M > GRID_ENDS_SHORT  # differ between intervals
-        assert len({tuple(p.tolist()) for p in pulses}) == obj.L  # and between controls
+        assert len({tuple(p.tolist()) for p in pulses}) == C  # and between controls
         top = theta.max(axis=0)
         assert np.all(top >= 0.1 * theta_max * (1 - 1e-12)) and np.all(top <= 0.9 * theta_max * (1 + 1e-12))
     else:
@@ -578,7 +657,7 @@ def regime_witness(obj, regime, theta_max, pulses, tables):
         assert theta.min() <= 1e-3 * theta_max
         assert np.ptp(regime_dt(obj)) > 0
     if regime in ('pulse_ramp', 'long'):
-        eps = np.abs(np.asarray(pulses, dtype=np.float64)).reshape(obj.L, -1)
+        eps = np.abs(np.asarray(pulses, dtype=np.float64)).reshape(n_pulses(obj), -1)
         assert np.ptp(regime_dt(obj)) < 1e-12 * regime_dt(obj).max()  # uniform grid
         guess = np.array(obj.pulses)
         assert np.all(guess[:, 0] == 0.0) and np.all(guess[:, -1] == 0.0) and np.count_nonzero(guess[0] == 0.0) >= 3

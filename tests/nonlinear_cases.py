@@ -93,6 +93,63 @@ def update_sweep(problem, chi_store, chi_norms, guess, terms, shapes, lambdas, s
     return opt, np.array(fw), g_a
 
 
+# ---------------------------------------------------------------------------
+# regime problems with a term table (tests/helpers.py: ``obj.terms``; tests/test_nonlinear_axes.py)
+# ---------------------------------------------------------------------------
+# by the number of slots J of a base case; J = 1: the two tables alternate over the single-slot bases of a kernel form
+AXES_TABLES = {
+    1: ([(0, 3)], [(0, 4)]),
+    2: [(0, 2), (0, 1)],                                   # powers descending
+    3: [(1, 1), (0, 2), (1, 3)],                           # slot 0 is not control 0; one control's terms are apart
+    4: [(1, 4), (0, 1), (1, 1), (0, 3)],                   # the same, with power 4 and two controls interleaved
+    6: [(0, 1), (1, 2), (2, 1), (0, 3), (1, 1), (2, 4)],   # three controls interleaved, beyond KH_MAX_L slots
+}
+
+
+def with_terms(obj, terms):
+    """The explicit regime problem ``obj`` (``helpers.explicit``: L pulses for L slots) with the term table ``terms``:
+    the slots stay, the pulses / shapes / lambdas are those of the first C controls."""
+    import copy
+
+    assert len(terms) == obj.L
+    new = copy.copy(obj)
+    C = n_controls(terms)
+    new.terms = list(terms)
+    new.pulses = [np.array(p, dtype=np.float64) for p in obj.pulses[:C]]
+    new.shapes = [np.array(s, dtype=np.float64) for s in obj.shapes[:C]]
+    new.lambdas = list(obj.lambdas[:C])
+    return new
+
+
+def coefficient_view(obj, pulses=None):
+    """The linear regime problem the plain sweeps see: no table, the J coefficient pulses of ``pulses`` (default: the
+    guess) as its pulses."""
+    import copy
+
+    new = copy.copy(obj)
+    new.terms = None
+    new.pulses = coefficients(obj.terms, obj.pulses if pulses is None else pulses)
+    return new
+
+
+def weights(terms, pulses, linear_weights=False):
+    """(J, nt - 1): d c_j / d eps_c(j) under ``pulses`` -- the ``dcde`` of ``kh_set_nonlinear``."""
+    return np.array([weight(np.asarray(pulses[c], dtype=np.float64), p, linear_weights) for c, p in terms])
+
+
+def lambdas_in_eps(obj):
+    """lambda_a of a regime problem with a table.  The update moves the coefficient c_j by about w_j^2 S / lambda Im D,
+    w_j = p_j eps^(p_j - 1), and the regime transforms leave |eps| up to ~10 with w up to ~1e3: with the base case's
+    lambda_a the first interval would throw the pulse (and theta with it) out of the regime.  lambda_c max(1, max_n (sum_{j
+    in c} |w_j[n]|)^2) keeps the change of the coefficients what the regime helpers arranged for the linear update."""
+    w = np.abs(weights(obj.terms, obj.pulses))
+    out = []
+    for c, lam in enumerate(obj.lambdas):
+        tot = sum(w[j] for j, (cj, _) in enumerate(obj.terms) if cj == c)
+        out.append(lam * max(1.0, float(tot.max()) ** 2))
+    return out
+
+
 def J_T_re(problem, tau):
     return 1.0 - float(np.mean(np.real(tau)))
 

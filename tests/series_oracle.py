@@ -65,12 +65,13 @@ def products(tab, nsub, deg, two_terms=False):
     return int((nsub * per).sum())
 
 
-def series_step(ops, norms, eps, dt, v, table, theta_max, backwards, is_super=False):
+def series_step(ops, norms, eps, dt, v, table, theta_max, backwards, is_super=False, theta_of=None):
     """One interval: theta = dt (n_0 + sum_l |eps_l| n_l) from the norm bounds ``norms`` (1 + L), (nsub, degree) from
     ``helpers.series_plan``, then ``nsub`` times v <- sum_j c_j Z^j v (Horner, one product per term) with
-    Z = f (H0 + sum_l eps_l H_l) dt / nsub."""
+    Z = f (H0 + sum_l eps_l H_l) dt / nsub.  ``theta_of(norms, eps, dt)``: a plan from outside -- the theta the series is
+    planned with, whatever the generator (a witness evaluates what a wrongly planned kernel would compute)."""
     eps = np.asarray(eps, dtype=np.complex128).reshape(-1)
-    theta = dt * (norms[0] + float(np.dot(np.abs(eps), norms[1:])))
+    theta = dt * (norms[0] + float(np.dot(np.abs(eps), norms[1:]))) if theta_of is None else float(theta_of(norms, eps, dt))
     nsub, deg = hp.series_plan([theta], theta_max, table.theta)
     nsub, c = int(nsub[0]), polynomial(table, int(deg[0]))
     f = ko._eqm_factor(is_super, backwards) * (dt / nsub)
@@ -93,10 +94,12 @@ def series_step(ops, norms, eps, dt, v, table, theta_max, backwards, is_super=Fa
 
 class SeriesOracle:
     """Context manager: the sweeps of ``ko`` on ``prob`` take ``series_step`` (norm bounds ``bounds`` (K, 1 + L), ``table``,
-    ``theta_max``) instead of the exact step.  ``ko.step`` and ``prob.adjoint_ops`` are restored on exit."""
+    ``theta_max``) instead of the exact step.  ``ko.step`` and ``prob.adjoint_ops`` are restored on exit.  ``theta_of``:
+    ``series_step``'s plan from outside."""
 
-    def __init__(self, prob, bounds, table, theta_max):
+    def __init__(self, prob, bounds, table, theta_max, theta_of=None):
         self.prob, self.bounds, self.table, self.theta_max = prob, np.asarray(bounds), table, theta_max
+        self.theta_of = theta_of
 
     def __enter__(self):
         prob = self.prob
@@ -108,7 +111,7 @@ class SeriesOracle:
 
         def step(ops_k, eps_n, dt, state, is_super=False, backwards=False, use_scipy=False):
             return series_step(ops_k, self.bounds[who[id(ops_k)]], eps_n, dt, state, self.table, self.theta_max, backwards,
-                               is_super)
+                               is_super, self.theta_of)
 
         ko.step = step
         return self

@@ -253,7 +253,10 @@ def launched_instantiation(spec):
 # N = 5 (odd, padded), 16, 17, 64, 96; L = 1, 2, 3, 4; nt = 2, 3, 9; nt - 1 = chunk - 1, chunk, chunk + 1; every
 # instantiation kh_grad_items<L, 1> (N <= 64) and <L, 2> (N > 64)
 SHAPES = [(5, 1, 2), (5, 2, 3), (5, 4, 9), (16, 1, 9), (16, 2, CHUNK), (17, 1, CHUNK + 1), (17, 4, CHUNK + 2), (17, 3, 9),
-          (64, 1, 9), (64, 2, 9), (64, 4, 5), (96, 1, 5), (96, 2, 4), (96, 3, 3), (96, 4, 3)]
+          (64, 1, 9), (64, 2, 9), (64, 4, 5), (96, 1, 5), (96, 2, 4), (96, 3, 3), (96, 4, 3),
+          # G = 3 row blocks at a multiple of 16 and just above it (the register-operand path, kb < G); G = 5 (N = 65 .. 80:
+          # only wave 0 owns a second block, the waves 1 .. 3 skip it)
+          (48, 2, 9), (49, 3, 5), (65, 1, 5), (80, 2, 4)]
 
 
 @pytest.mark.gpu
